@@ -10,12 +10,30 @@ Metric (BASELINE.json / SURVEY.md section 8d): audio-seconds/sec of one training
 on the LibriSpeech-shaped configuration cfg3: 5 x BiGRU hidden=1024, batch 32 clips/GPU of 12-15 s, bf16 activations /
 MFMA operands with fp32 master weights, statistics, gate math and CTC; synthetic 16 kHz log-spectrograms already
 resident in HBM when the timed region starts; weak scaling (32 clips per GPU).  Audio seconds = true (unpadded) frames
-x 10 ms.  One JSON line is printed by rank 0; it also carries
+x 10 ms.  One JSON line is printed by rank 0.
+
+A plain run does only what that line's headline needs: set-up, `--warmup` steps, `--steps` timed steps, the optional output dump
+and the line itself, whose `ms_per_step` is the mean time of one timed step.  `--full` adds every other leg: the stock PyTorch-ROCm
+leg, the other configurations, the CPU baseline, the comparison with the reference's loss and (under DDP) the no_sync leg; their
+time limits shrink so that the whole `--full` run ends within `--full-budget` seconds (a CPU leg cut short reports its short sample).
+
+`--dump-outputs DIR` writes what the last timed step computed, as float32 / float64 `.npy` files: `loss`, every entry of the
+model's state after the optimizer step (`state.<name>`) and every parameter gradient (`grad.<name>`).  Arrays of more than
+65536 elements are dumped as a fixed, seeded sample of up to 65536 of their elements (the same indices in every run), so two builds
+run with the same arguments can be compared output for output.  The inputs are the same in every run.  On cfg3, the default
+configuration, what the timed path computes from them is too: two runs of one build write byte-identical files
+(tests/test_gpu_bench.py).  The other configurations are not checked for that.
+
+The line always carries
 
   "roofline":     the dominant kernel (the persistent recurrent sweep k_rnn_persist_bwd / _fwd: ONE launch per layer and
                   sweep): algorithmic h2h FLOPs of a sweep over valid frames / average launch duration measured live with
                   HIP events on the launch stream, against the dense MFMA peak of the compute dtype (bf16 2.5 PFLOP/s, fp32
                   157.3 TFLOP/s, /opt/skills/guides/MI355X_MICROARCH.md);
+  "ms_per_step_median", "step_time_distribution": per-step HIP-event times of the timed steps (the mean is `ms_per_step`);
+
+and with `--full` also
+
   "cpu_baseline": oracle/ds2_torch_port.py (a port of the reference's model.py:214-249: the same torch calls in the same order)
                   timed on the host cores of THIS box (rank 0, N=1 only), fp32, all usable cores.  For cfg3 -- the metric's
                   configuration -- `value` is ONE training step at the bench's own full batch (32 clips of 12-15 s; minutes of CPU
@@ -27,7 +45,7 @@ x 10 ms.  One JSON line is printed by rank 0; it also carries
                   batch, the same parameters and the same device (N=1, rank 0; --no-stock-baseline skips it), and value / its value;
   "ctc_loss_ref" / "ctc_loss_rel_diff": the reference's fp32 CPU loss of this very batch and parameters (generated offline from the
                   real reference, tests/golden/) against the first timed-path loss -- the line proves it computed the same thing;
-  "ms_per_step_median", "step_time_distribution": per-step HIP-event times of the timed steps (the mean is `ms_per_step`).
+  "other_configs": cfg5a / cfg5b / cfg2 timed in child processes after the headline (cfg3 only).
 
 With `--gpus N` and no launcher environment (WORLD_SIZE unset) the script re-executes itself under torch.distributed.run
 with N ranks on 127.0.0.1.
@@ -92,17 +110,18 @@ def train_flops(cfg_name, lengths):
 PARAM_SEED = {"cfg2": 2202, "cfg3": 3303, "cfg5a": 5505, "cfg5b": 6606}     # tests/golden/make_fullsize_golden.py
 
 
-def load_reference_loss(cfg_name, model):
+def load_reference_loss(cfg_name, model, read_loss=True):
     """Random-init weights of the architecture, drawn the way the full-size reference fixture draws them (synth.synth_params, the
     fixture's seed), so that the FIRST step of the bench on rank 0's batch is exactly the step the reference's own model.py was run
     on when tests/golden/full/<config>.npz was generated (make_fullsize_golden.py: same batch seed, same parameters): its CTC loss
-    is the `ctc_loss_ref` of the JSON line.  Returns {"fp32": loss of the reference as shipped, "autocast": under bf16 autocast}."""
+    is the `ctc_loss_ref` of the JSON line.  Returns {"fp32": loss of the reference as shipped, "autocast": under bf16 autocast}, or
+    None when read_loss is False (a plain run: the parameters are loaded all the same)."""
     from deepspeech.pytorch_amd import synth
     shapes = {k: tuple(v.shape) for k, v in model.state_dict().items()}
     P = synth.synth_params(shapes, PARAM_SEED[cfg_name])
     model.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in P.items()}, strict=True)
     path = os.path.join(ROOT, "tests", "golden", "full", cfg_name + ".npz")
-    if not os.path.exists(path):
+    if not read_loss or not os.path.exists(path):
         return None
     z = np.load(path)
     return {"fp32": float(z["loss"]), "autocast": float(z["loss_ac"]) if "loss_ac" in z.files else None}
@@ -118,7 +137,7 @@ def run_native(args, rank, world, device):
     mc = configs.BiDirectionalConfig(rnn_type=rt, hidden_size=H, hidden_layers=L) if bi else \
         configs.UniDirectionalConfig(rnn_type=rt, hidden_size=H, hidden_layers=L, lookahead_context=20)
     model = DeepSpeech(configs.LABELS, mc, "bf16" if dtype == "bf16" else 32, configs.AdamConfig(), configs.SpectConfig())
-    ref = load_reference_loss(args.config, model)          # parameters of the full-size reference fixture (same on every rank)
+    ref = load_reference_loss(args.config, model, args.full)    # parameters of the full-size reference fixture (same on every rank)
     model = model.to(device)
     model.train()
     lengths, batch = build_batch(args.config, rank, device)
@@ -173,13 +192,15 @@ def run_native(args, rank, world, device):
                   "how": "HIP events at every step start on the step's stream (device time between consecutive steps)"} if per_step else None
     log("timed region done: %.1f ms/step" % (dt / args.steps * 1e3))
     last_loss = float(last.detach().item())
+    if args.dump_outputs and rank == 0:           # before anything else steps the model again
+        dump_outputs(args.dump_outputs, last, model.state_dict(), model.named_parameters())
     # ---- data-parallel evidence (world > 1, or DS2_FORCE_DDP=1 on one GPU): what the exchange costs, and that the ranks are N GPUs
     dp_info = None
     is_ddp = isinstance(step_mod, torch.nn.parallel.DistributedDataParallel)
     if world > 1 or is_ddp:
         import torch.distributed as dist_
         dp_info = {"wrapper": type(step_mod).__name__}
-        if is_ddp:
+        if is_ddp and args.full:
             # the same step with the gradient exchange switched off (DDP.no_sync): step time with - without = what the all-reduce
             # costs the step after overlap (exposed tail + contention under the sweeps), measured, not modelled
             k2 = max(3, min(args.steps, 10))
@@ -296,7 +317,37 @@ def run_stock(args, rank, world, device):
         last = port.train_step(batch, opt, ac)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, dict(port.P, **port.buf), port.P.items())
     return lengths, dt, first if first is not None else float("nan"), float(last.detach().item()), None
+
+
+DUMP_SAMPLE = 1 << 16          # larger arrays are dumped as a fixed, seeded sample of this many elements
+DUMP_LIMIT = 64 << 20          # bytes of one dump, all files together
+
+
+def dump_outputs(out_dir, loss, state, params):
+    """--dump-outputs: the loss of the last timed step, the state after it and the parameter gradients as DIR/<name>.npy (float32;
+    float64 for integer buffers).  The sample indices of a large array depend only on the tensor's name and size, so a parameter and
+    its gradient are sampled at the same elements."""
+    import zlib
+    arrays = {"loss": loss}
+    arrays.update(("state." + k, v) for k, v in state.items())
+    arrays.update(("grad." + k, p.grad) for k, p in params if p.grad is not None)
+    os.makedirs(out_dir, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t.float() if t.is_floating_point() and t.element_size() <= 4 else t.double()
+        if t.numel() > DUMP_SAMPLE:
+            rs = np.random.RandomState(zlib.crc32(("%s:%d" % (name.split(".", 1)[-1], t.numel())).encode()))
+            idx = np.unique(rs.randint(0, t.numel(), size=DUMP_SAMPLE))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, "the output dump would exceed %d bytes" % DUMP_LIMIT
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("wrote %d arrays (%.1f MB) to %s" % (len(arrays), total / 2 ** 20, out_dir))
 
 
 def usable_cores():
@@ -318,18 +369,32 @@ def log(msg):
 _T0 = time.perf_counter()
 
 
+LEG_MIN_S = 20          # a --full leg that would get less than this is skipped
+LEG_MARGIN_S = 15       # kept back from each leg for the parent's own exit
+
+
+def leg_limit(args, own_limit):
+    """Time limit of one --full leg in seconds: its own, cut to what is left of --full-budget; None when too little is left."""
+    left = args.full_budget - (time.perf_counter() - _T0) - LEG_MARGIN_S
+    limit = int(min(own_limit, left))
+    return limit if limit >= LEG_MIN_S else None
+
+
 def other_config_subprocess(args, cfg):
     """`bench.py --config <cfg>` (native path, a few steps, no baselines) in a child process under a time limit: the configurations
     the driver does not time itself (cfg2: the fp32 parity configuration; cfg5a / cfg5b: 7 x LSTM-1280, batch 64) ride along with the
     headline line as `other_configs`, timed after it and outside `value`."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", str(args.other_steps), "--warmup", "3",
+    cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--steps", str(args.other_steps), "--warmup", "3", "--full",
            "--no-cpu-baseline", "--no-stock-baseline", "--no-other-configs"]
     env = dict(os.environ)
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
+    limit = leg_limit(args, args.other_timeout)
+    if limit is None:
+        return {"error": "skipped: the --full budget of %d s was spent" % args.full_budget}
     try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.other_timeout, env=env)
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit, env=env)
         j = _last_json_line(r.stdout)
         if j is None:
             return {"error": (r.stderr.strip().splitlines() or ["?"])[-1][:200]}
@@ -341,7 +406,7 @@ def other_config_subprocess(args, cfg):
                 "roofline_kernel": rf.get("kernel"), "roofline_frac": rf.get("frac"), "us_per_time_step": rf.get("us_per_time_step"),
                 "recurrent_kernels": rf.get("recurrent_kernels"), "whole_step_frac_of_mfma_roofline": rf.get("whole_step_frac_of_mfma_roofline")}
     except subprocess.TimeoutExpired:
-        return {"error": "exceeded its %d s limit" % args.other_timeout}
+        return {"error": "exceeded its %d s limit" % limit}
 
 
 def _last_json_line(text):
@@ -361,7 +426,10 @@ def cpu_baseline_subprocess(args):
     full = args.cpu_full
     cmd = [sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--config", args.config,
            "--cpu-clips", str(args.cpu_clips), "--cpu-frames", str(args.cpu_frames), "--cpu-full", "1" if full else "0"]
-    limit = args.cpu_timeout if args.cpu_timeout > 0 else (1200 if full else 170)
+    limit = leg_limit(args, args.cpu_timeout if args.cpu_timeout > 0 else (1200 if full else 170))
+    if limit is None:
+        return {"value": None, "unit": "audio-seconds/sec", "cores": usable_cores(), "kind": "port",
+                "sample": "skipped: the --full budget of %d s was spent" % args.full_budget}
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
         j = _last_json_line(r.stdout)
@@ -389,8 +457,12 @@ def stock_baseline_subprocess(args):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     base = {"impl": "stock-pytorch-rocm", "unit": "audio-seconds/sec", "steps": args.stock_steps, "warmup": args.stock_warmup}
+    limit = leg_limit(args, args.stock_timeout)
+    if limit is None:
+        base.update(value=None, note="skipped: the --full budget of %d s was spent" % args.full_budget)
+        return base
     try:
-        r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.stock_timeout, env=env)
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=limit, env=env)
         for line in r.stdout.splitlines()[::-1]:
             if line.startswith("{"):
                 j = json.loads(line)
@@ -399,7 +471,7 @@ def stock_baseline_subprocess(args):
                 return base
         base.update(value=None, note="stock leg failed: " + (r.stderr.strip().splitlines() or ["?"])[-1][:200])
     except subprocess.TimeoutExpired:
-        base.update(value=None, note="stock leg exceeded its %d s limit" % args.stock_timeout)
+        base.update(value=None, note="stock leg exceeded its %d s limit" % limit)
     return base
 
 
@@ -492,7 +564,14 @@ def main():
     ap.add_argument("--other-configs", default="cfg5a,cfg5b,cfg2", help="configurations timed after the headline (N=1, --config cfg3 only)")
     ap.add_argument("--other-steps", type=int, default=10)
     ap.add_argument("--other-timeout", type=int, default=120)
+    ap.add_argument("--full", action="store_true", help="besides the headline: the stock PyTorch-ROCm leg, the other configurations, the "
+                    "CPU baseline, the comparison with the reference's loss and the DDP no_sync leg (a plain run times the steps only)")
+    ap.add_argument("--full-budget", type=int, default=540, help="seconds a --full run may take in all: the limits of its extra legs "
+                    "shrink to fit (default 540)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.cpu_full < 0:
         args.cpu_full = 1 if args.config == "cfg3" else 0
     if args.cpu_baseline_only:
@@ -553,7 +632,7 @@ def main():
     if step_stats is not None:
         out["ms_per_step_median"] = step_stats["median_ms"]
         out["step_time_distribution"] = step_stats
-    if loss_ref is not None and first_loss == first_loss:
+    if loss_ref is not None and first_loss == first_loss:          # --full only (load_reference_loss)
         # BASELINE.json's metric is "audio-s/s + CTC loss vs ref": the first step runs on the full-size fixture's parameters and
         # (on rank 0) its batch, so its loss is directly comparable with the reference's own model.py on the CPU
         ref_mode = loss_ref["autocast"] if (dtype == "bf16" and loss_ref.get("autocast") is not None) else loss_ref["fp32"]
@@ -567,7 +646,7 @@ def main():
         out["roofline"] = roofline
     if dp_info is not None:
         out["data_parallel"] = dp_info
-    if rank == 0 and world == 1 and not args.stock and not args.no_stock_baseline:
+    if args.full and rank == 0 and world == 1 and not args.stock and not args.no_stock_baseline:
         log("stock PyTorch-ROCm leg (subprocess, <= %d s)" % args.stock_timeout)
         sb = stock_baseline_subprocess(args)
         out["stock_baseline"] = sb
@@ -578,12 +657,12 @@ def main():
                                        "holds no published number for this metric")
     if args.no_cpu_baseline and args.no_stock_baseline:
         args.no_other_configs = True          # "just the number" runs (tools/*.sh, A/B scripts) skip every extra leg
-    if rank == 0 and world == 1 and not args.stock and not args.no_other_configs and args.config == "cfg3":
+    if args.full and rank == 0 and world == 1 and not args.stock and not args.no_other_configs and args.config == "cfg3":
         out["other_configs"] = {}
         for cfg in [c for c in args.other_configs.split(",") if c in CONFIGS and c != args.config]:
             log("other configuration %s (subprocess, <= %d s)" % (cfg, args.other_timeout))
             out["other_configs"][cfg] = other_config_subprocess(args, cfg)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stock:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.stock:
         log("cpu baseline leg (subprocess%s)" % (": short sample, then ONE full-shape step on the host cores -- minutes" if args.cpu_full else ""))
         out["cpu_baseline"] = cpu_baseline_subprocess(args)
     if rank == 0:

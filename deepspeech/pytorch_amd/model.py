@@ -986,7 +986,7 @@ class _HeadFn(torch.autograd.Function):
             [wfc.detach(), torch.zeros(Cp - Cc, Ht, device=wfc.device)], 0), H).t().to(dtype).contiguous())  # [H][Cp]
         dXh = ops.gemm_nt(dl, WpT)                                                                           # [R][H]
         dl_T, Xh_T = ops.transpose(dl), ops.transpose(Xh)
-        dW = ops.gemm_nt(dl_T, Xh_T, out_dtype=torch.float32, splitk=max(1, min(32, R // 2048)))             # [Cp][H]
+        dW = ops.gemm_nt_kslices(dl_T, Xh_T, max(1, min(32, R // 2048)))         # [Cp][H], the same in every run (no atomics)
         dX = torch.empty_like(dXh)
         dg, db = _bn_seq_bwd(dXh, X, dX, ctx.sv, R, Ht, H)
         return dX, dg, db, dW[:Cc, :Ht].contiguous(), None, None, None, None, None

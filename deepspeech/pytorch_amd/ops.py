@@ -166,6 +166,32 @@ def gemm_nt(A, B, bias=None, out_dtype=None, M=None, N=None, K=None, lda=None, l
     return out
 
 
+def gemm_nt_kslices(A, B, slices):
+    """C[M][N] f32 = A[M][K] * B[N][K]^T (2-D row-major A, B) with the contraction cut into `slices` K-slices of equal length (whole
+    64-element tiles) that run as the kernel's BATCH into a [slices (+1 for the rest of K)][M][N] scratch and are added in index order
+    (ds2_sum_slices): split-K with a fixed summation order, so the result is the same in every run (atomic split-K is not)."""
+    M, K = A.shape[-2], A.shape[-1]
+    N = B.shape[-2]
+    lda, ldb = A.stride(-2), B.stride(-2)
+    nkt = K // 64
+    for s_ in range(slices, max(1, slices // 2), -1):   # a slice count that divides the 64-element tiles leaves no rest
+        if nkt % s_ == 0 and K % 64 == 0:
+            slices = s_
+            break
+    Ks = (K // max(slices, 1)) // 64 * 64
+    if slices <= 1 or Ks == 0 or (M * N) % 4 != 0:
+        return gemm_nt(A, B, out_dtype=torch.float32)
+    rest = K - slices * Ks
+    ws = torch.empty((slices + (1 if rest else 0), M, N), dtype=torch.float32, device=A.device)
+    call("ds2_gemm_nt", dt(A), P(A), P(B), P(ws), None, M, N, Ks, lda, ldb, N, 1, slices, Ks, Ks, M * N, 0, 1, S())
+    if rest:
+        call("ds2_gemm_nt", dt(A), P(A[:, slices * Ks:]), P(B[:, slices * Ks:]), P(ws[slices]), None, M, N, rest, lda, ldb, N, 1, 1,
+             0, 0, 0, 0, 1, S())
+    out = torch.empty((M, N), dtype=torch.float32, device=A.device)
+    call("ds2_sum_slices", P(ws), P(out), M * N, ws.shape[0], S())
+    return out
+
+
 FP32_KSPLIT = __import__("os").environ.get("DS2_FP32_KSPLIT", "1") != "0"    # 0: every exact-fp32 product in one pass (round 5)
 
 

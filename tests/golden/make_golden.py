@@ -272,5 +272,42 @@ def main():
             os.path.getsize(path) / 1024))
 
 
+def host_results():
+    """--host-results: reference_host_results.json, what tests/test_host.py compares the drop-in decoder and validation_step with
+    (the reference's GreedyDecoder.convert_to_strings on the test's random label sequences; WER / CER that validation_step logs
+    with the reference's GreedyDecoder / WordErrorRate / CharErrorRate on the gru_bi_mid fixture)."""
+    ns = ref_harness.load_reference()
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from deepspeech_pytorch.validation import CharErrorRate, WordErrorRate
+    from fixtures import Fixture
+    from test_host import build_model
+    out = {"about": "Results of the reference's own GreedyDecoder.convert_to_strings (decoder.py) and of validation_step with its "
+                    "GreedyDecoder / WordErrorRate / CharErrorRate (validation.py), recorded on the inputs of "
+                    "tests/test_host.py (make_golden.py --host-results)"}
+    rs = np.random.RandomState(0)
+    seqs = torch.from_numpy(rs.randint(0, 29, size=(6, 40)))
+    sizes = torch.tensor([40, 33, 21, 7, 1, 0])
+    dec = ns.GreedyDecoder(ns.labels)
+    for rr in (False, True):
+        strings, offsets = dec.convert_to_strings(seqs, sizes, remove_repetitions=rr, return_offsets=True)
+        out["convert_to_strings_remove_repetitions_%s" % str(rr).lower()] = {
+            "strings": strings, "offsets": [[o.tolist() for o in per] for per in offsets], "offsets_dtype": str(offsets[0][0].dtype)}
+    fx = Fixture("gru_bi_mid")
+    m = build_model(fx).eval()
+    m.attach_evaluation(dec, WordErrorRate(decoder=dec, target_decoder=dec), CharErrorRate(decoder=dec, target_decoder=dec))
+    probs, out_sizes = torch.from_numpy(fx.z["eval_probs"]), torch.from_numpy(fx.z["output_lengths"].copy())
+    m.forward = lambda x, lengths, hs=None: (probs, out_sizes, None)
+    logged = {}
+    m.log = lambda k, v, **kw: logged.__setitem__(k, v)
+    inputs, targets, pct, tsz = fx.batch()
+    m.validation_step((torch.from_numpy(inputs), torch.from_numpy(targets), torch.from_numpy(pct.copy()), torch.from_numpy(tsz)), 0)
+    out["validation_step_gru_bi_mid"] = {k: float(v) for k, v in logged.items()}
+    with open(os.path.join(HERE, "reference_host_results.json"), "w") as f:
+        json.dump(out, f, indent=1)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["--host-results"]:
+        host_results()
+    else:
+        main()

@@ -82,6 +82,23 @@ def test_gemm_nt_fp32_k_slices_are_exact_and_repeatable(M, N, K):
     assert relerr(np64(one), np64(got)) < 1e-5
 
 
+@pytest.mark.parametrize("dtype,K", [(torch.bfloat16, 24064), (torch.bfloat16, 24000), (torch.float32, 8320)])
+def test_gemm_nt_kslices_matches_and_is_repeatable(dtype, K):
+    """The head's weight gradient (Cp = 32 rows, H = 1024 columns, K = the frames of the batch): K-slices as the kernel's batch,
+    with the rest of K as one more slice when the tiles do not divide evenly, added in index order -- against float64 and
+    bit-identical from launch to launch (atomic split-K is not)."""
+    M, N = 32, 1024
+    rs = np.random.RandomState(K)
+    A, B = rs.standard_normal((M, K)), rs.standard_normal((N, K))
+    o = ops()
+    Ad, Bd = cu(A, dtype), cu(B, dtype)
+    got = o.gemm_nt_kslices(Ad, Bd, 11)
+    ref = rnd(A, dtype) @ rnd(B, dtype).T
+    assert relerr(np64(got), ref) < 1e-5
+    for _ in range(3):
+        assert torch.equal(o.gemm_nt_kslices(Ad, Bd, 11), got)
+
+
 @pytest.mark.parametrize("coresident", [False, True])
 @pytest.mark.parametrize("M,ms,N,K,sk", [(3072, 2048, 1024, 1536, 1), (192, 128, 96, 640, 1), (160, 96, 64, 4096, 4)])
 def test_gemm_nt_rows2(coresident, M, ms, N, K, sk):

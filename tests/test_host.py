@@ -124,46 +124,63 @@ def test_model_carries_the_reference_evaluation_attributes():
     assert not any(k.startswith(("criterion", "inference_softmax", "wer", "cer")) for k in m.state_dict())
 
 
+def _reference_host_results():
+    """What the reference's own decoder and metrics produced on these tests' inputs (tests/golden/make_golden.py --host-results)."""
+    import json
+    with open(os.path.join(ROOT, "tests", "golden", "reference_host_results.json")) as f:
+        return json.load(f)
+
+
 def test_greedy_decoder_string_building_equals_the_reference():
     """convert_to_strings / process_string (host side; the metrics use them for the TARGET strings) against the reference's
-    GreedyDecoder on random label sequences, with and without repeat removal."""
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    import ref_harness
-    if not ref_harness.reference_available():
-        pytest.skip("reference tree not present")
-    ns = ref_harness.load_reference()
+    GreedyDecoder on random label sequences, with and without repeat removal (its results recorded in tests/golden)."""
     from deepspeech.pytorch_amd import configs
     from deepspeech.pytorch_amd.decoder import GreedyDecoder
-    ref, own = ns.GreedyDecoder(ns.labels), GreedyDecoder(configs.LABELS)
-    assert configs.LABELS == ns.labels
+    golden = _reference_host_results()
+    own = GreedyDecoder(configs.LABELS)
     rs = np.random.RandomState(0)
     seqs = torch.from_numpy(rs.randint(0, 29, size=(6, 40)))
     sizes = torch.tensor([40, 33, 21, 7, 1, 0])
     for rr in (False, True):
-        a, ao = ref.convert_to_strings(seqs, sizes, remove_repetitions=rr, return_offsets=True)
+        ref = golden["convert_to_strings_remove_repetitions_%s" % str(rr).lower()]
+        a = ref["strings"]
+        ao = [[torch.tensor(o, dtype=getattr(torch, ref["offsets_dtype"].split(".")[-1])) for o in per] for per in ref["offsets"]]
         b, bo = own.convert_to_strings(seqs, sizes, remove_repetitions=rr, return_offsets=True)
         assert a == b
+        assert len(ao) == len(bo)
         for x, y in zip(ao, bo):
             assert torch.equal(x[0], y[0])
 
 
-def test_validation_step_drives_reference_decoder_and_metrics():
-    """validation_step with the REFERENCE's GreedyDecoder / WordErrorRate / CharErrorRate objects (through the stubs of
-    tests/golden/ref_harness.py) on the reference's own eval probabilities: same transcripts, WER / CER logged."""
+def test_validation_step_drives_reference_decoder_and_metrics(monkeypatch):
+    """validation_step with decoder / WordErrorRate / CharErrorRate objects of the reference's interfaces on the reference's own
+    eval probabilities: the WER / CER it logs are the ones the reference's own GreedyDecoder / WordErrorRate / CharErrorRate logged
+    on this batch (recorded in tests/golden).  That is the check with weight here: the module and transcript checks below cover only
+    the model's import hook and the test's own pieces.  The class takes its metric classes from the reference's
+    deepspeech_pytorch.validation whenever that module is importable (a stand-in module here)."""
     import sys
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    import ref_harness
-    if not ref_harness.reference_available():
-        pytest.skip("reference tree not present")
-    ns = ref_harness.load_reference()
-    from deepspeech_pytorch.validation import CharErrorRate, WordErrorRate
+    import types
+    from deepspeech.pytorch_amd import decoder as own
+    golden = _reference_host_results()["validation_step_gru_bi_mid"]
+    pkg, val = types.ModuleType("deepspeech_pytorch"), types.ModuleType("deepspeech_pytorch.validation")
+    val.WordErrorRate = type("WordErrorRate", (own.WordErrorRate,), {"__module__": val.__name__})
+    val.CharErrorRate = type("CharErrorRate", (own.CharErrorRate,), {"__module__": val.__name__})
+    pkg.validation = val
+    monkeypatch.setitem(sys.modules, "deepspeech_pytorch", pkg)
+    monkeypatch.setitem(sys.modules, "deepspeech_pytorch.validation", val)
+
+    class HostGreedyDecoder(own.GreedyDecoder):
+        """decode() of the reference's interface on host tensors (the class's own decode runs on the device): the arg-max label of
+        every frame, then the host-side string building with repeats collapsed."""
+        def decode(self, probs, sizes=None):
+            return self.convert_to_strings(probs.argmax(dim=-1), sizes, remove_repetitions=True, return_offsets=True)
+
     fx = Fixture("gru_bi_mid")
     m = build_model(fx).eval()
-    from deepspeech.pytorch_amd import model as own_model
-    assert type(m.wer).__module__ == "deepspeech_pytorch.validation"      # the reference's classes are picked up when importable
-    dec = ns.GreedyDecoder(ns.labels)
-    m.attach_evaluation(dec, WordErrorRate(decoder=dec, target_decoder=dec), CharErrorRate(decoder=dec, target_decoder=dec))
+    # the model's import hook only: the module is the stand-in above, so this says nothing about the reference's own classes
+    assert type(m.wer).__module__ == "deepspeech_pytorch.validation"
+    dec = HostGreedyDecoder(fx.labels)
+    m.attach_evaluation(dec, val.WordErrorRate(decoder=dec, target_decoder=dec), val.CharErrorRate(decoder=dec, target_decoder=dec))
     probs = torch.from_numpy(fx.z["eval_probs"])
     sizes = torch.from_numpy(fx.z["output_lengths"].copy())
     m.forward = lambda x, lengths, hs=None: (probs, sizes, None)          # the HIP forward is covered by the -m gpu tests
@@ -173,6 +190,10 @@ def test_validation_step_drives_reference_decoder_and_metrics():
     out = m.validation_step((torch.from_numpy(inputs), torch.from_numpy(targets), torch.from_numpy(pct.copy()), torch.from_numpy(tsz)), 0)
     assert out is None                                                     # model.py:251-271 returns nothing
     assert set(logged) == {"wer", "cer"} and all(np.isfinite(v) and v > 0 for v in logged.values())
+    for k in ("wer", "cer"):
+        assert abs(float(logged[k]) - golden[k]) <= 1e-6 * abs(golden[k]), (k, float(logged[k]), golden[k])   # the reference sums in fp32
+    # the test's own host decoder against the reference's transcripts: a check of the fixture and of convert_to_strings, not of the
+    # class's device decoder (that one is covered by the -m gpu tests)
     strings, _ = dec.decode(probs, sizes)
     assert [s[0] for s in strings] == fx.meta["transcripts"]
 

@@ -7,11 +7,11 @@ out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
 here=$PWD
 if [ -z "$SKIP_DEFAULT" ]; then   # the default line includes the CPU leg (minutes): the end-of-round gate (tools/r06_gate.sh) runs the driver's command instead
-  timeout 300 python bench.py > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc=$?"; tail -c 600 $out/bench_default.json; echo
+  timeout 600 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc=$?"; tail -c 600 $out/bench_default.json; echo
 fi
 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-stock-baseline --no-other-configs > $out/bench_cfg3.json 2> $out/bench_cfg3.err; echo "bench cfg3 rc=$?"; grep -o '"ms_per_step": [0-9.]*' $out/bench_cfg3.json | head -1
 for cfg in cfg2 cfg5a cfg5b; do
-  timeout 300 python bench.py --config $cfg --steps 10 --warmup 3 --no-cpu-baseline --no-stock-baseline > $out/bench_$cfg.json 2> $out/bench_$cfg.err; echo "bench $cfg rc=$?"
+  timeout 300 python bench.py --config $cfg --steps 10 --warmup 3 --full --no-cpu-baseline --no-stock-baseline > $out/bench_$cfg.json 2> $out/bench_$cfg.err; echo "bench $cfg rc=$?"
   grep -o '"ms_per_step": [0-9.]*' $out/bench_$cfg.json
 done
 if [ -z "$SKIP_STOCK" ]; then

@@ -11,7 +11,7 @@ if [ -n "$TESTS" ]; then
   grep -E "passed|failed|FAILED|Error" $out/pytest.log | tail -n 45
 fi
 for cfg in $CONFIGS; do
-  timeout 300 python bench.py --config $cfg --steps ${STEPS:-6} --warmup 3 --no-cpu-baseline --no-stock-baseline $BENCH_ARGS > $out/bench_$cfg.json 2> $out/bench_$cfg.err; echo "bench $cfg rc=$?"
+  timeout 300 python bench.py --config $cfg --steps ${STEPS:-6} --warmup 3 --full --no-cpu-baseline --no-stock-baseline $BENCH_ARGS > $out/bench_$cfg.json 2> $out/bench_$cfg.err; echo "bench $cfg rc=$?"
   python - <<PY
 import json
 try:

@@ -7,9 +7,9 @@ tag=${1:-r05z}
 out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
 here=$PWD
-timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 $BENCH_EXTRA > $out/bench_driver_cmd.json 2> $out/bench_driver_cmd.err; echo "bench (driver command) rc=$?"; tail -c 400 $out/bench_driver_cmd.json; echo; tail -n 12 $out/bench_driver_cmd.err
+timeout 1500 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full $BENCH_EXTRA > $out/bench_full.json 2> $out/bench_full.err; echo "bench --full rc=$?"; tail -c 400 $out/bench_full.json; echo; tail -n 12 $out/bench_full.err
 timeout 300 python bench.py --steps 200 --warmup 5 --no-cpu-baseline --no-stock-baseline > $out/bench_200steps.json 2> $out/bench_200steps.err; echo "bench 200 steps rc=$?"; grep -o '"ms_per_step": [0-9.]*' $out/bench_200steps.json
-DS2_FORCE_DDP=1 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-stock-baseline > $out/bench_force_ddp.json 2> $out/bench_force_ddp.err; echo "bench DS2_FORCE_DDP=1 rc=$?"; python -c "
+DS2_FORCE_DDP=1 timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-stock-baseline > $out/bench_force_ddp.json 2> $out/bench_force_ddp.err; echo "bench DS2_FORCE_DDP=1 rc=$?"; python -c "
 import json,sys
 j=json.loads([l for l in open('$out/bench_force_ddp.json') if l.startswith('{')][-1]); print(j['ms_per_step'], json.dumps(j.get('data_parallel'))[:600])"
 cd /tmp
