@@ -4,6 +4,7 @@ decoder.py:117-181; ``deepspeech_pytorch.validation.WordErrorRate / CharErrorRat
 
 The arg-max + repeat collapse + blank removal of ``decode`` runs on the device (ds2_greedy_decode); only the surviving
 labels travel to the host.  String building and the edit distance are host-side bookkeeping, as in the reference.
+``BeamCTCDecoder`` (decoder.py:56-117) runs CTC prefix beam search on the device (ds2_beam_decode), without a language model.
 When the reference's metric classes are importable the model uses THEM (with this decoder inside); the classes below are the
 stand-ins for images without torchmetrics / Levenshtein."""
 import torch
@@ -50,6 +51,44 @@ class GreedyDecoder:
         toks, offs = ops.greedy_decode(probs, sizes, self.blank_index)
         strings = [[''.join(' ' if v == self.space_index else self.int_to_char[v] for v in t)] for t in toks]
         return strings, [[o.to(torch.int)] for o in offs]
+
+
+class BeamCTCDecoder:
+    """CTC prefix beam search with the reference's interface (``deepspeech_pytorch.decoder.BeamCTCDecoder``, decoder.py:56-117),
+    run on the device (ds2_beam_decode) instead of the ctcdecode library on a host copy.  No language model: ``lm_path`` must be
+    empty; ``alpha`` / ``beta`` are ignored without one (as in ctcdecode) and ``num_processes`` is ignored (no CPU threads)."""
+
+    def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
+                 num_processes=4, blank_index=0):
+        if lm_path:
+            raise ValueError("BeamCTCDecoder: language-model scoring (lm_path=%r) is not implemented; the device beam search "
+                             "runs without a language model (lm_path=None)" % (lm_path,))
+        self.labels = labels
+        self.int_to_char = dict((i, c) for (i, c) in enumerate(labels))
+        self.blank_index = blank_index
+        space_index = len(labels)          # decoder.py:36-38
+        if ' ' in labels:
+            space_index = labels.index(' ')
+        self.space_index = space_index
+        self.lm_path, self.alpha, self.beta = lm_path, alpha, beta
+        self.cutoff_top_n, self.cutoff_prob, self.beam_width = int(cutoff_top_n), float(cutoff_prob), int(beam_width)
+        self.num_processes = num_processes
+
+    def decode_beams(self, probs, sizes=None):
+        """(strings, offsets, scores): strings[n] = beam_width transcripts (best first), offsets[n] = the matching int tensors of
+        frames, scores = host (N, beam_width) float tensor of -log p (lower is better; +inf where no beam is alive)."""
+        if not probs.is_cuda:              # the reference's run_transcribe passes out.cpu() (inference.py:96-98)
+            probs = probs.to("cuda")
+        toks, offs, scores = ops.beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob)
+        strings = [[''.join(self.int_to_char[v] for v in t) for t in beams] for beams in toks]
+        offsets = [[o.to(torch.int) for o in beams] for beams in offs]
+        return strings, offsets, scores
+
+    def decode(self, probs, sizes=None):
+        """probs: (N, T', C) probabilities (device or host tensor).  Returns (strings, offsets) in the reference's shapes:
+        strings[n] is a list of beam_width transcripts, offsets[n] the matching list of int tensors."""
+        strings, offsets, _ = self.decode_beams(probs, sizes)
+        return strings, offsets
 
 
 def _edit_distance(a, b):

@@ -858,6 +858,50 @@ def greedy_decode(scores, sizes, blank):
     return toks, offs
 
 
+BEAM_MAX_WIDTH, BEAM_MAX_TOP_N, BEAM_MAX_CLASSES = 256, 64, 8192     # ds2_beam_decode's limits
+
+
+def beam_decode(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob):
+    """CTC prefix beam search without a language model (ds2_beam_decode).  probs: (N, T', C) CUDA tensor of probabilities (any
+    strides with a contiguous class dimension); sizes: [N] int tensor or None (= T').  Returns host lists: tokens[n][b] (labels
+    of beam b, best first), offsets[n][b] (int tensor of their frames) and a host (N, B) float tensor of scores (-log p, ctcdecode's
+    convention; +inf where fewer than B beams are alive).  Only the surviving labels, their frames and the scores travel."""
+    N, T, Cc = probs.shape
+    B, top_n = int(beam_width), int(cutoff_top_n)
+    if not 1 <= B <= BEAM_MAX_WIDTH:
+        raise ValueError("beam_width must be in [1, %d], got %d" % (BEAM_MAX_WIDTH, B))
+    if top_n < 1 or min(top_n, Cc) > BEAM_MAX_TOP_N:
+        raise ValueError("min(cutoff_top_n, number of classes) must be in [1, %d], got cutoff_top_n=%d with %d classes"
+                         % (BEAM_MAX_TOP_N, top_n, Cc))
+    if not 1 <= Cc <= BEAM_MAX_CLASSES:
+        raise ValueError("the beam decoder supports up to %d classes, got %d" % (BEAM_MAX_CLASSES, Cc))
+    if not 0 <= blank < Cc:
+        raise ValueError("blank index %d out of range for %d classes" % (blank, Cc))
+    if N == 0 or T == 0:             # no frames: the only beam is the empty string, score 0
+        scores = torch.full((N, B), float("inf"))
+        scores[:, 0] = 0.0
+        return [[[] for _ in range(B)] for _ in range(N)], \
+            [[torch.zeros(0, dtype=torch.int32) for _ in range(B)] for _ in range(N)], scores
+    if probs.dtype != torch.float32:
+        probs = probs.float()
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    dev = probs.device
+    sz = sizes.to(dev, torch.int32) if sizes is not None else None
+    buf = torch.empty((2, N, B, T), dtype=torch.int32, device=dev)
+    lens = torch.empty((N, B), dtype=torch.int32, device=dev)
+    scores = torch.empty((N, B), dtype=torch.float32, device=dev)
+    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
+    call("ds2_beam_decode", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob),
+         P(buf[0]), P(buf[1]), P(lens), P(scores), P(ws), S())
+    ln = lens.cpu().numpy()
+    width = max(int(ln.max()), 1)
+    host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
+    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(B)] for n in range(N)]
+    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(B)] for n in range(N)]
+    return toks, offs, scores.cpu()
+
+
 CTC_RECURSION = 0    # tests / A-B tools: 0 = pair tiles (default), 1 = always the four-wave recursion kernel, 2 = the one-wave kernel up to 255 labels, 3 = rounds 3-5
 
 

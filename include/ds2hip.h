@@ -319,6 +319,17 @@ int ds2_spectrogram(const float* wav, long ldw, const int* nsamples, int N, int 
 int ds2_greedy_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank,
                       int* tokens, int* offsets, int* counts, ds2_stream_t stream);
 
+/* ---- CTC prefix beam search on the device, no language model (BeamCTCDecoder, reference decoder.py:56-117) ---------------
+ * x[n*stride_n + t*stride_t + c] f32 probabilities, C <= 8192; sizes [N] int32 on the device (null = T); 1 <= B <= 256,
+ * cutoff_top_n >= 1 with min(cutoff_top_n, C) <= 64; cutoff_prob < 1 also cuts each frame at that cumulative probability.
+ * Outputs (device): tokens / offsets [N][B][T] int32 (the first lens[n][b] entries of row (n, b): label index and its frame),
+ * lens [N][B] int32, scores [N][B] f32 = -log p of the prefix (ctcdecode's convention; +inf for a rank without a beam).
+ * ws: ds2_beam_ws_bytes(N, T, B) bytes of device memory, 256-byte aligned (host-only size query). */
+long ds2_beam_ws_bytes(int N, int T, int B);
+int ds2_beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                    int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws,
+                    ds2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
