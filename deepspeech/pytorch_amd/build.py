@@ -15,13 +15,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(CSRC, "_obj")
 LIB = os.path.join(HERE, "libds2hip.so")
-SOURCES = ["ds2_norm.hip", "ds2_gemm.hip", "ds2_gemm8.hip", "ds2_rnn.hip", "ds2_rnn_persist.hip", "ds2_rnn_persist_gru.hip", "ds2_rnn_persist_lstm.hip",
-           "ds2_rnn_persist_rnn.hip", "ds2_rnn_persist2_bf16_800.hip", "ds2_rnn_persist2_bf16_1280.hip", "ds2_rnn_persist2_f32_800.hip",
-           "ds2_rnn_persist2_f32_1024.hip", "ds2_rnn_persist2_f32_1280.hip", "ds2_rnn_persist3_384.hip", "ds2_rnn_persist3_640.hip", "ds2_rnn_persist3_896.hip", "ds2_rnn_persist3_1152.hip", "ds2_rnn_persist3_1408.hip", "ds2_rnn_persist3_512.hip", "ds2_rnn_persist3_768.hip", "ds2_rnn_persist3_800.hip",
-           "ds2_rnn_persist3_1024.hip", "ds2_rnn_persist3_1280.hip", "ds2_rnn_persist3_1536.hip", "ds2_conv.hip", "ds2_ctc.hip", "ds2_seqops.hip", "ds2_decode.hip", "ds2_beam.hip", "ds2_optim.hip", "ds2_spect.hip"]
+SOURCES = ["ds2_norm.hip", "ds2_gemm.hip", "ds2_gemm8.hip", "ds2_rnn.hip", "ds2_rnn_persist.hip", "ds2_rnn_persist_gru.hip",
+           "ds2_rnn_persist_lstm.hip", "ds2_rnn_persist_rnn.hip", "ds2_conv.hip", "ds2_ctc.hip", "ds2_seqops.hip", "ds2_decode.hip",
+           "ds2_beam.hip", "ds2_optim.hip", "ds2_spect.hip"]
+# the general persistent recurrent kernels: instantiation source -> its table in ds2_rnn_persist_widths.h; one object per row
+INSTANCES = {"ds2_rnn_persist3_inst.hip": "DS2_PERSIST3_WIDTHS", "ds2_rnn_persist2_inst.hip": "DS2_PERSIST2_INSTANCES"}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-pass-failed"] + \
-    os.environ.get("DS2_EXTRA_HIPCC_FLAGS", "").split()
+FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", "-Wno-pass-failed"]
+FLAGS += os.environ.get("DS2_EXTRA_HIPCC_FLAGS", "").split()
 
 
 # ds2_rnn_persist_impl.h lands its fire-and-forget scalar loads (l2_touch) in one fixed SGPR; nothing else may name that register,
@@ -50,44 +51,42 @@ def _l2_sink_misuse(obj):
 
 
 def _stale(target, deps):
-    if not os.path.exists(target):
-        return True
-    t = os.path.getmtime(target)
-    return any(os.path.getmtime(d) > t for d in deps)
+    return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in deps)
+
+
+def _instance_rows(table):
+    """The rows of an X-macro table of ds2_rnn_persist_widths.h: the arguments of every line `X(...)` of its #define."""
+    text = open(os.path.join(CSRC, "ds2_rnn_persist_widths.h")).read()
+    body = re.search(r"^#define %s\(X\)((?:.*\\\n)*.*\n)" % table, text, re.M).group(1)
+    return [re.sub(r"\s", "", row) for row in re.findall(r"^\s*X\((.*?)\)\s*\\?$", body, re.M)]
 
 
 def build(force=False, verbose=True, probe=False):
     """probe=True: the instrumented library for tools/probe_rnn_persist.py (-DDS2_PROBE: in-kernel cycle counters and the
     DS2_PERSIST_DBG work-skipping masks) as libds2hip_probe.so -- never loaded by the product."""
-    global OBJ, LIB
-    obj_dir, lib_path, flags = OBJ, LIB, FLAGS
-    if probe:
-        obj_dir, lib_path, flags = OBJ + "_probe", LIB.replace("libds2hip.so", "libds2hip_probe.so"), FLAGS + ["-DDS2_PROBE"]
-    return _build(obj_dir, lib_path, flags, force, verbose)
+    return _build("_probe", ["-DDS2_PROBE"], force, verbose) if probe else _build("", [], force, verbose)
 
 
 def build_variant(name, extra_flags, force=False, verbose=False):
     """A/B builds (tools/ab_variants.py): the same sources with extra compiler flags (-DDS2_L2_AHEAD=4, -DDS2_CHUNK=8, ...) as
     libds2hip_<name>.so next to the shipping library -- never loaded by the product."""
     assert name.isidentifier() and name not in ("probe",), name
-    return _build(OBJ + "_" + name, LIB.replace("libds2hip.so", "libds2hip_%s.so" % name), FLAGS + list(extra_flags), force, verbose)
+    return _build("_" + name, extra_flags, force, verbose)
 
 
-def _build(OBJ, LIB, FLAGS, force, verbose):
-    os.makedirs(OBJ, exist_ok=True)
-    headers = [os.path.join(CSRC, "ds2_common.h"), os.path.join(CSRC, "ds2_rnn_persist_impl.h"), os.path.join(CSRC, "ds2_rnn_persist2_impl.h"), os.path.join(CSRC, "ds2_rnn_persist3_impl.h"),
-               os.path.join(HERE, "..", "..", "include", "ds2hip.h")]
-    jobs = []
-    for src in SOURCES:
-        s = os.path.join(CSRC, src)
-        o = os.path.join(OBJ, src.replace(".hip", ".o"))
-        if force or _stale(o, [s] + headers):
-            jobs.append((s, o))
+def _build(suffix, extra_flags, force, verbose):
+    obj_dir, lib_path, flags = OBJ + suffix, LIB.replace(".so", suffix + ".so"), FLAGS + list(extra_flags)
+    os.makedirs(obj_dir, exist_ok=True)
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "..", "include", "ds2hip.h")]
+    units = [(src, os.path.join(obj_dir, src.replace(".hip", ".o")), []) for src in SOURCES]
+    units += [(src, os.path.join(obj_dir, "%s_%s.o" % (src.replace("_inst.hip", ""), re.sub(r"\W+", "_", row))), ["-DDS2_INST=" + row])
+              for src, table in INSTANCES.items() for row in _instance_rows(table)]
+    jobs = [(os.path.join(CSRC, src), o, defs) for src, o, defs in units if force or _stale(o, [os.path.join(CSRC, src)] + headers)]
 
     def cc(job):
-        s, o = job
+        s, o, defs = job
         extra = ["-save-temps=obj"] if os.path.basename(s) in L2_SINK_SOURCES else []
-        r = subprocess.run([HIPCC] + FLAGS + extra + ["-c", s, "-o", o], capture_output=True, text=True)
+        r = subprocess.run([HIPCC] + flags + defs + extra + ["-c", s, "-o", o], capture_output=True, text=True)
         out = r.stdout + r.stderr
         if extra:
             bad = _l2_sink_misuse(o) if r.returncode == 0 else []
@@ -105,12 +104,12 @@ def _build(OBJ, LIB, FLAGS, force, verbose):
                 print(out, file=sys.stderr)
             if rc != 0:
                 raise RuntimeError("hipcc failed on %s\n%s" % (s, out))
-    objs = [os.path.join(OBJ, src.replace(".hip", ".o")) for src in SOURCES]
-    if force or jobs or _stale(LIB, objs):
-        r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs, capture_output=True, text=True)
+    objs = [o for _, o, _ in units]
+    if force or jobs or _stale(lib_path, objs):
+        r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path] + objs, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("link failed\n" + r.stdout + r.stderr)
-    return LIB
+    return lib_path
 
 
 if __name__ == "__main__":

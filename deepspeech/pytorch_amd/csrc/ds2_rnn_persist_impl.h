@@ -30,6 +30,7 @@
 #include <stdlib.h>
 
 #include "ds2_common.h"
+#include "ds2_rnn_persist_scratch.h"
 
 namespace ds2p {
 
@@ -40,6 +41,7 @@ constexpr int NGROUPS = 8;
 constexpr int MAXS = 16;                 // samples per group (MFMA M tile)
 constexpr unsigned SPIN_LIMIT = 4000000; // ~ seconds; then give up loudly
 constexpr unsigned TAG_INIT = 0x40000000u;
+static_assert(sizeof(ScratchHead::xcc) == NGROUPS * 32 * sizeof(u64), "one handshake slot per workgroup of the tuned kernels");
 
 template <int CELL>
 struct CellInfo;
@@ -77,7 +79,7 @@ struct PArgs {
                             // LSTM di,df,dg,do; RNN dg) -- the bias gradients are their sums over the samples
   u64* xbuf;                // [NGROUPS][2][MAXS][X/2] granules (or four payload-only slots), filled with 0xFF bytes before the launch
   int* err;                 // device word, set to 1 on a spin time-out (sticky: the host reads it)
-  int* lerr;                // per-LAUNCH word in the scratch (reset before the launch, raised == 1): lets the peers of a timed-out workgroup stop early
+  int* lerr;                // LaunchWords::raised, the per-LAUNCH word in the scratch (reset before the launch, raised == 1): lets the peers of a timed-out workgroup stop early
   u64* xcc;                 // [NGROUPS][32] start-up exchange of the workgroups' XCC ids, reset (0xFF bytes) before the launch
   unsigned startup_ms;      // per-launch budget of the start-up handshake (wall clock; ds2_persist_opts.startup_ms, never 0 here)
 #ifdef DS2_PROBE            // tools/probe_rnn_persist.py builds its own library with -DDS2_PROBE; the shipping kernels carry none of it
@@ -112,12 +114,12 @@ __device__ __forceinline__ void publish(u64* p, u64 v, bool local) {
 
 // Start-up handshake (placement-independent sc1 protocol): every workgroup publishes its XCC id, waits for the 31 peers of
 // its group and returns true iff all 32 ids are equal.  Every member evaluates the same 32 words, so the group agrees.
-// Every 1024 polls of a mid-sweep wait: has a peer already given up (lerr[0] == 1), or has this wait outlived the launch's own spin
-// budget (lerr[1]: all-ones from the scratch reset = none beyond SPIN_LIMIT; ds2_persist_opts.spin_limit lowers it per launch for
+// Every 1024 polls of a mid-sweep wait: has a peer already given up (LaunchWords::raised == 1), or has this wait outlived the launch's own spin
+// budget (LaunchWords::spin_budget: all-ones from the scratch reset = none beyond SPIN_LIMIT; ds2_persist_opts.spin_limit lowers it per launch for
 // fault-injection tests)?
 __device__ __forceinline__ bool spin_check(int* lerr, unsigned spins) {
   return __hip_atomic_load(lerr, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1 ||
-         spins > (unsigned)__hip_atomic_load(lerr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+         spins > (unsigned)__hip_atomic_load(&launch_words(lerr)->spin_budget, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void raise_err(int* err, int* lerr) {
   __hip_atomic_fetch_max(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // max: never hides a start-up failure (code 2) -- the healthy
@@ -172,13 +174,13 @@ __device__ __forceinline__ bool group_is_xcd_local(u64* slots /* this group's [3
   return s_local != 0;
 }
 // Kernels without an XCC-id handshake (groups that span XCDs, the round-2 general kernels): ONE arrival word per launch in the
-// scratch head (lerr[2], all-ones after the reset): every workgroup adds 1 and waits until all gridDim.x have, under the same
+// scratch head (LaunchWords::arrived, all-ones after the reset): every workgroup adds 1 and waits until all gridDim.x have, under the same
 // start-up budget and with the same error code.  After it every wait of the sweep is between RESIDENT workgroups.
 __device__ __forceinline__ void wait_all_resident(int* lerr, int tid, int* err, unsigned startup_ms, bool& dead) {
   __shared__ int s_dead;
   if (tid == 0) {
     int gone = 0;
-    unsigned* arrive = reinterpret_cast<unsigned*>(lerr + 2);
+    unsigned* arrive = &launch_words(lerr)->arrived;
     __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned want = gridDim.x - 1u;          // 0xFFFFFFFF + gridDim.x
     unsigned spins = 0;

@@ -102,8 +102,8 @@ PAD_HIDDEN = os.environ.get("DS2_PAD_HIDDEN", "1") != "0"
 
 def _padded_hidden(H, kind, precision, bidirectional=None):
     """Internal width of the recurrent stack: `hidden_size` rounded up to the 16-unit MFMA tile -- and, from 200 units on, further up to
-    the nearest width the persistent sweeps are instantiated for (bf16: every 128 from 384 to 1280 / 1536, plus 800; fp32: 800 and
-    1024), if that is at most 1.5x as wide.  The extra units carry zero weights and biases and stay exactly 0 (GRU, LSTM and tanh
+    the nearest width the persistent sweeps are instantiated for (csrc/ds2_rnn_persist_widths.h is the list; today bf16: every 128
+    from 384 to 1280, GRU to 1536, plus 800; fp32: 800, 1024 and 1280), if that is at most 1.5x as wide.  The extra units carry zero weights and biases and stay exactly 0 (GRU, LSTM and tanh
     cells, forward and backward); the padding lives in the weight cache and the activations, never in the state_dict.  Why: a width
     one notch off the instantiated set used to fall to the launch-per-time-step kernels at 5-8x the time per step (the reference
     leaves hidden_size free, train_config.py:49); zero units in a latency-bound sweep cost next to nothing."""

@@ -714,12 +714,13 @@ def use_persistent(kind, dtype, D, N, H):
         key = (kind, str(dtype), D, N, H)
         if key not in _WARNED_SHAPES:
             _WARNED_SHAPES.add(key)
+            # the widths a full device takes for this dtype, cell, direction count and batch (csrc/ds2_rnn_persist_widths.h is the list)
+            widths = [w for w in range(16, 2049, 16) if query("ds2_rnn_persist_shape_covered", dt(dtype), CELLS[kind], D, N, w)]
             warnings.warn("ds2hip: no persistent recurrent kernel is instantiated for %s %s hidden=%d, %d direction(s), batch %d: the "
-                          "sweeps run one launch per time step (5-8x slower per step).  Persistent kernels exist for bf16 GRU / LSTM "
-                          "with hidden in {384, 512, 640, 768, 800, 896, 1024, 1152, 1280, 1408, 1536} (LSTM: not 1408 / 1536) up to 32 "
-                          "clips per group, bf16 hidden 1024 (any cell), and fp32 GRU / LSTM / RNN with hidden in {800, 1024, 1280}; the model class "
-                          "zero-pads other hidden sizes up to the nearest of these when that is at most 1.5x as wide (DS2_PAD_HIDDEN)."
-                          % (str(dtype).replace("torch.", ""), kind, H, D, N))
+                          "sweeps run one launch per time step (5-8x slower per step).  For this cell, type, direction count and batch "
+                          "persistent kernels exist with hidden in {%s}; the model class zero-pads other hidden sizes up to the nearest "
+                          "instantiated width when that is at most 1.5x as wide (DS2_PAD_HIDDEN)."
+                          % (str(dtype).replace("torch.", ""), kind, H, D, N, ", ".join(map(str, widths))))
     return False
 
 

@@ -166,10 +166,10 @@ int ds2_rnn_bwd(int dtype, int cell, int D, int N, int H, int Tp, const int* len
  * registers, h exchanged between the workgroups of a group through a polled exchange buffer inside ws (pure payload in four
  * slots with an all-ones "not published yet" dword, or tagged 8-byte granules: csrc/ds2_rnn_persist_impl.h); same buffer contract as
  * ds2_rnn_fwd / ds2_rnn_bwd.  Covered (ds2_rnn_persist_supported): bf16 with H = 1024 (any cell, <= 16 samples per group of an
- * 8-group chip: BASELINE config 3); GRU / LSTM with bf16 H in {512, 768, 800, 1024, 1280, 1536} (LSTM: not 1536) and <= 32
- * samples per group (round-4 general kernels: 32 units per workgroup, groups inside one XCD for H <= 1024 -- config 5); GRU /
- * LSTM with fp32 H in {800, 1024} or bf16 H in {800, 1280} and <= 64 samples per group (round-2 general kernels: config 2, the 1e-3
- * parity mode); everything else runs ds2_rnn_fwd / _bwd.
+ * 8-group chip: BASELINE config 3); GRU / LSTM with bf16 storage at the widths of DS2_PERSIST3_WIDTHS and <= 32 samples per group
+ * (round-4 general kernels: 32 units per workgroup, groups inside one XCD for H <= 1024 -- config 5); the (cell, type, H, m-tiles)
+ * rows of DS2_PERSIST2_INSTANCES with <= 64 samples per group (round-2 general kernels: config 2, the 1e-3 parity mode) -- both
+ * tables are csrc/ds2_rnn_persist_widths.h, the one list of instantiated widths; everything else runs ds2_rnn_fwd / _bwd.
  * ws: ds2_rnn_persist_ws_bytes() bytes of scratch (reset by every call on `stream`); err: one device int, sticky (maximum): 1 = a
  * workgroup gave up waiting for its peers in the middle of a sweep, 2 = the launch's workgroups never became co-resident within
  * opts->startup_ms; the outputs are then NaN-poisoned. */
@@ -194,6 +194,10 @@ typedef struct ds2_persist_opts {
   unsigned spin_limit;
   unsigned startup_ms;
 } ds2_persist_opts;
+/* The routing decision behind every entry below, with the CU count given instead of asked of the current device (256 = a full
+ * MI355X): returns the kernel family (ds2_rnn_persist_kind's numbers) and stores the scratch bytes of one sweep in *ws_bytes (may be
+ * NULL; 0 for family 0).  Host arithmetic only -- no device is needed, so the routing table can be pinned by a host test. */
+int ds2_rnn_persist_plan(int dtype, int cell, int D, int N, int H, int cus, unsigned variant, long* ws_bytes);
 int ds2_rnn_persist_supported(int dtype, int cell, int D, int N, int H, unsigned variant);
 /* 1 if a persistent kernel exists for the problem on a FULL device (256 CUs), whatever the current device exposes: tells "this
  * device is too small for the persistent sweeps" (the caller raises) from "no persistent kernel for this shape" (it warns). */

@@ -489,6 +489,20 @@ def test_rnn_persist3_sparse_and_dense_sets_agree(kind, D, N, H, Tp):
         assert np.abs(a - b).max() <= 2e-2 * max(1.0, np.abs(b).max()), np.abs(a - b).max()
 
 
+def test_persist_routing_on_the_device_matches_the_recorded_table():
+    """The live routing entries on this device (support, kernel family, scratch bytes under every A/B variant; shape_covered) against
+    the table recorded from the commit before the routing was unified (tests/golden/routing, tests/fixtures.check_persist_routing)."""
+    from deepspeech.pytorch_amd._lib import query
+    from fixtures import check_persist_routing
+    ops()
+    assert torch.cuda.get_device_properties(torch.cuda.current_device()).multi_processor_count == 256
+
+    def answer(*problem):
+        return tuple(query("ds2_rnn_persist_" + q, *problem) for q in ("supported", "kind", "ws_bytes"))
+
+    assert check_persist_routing(answer, lambda *shape: query("ds2_rnn_persist_shape_covered", *shape)) == 54000 * 10
+
+
 @pytest.mark.parametrize("kind,D,N,H,Tp", PERSIST3_CASES)
 def test_rnn_persist3_sweeps(kind, D, N, H, Tp):
     """Round-4 general persistent kernels against the oracle, against the launch-per-time-step kernels and (where the round-2

@@ -41,6 +41,24 @@ def test_library_exports_every_declared_symbol(lib):
     assert lib.ds2_conv2_fwd_ws_bytes(1, 32, 161, 751) == 32 * 41 * 751 * 32 * 4 and lib.ds2_conv2_fwd_ws_bytes(0, 32, 161, 751) == 0 and lib.ds2_conv2_fwd_ws_bytes(1, 32, 81, 751) == 0
 
 
+def test_persist_routing_matches_the_recorded_table(lib):
+    """The one routing decision of the persistent sweeps (ds2_rnn_persist.hip, plan), asked with 256 CUs given explicitly, against
+    every row of the table recorded from the live entries of the commit before the routing was unified: support, kernel family and
+    scratch bytes under every A/B variant, and shape_covered (which the recording on the MI355X and this host must answer alike)."""
+    import ctypes as C
+    from fixtures import check_persist_routing
+
+    def answer(dtype, cell, D, N, H, variant):
+        ws = C.c_long(-1)
+        family = lib.ds2_rnn_persist_plan(dtype, cell, D, N, H, 256, variant, C.byref(ws))
+        assert lib.ds2_rnn_persist_plan(dtype, cell, D, N, H, 256, variant, None) == family
+        return int(family != 0), family, ws.value
+
+    assert check_persist_routing(answer, lib.ds2_rnn_persist_shape_covered) == 54000 * 8 + 54000 * 2
+    # a device below 256 CUs runs none of them
+    assert lib.ds2_rnn_persist_plan(1, 0, 2, 32, 1024, 255, 0, None) == 0 and lib.ds2_rnn_persist_plan(1, 0, 2, 32, 1024, 256, 0, None) == 1
+
+
 def build_model(fx):
     from deepspeech.pytorch_amd import configs
     from deepspeech.pytorch_amd.model import DeepSpeech
