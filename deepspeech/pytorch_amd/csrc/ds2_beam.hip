@@ -1,4 +1,4 @@
-// CTC prefix beam search on the device, without a language model: the beam counterpart of ds2_decode.hip, behind
+// CTC prefix beam search on the device, with or without a word n-gram language model: the beam counterpart of ds2_decode.hip, behind
 // decoder.BeamCTCDecoder (the interface of the reference's BeamCTCDecoder, decoder.py:56-117, which wraps the ctcdecode C++
 // library and runs it in CPU threads on a host copy of the whole (N, T', C) probability tensor).  The rules are those of
 // ctcdecode's ctc_beam_search_decoder without a scorer, as restated in DESIGN.md ("ds2_beam") and in tests/beam_reference.py.
@@ -24,8 +24,17 @@
 //                       string appends the node (parent, label, frame) at slot t*B + rank of the sample's node pool
 //                 At the end one thread per beam walks the parent links and writes labels and frames.
 // Workspace (torch-owned, ds2_beam_ws_bytes): the kept lists [N][T][64] and the node pool [N][T+1][B] x (parent, label, frame).
-// A candidate's score is formed in one place per kind (the extension in P2, the beam itself in P3): a language-model bonus and
-// a word-boundary hook at the space label would enter there, with pb / pnb kept as the acoustic part.
+// A candidate's score is formed in one place per kind (the extension in P2, the beam itself in P3).
+//
+// k_beam_search<true> (ds2_beam_decode_lm) adds the language model of DESIGN.md "ds2_beam": what the selection compares is
+// lse(pb, pnb) + lm, with pb / pnb kept as the acoustic part.  A beam carries lm (the fp32 sum of its word bonuses), the hash of its
+// partial word (the labels after its last space), the id of that word, the ids of its last order - 1 completed words, and its
+// space bonus: what an extension by the space label adds to lm.  The space bonus depends on the string alone, so it is
+// computed once, in P6, when the string is created: one probe of the word table for the id, then the n-gram probes of all suffix
+// orders and their contexts together.  P2 only adds lm (plus the space bonus at the space label); in lexicon mode it probes the
+// word table once per new candidate and drops the ones that spell no word prefix.  The tables are built on the host (lm.py).
+// k_beam_search<false> is the code without any of it: every addition sits under `if constexpr (LM)`, and the LM state and
+// arguments exist only in the LM instantiation.
 #include <float.h>
 
 #include "ds2_common.h"
@@ -36,6 +45,7 @@
 #define BEAM_THREADS 256
 #define BEAM_TABLE 512   // >= 2 * BEAM_MAXB: load factor <= 1/2
 #define BEAM_TIE_CLASS_BITS 14
+#define BEAM_LM_MAX_ORDER 5
 
 namespace {
 
@@ -71,6 +81,124 @@ __device__ __forceinline__ uint32_t ord_bits(float f) {
   const uint32_t u = __float_as_uint(f);
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
+
+// ---- language model ------------------------------------------------------------------------------------------------------
+constexpr uint64_t kTabEmpty = ~0ull;                  // free slot of both tables
+constexpr uint64_t kNgramSeed = 0x243f6a8885a308d3ull;
+constexpr uint64_t kNgramMul = 0x9e3779b97f4a7c15ull;
+constexpr double kLog10e = 0.4342944819032518;
+constexpr double kOovScore = -1000.0;                  // ln P of a word event with an unknown word or context
+constexpr int kWordAbsent = -2;                        // word-table answers besides a word id; -1 = a proper prefix
+
+struct LmArgs {
+  const ulonglong2* wtab;   // word table [wmask + 1] x (key, value)
+  const ulonglong2* gtab;   // n-gram table [gmask + 1] x (key, log10 p bits | log10 backoff bits << 32)
+  unsigned wmask, gmask;
+  int space, order, bos, lexicon;
+  float alpha, beta;
+  float* acoustic;          // [N][B] -lse(pb, pnb), or null
+};
+
+struct LmState {
+  float lm[BEAM_MAXB], spb[BEAM_MAXB];                 // sum of the word bonuses; space bonus (-inf: no space extension)
+  uint64_t whash[BEAM_MAXB];                           // partial word, kHashEmpty when there is none
+  int wid[BEAM_MAXB];                                  // its word id, -1 when it is no vocabulary word
+  int ctx[BEAM_LM_MAX_ORDER - 1][BEAM_MAXB];           // ctx[0] = the last completed word; -1 = out of vocabulary
+};
+
+__device__ __forceinline__ uint64_t ngram_mix(uint64_t h, int id) {
+  const uint64_t t = (h ^ (uint64_t)(int64_t)(id + 1)) * kNgramMul;
+  return t ^ (t >> 29);
+}
+
+__device__ __forceinline__ unsigned tab_slot(uint64_t key, unsigned mask) { return ((unsigned)key ^ (unsigned)(key >> 32)) & mask; }
+
+// word id (>= 0), -1 for a proper prefix of a word, kWordAbsent
+__device__ __forceinline__ int word_lookup(const LmArgs& A, uint64_t h) {
+  unsigned slot = tab_slot(h, A.wmask);
+  for (unsigned probe = 0; probe <= A.wmask; ++probe) {
+    const ulonglong2 e = A.wtab[slot];
+    if (e.x == h) return (int)(long long)e.y;
+    if (e.x == kTabEmpty) return kWordAbsent;
+    slot = (slot + 1) & A.wmask;
+  }
+  return kWordAbsent;
+}
+
+// alpha * ln P + beta, formed in fp64 without contraction and rounded once
+__device__ __forceinline__ float lm_bonus(const LmArgs& A, double lnp) {
+  return (float)__dadd_rn(__dmul_rn((double)A.alpha, lnp), (double)A.beta);
+}
+
+// The bonus of completing word w after the context c[0] (most recent), c[1], ...: backoff over the stored n-grams.  Keys of
+// (c[m-1] .. c[0], w) for m = 0 .. order-1 and of the contexts (c[m] .. c[0]) for m = 0 .. order-2; all first probes are loaded
+// before any is looked at, and a later probe round only serves the keys whose slot held another key.
+__device__ __forceinline__ float word_bonus(const LmArgs& A, int w, const int (&c)[BEAM_LM_MAX_ORDER - 1]) {
+  constexpr int NP = 2 * BEAM_LM_MAX_ORDER - 1;   // 0 .. 4: n-grams ending in w; 5 .. 8: contexts
+  bool oov = w < 0;
+#pragma unroll
+  for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) oov |= m < A.order - 1 && c[m] < 0;
+  if (oov) return lm_bonus(A, kOovScore);
+  uint64_t key[NP];
+  unsigned slot[NP], pending = 0, found = 0;
+  uint64_t val[NP];
+  uint64_t h = ngram_mix(kNgramSeed, w), g = kNgramSeed;
+  key[0] = h;
+  pending = 1u;
+#pragma unroll
+  for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) {
+    h = ngram_mix(h, c[m]);
+    g = ngram_mix(g, c[m]);
+    key[m + 1] = h;
+    key[BEAM_LM_MAX_ORDER + m] = g;
+    if (m < A.order - 1) pending |= (1u << (m + 1)) | (1u << (BEAM_LM_MAX_ORDER + m));
+  }
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    slot[j] = tab_slot(key[j], A.gmask);
+    val[j] = 0;
+  }
+  for (unsigned probe = 0; probe <= A.gmask && pending; ++probe) {
+    // every key loads, pending or not (a settled key reads its last slot again): no branch separates the loads, so they are in
+    // flight together
+    ulonglong2 e[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) e[j] = A.gtab[slot[j]];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const bool open = pending >> j & 1, match = e[j].x == key[j], free_slot = e[j].x == kTabEmpty;
+      val[j] = open && match ? e[j].y : val[j];
+      found |= (unsigned)(open && match) << j;
+      pending &= ~((unsigned)(open && (match || free_slot)) << j);
+      slot[j] = open && !match && !free_slot ? (slot[j] + 1) & A.gmask : slot[j];
+    }
+  }
+  // the longest stored n-gram ending in w; every shorter step adds the backoff of the context it drops (0 when not stored)
+  double acc = 0.0;
+  bool hit = false;
+#pragma unroll
+  for (int m = BEAM_LM_MAX_ORDER - 1; m >= 0; --m) {
+    if (m < A.order && !hit) {
+      if (found >> m & 1) {
+        acc = __dadd_rn(acc, (double)__uint_as_float((unsigned)val[m]));
+        hit = true;
+      } else if (m > 0) {
+        acc = __dadd_rn(acc, (double)__uint_as_float((unsigned)(val[BEAM_LM_MAX_ORDER + m - 1] >> 32)));
+      }
+    }
+  }
+  if (!hit) return lm_bonus(A, kOovScore);   // a word id without a unigram: not built by lm.py
+  return lm_bonus(A, __ddiv_rn(acc, kLog10e));
+}
+
+// the LM instantiation's state lives in a function of its own, so that the plain instantiation never names it
+__device__ __forceinline__ LmState* lm_state() {
+  __shared__ LmState s[2];
+  return s;
+}
+
+template <class A, class... R>
+__device__ __forceinline__ const A& first_arg(const A& a, const R&...) { return a; }
 
 // ---- per-frame pruning --------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_beam_prune(const float* __restrict__ x, long stride_n, long stride_t, int N, int T, int C,
@@ -146,12 +274,14 @@ __device__ __forceinline__ uint64_t cand_key(float s, int i, int cls1) {
   return ((uint64_t)ord_bits(s) << 32) | (uint32_t)~(((uint32_t)i << BEAM_TIE_CLASS_BITS) | (uint32_t)cls1);
 }
 
+// Extra is empty (LM = false) or one LmArgs (LM = true)
+template <bool LM, class... Extra>
 __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, const int* __restrict__ sizes, int blank, int B, int K,
                                                               const int* __restrict__ pcnt, const int* __restrict__ pcls,
                                                               const float* __restrict__ plp, int* __restrict__ parent_,
                                                               int* __restrict__ label_, int* __restrict__ frame_,
                                                               int* __restrict__ tokens, int* __restrict__ offsets,
-                                                              int* __restrict__ lens, float* __restrict__ scores) {
+                                                              int* __restrict__ lens, float* __restrict__ scores, Extra... extra) {
   __shared__ BeamState st[2];
   __shared__ int table[2][BEAM_TABLE];
   __shared__ float score[BEAM_MAXB], stay_pb[BEAM_MAXB], stay_pnb[BEAM_MAXB], ext_mass[BEAM_MAXB], new_lpc[BEAM_MAXB];
@@ -185,6 +315,16 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
     st[0].len[0] = 0;
     st[0].last[0] = -1;
     st[0].node[0] = -1;
+    if constexpr (LM) {
+      const LmArgs& A = first_arg(extra...);
+      LmState* L = lm_state();
+      L[0].lm[0] = 0.f;
+      L[0].spb[0] = A.lexicon ? -INFINITY : 0.f;
+      L[0].whash[0] = kHashEmpty;
+      L[0].wid[0] = -1;
+#pragma unroll
+      for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) L[0].ctx[m][0] = A.bos;
+    }
   }
   int nb = 1, cur = 0;
   // kept list of the next frame, in registers of wave 0 (lane k holds slot k)
@@ -249,6 +389,14 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
           }
         } else {
           s = mass;
+          if constexpr (LM) {
+            const LmArgs& A = first_arg(extra...);
+            const LmState& LS = lm_state()[cur];
+            float l = LS.lm[i];
+            if (c == A.space) l += LS.spb[i];   // a word event; 0 (open mode) or -inf (lexicon mode) where it is none
+            else if (A.lexicon && word_lookup(A, hash_ext(LS.whash[i], c)) == kWordAbsent) l = -INFINITY;
+            s = mass + l;
+          }
         }
       }
       cs[i * W + 1 + k] = s;
@@ -265,7 +413,8 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
       npnb = lse(npnb, ext_mass[i]);
       stay_pb[i] = npb;
       stay_pnb[i] = npnb;
-      cs[i * W] = lse(npb, npnb);
+      if constexpr (LM) cs[i * W] = lse(npb, npnb) + lm_state()[cur].lm[i];
+      else cs[i * W] = lse(npb, npnb);
     }
     __syncthreads();
     // ---- P4: radix select of the B largest keys among the finite candidates
@@ -365,11 +514,22 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         D.len[r] = S.len[i];
         D.last[r] = S.last[i];
         D.node[r] = S.node[i];
+        if constexpr (LM) {
+          const LmState& LS = lm_state()[cur];
+          LmState& LD = lm_state()[cur ^ 1];
+          LD.lm[r] = LS.lm[i];
+          LD.spb[r] = LS.spb[i];
+          LD.whash[r] = LS.whash[i];
+          LD.wid[r] = LS.wid[i];
+#pragma unroll
+          for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) LD.ctx[m2][r] = LS.ctx[m2][i];
+        }
       } else {
         const int c = kc[m - 1];
         const int id = t * B + r;
         D.pb[r] = -INFINITY;
-        D.pnb[r] = cs[q];
+        if constexpr (LM) D.pnb[r] = (c == S.last[i] ? S.pb[i] : score[i]) + klp[m - 1];   // the acoustic mass, as P2 formed it
+        else D.pnb[r] = cs[q];
         D.lpc[r] = klp[m - 1];
         D.hash[r] = hash_ext(S.hash[i], c);
         D.len[r] = S.len[i] + 1;
@@ -378,6 +538,35 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         parent[id] = S.node[i];
         label[id] = c;
         frame[id] = t;
+        if constexpr (LM) {
+          const LmArgs& A = first_arg(extra...);
+          const LmState& LS = lm_state()[cur];
+          LmState& LD = lm_state()[cur ^ 1];
+          int cx[BEAM_LM_MAX_ORDER - 1];
+#pragma unroll
+          for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) cx[m2] = LS.ctx[m2][i];
+          if (c == A.space) {
+            LD.lm[r] = LS.lm[i] + LS.spb[i];
+            if (LS.whash[i] != kHashEmpty) {       // a word event: the context takes the word's id (-1: out of vocabulary)
+#pragma unroll
+              for (int m2 = BEAM_LM_MAX_ORDER - 2; m2 > 0; --m2) cx[m2] = cx[m2 - 1];
+              cx[0] = LS.wid[i];
+            }
+            LD.spb[r] = A.lexicon ? -INFINITY : 0.f;
+            LD.whash[r] = kHashEmpty;
+            LD.wid[r] = -1;
+          } else {
+            const uint64_t wh = hash_ext(LS.whash[i], c);
+            const int v = word_lookup(A, wh);
+            const int id = v >= 0 ? v : -1;
+            LD.lm[r] = LS.lm[i];
+            LD.spb[r] = (A.lexicon && id < 0) ? -INFINITY : word_bonus(A, id, cx);
+            LD.whash[r] = wh;
+            LD.wid[r] = id;
+          }
+#pragma unroll
+          for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) LD.ctx[m2][r] = cx[m2];
+        }
       }
     }
     if (tid < nk) kidx[kc[tid]] = -1;
@@ -391,8 +580,29 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
   __syncthreads();
   __threadfence();
   const BeamState& S = st[cur];
+  int orank = tid;
+  if constexpr (LM) {
+    // end of utterance: a beam that ends inside a word gets that word's bonus too (a mere prefix counts as out of vocabulary in
+    // lexicon mode); the beams are re-ranked by the total, ties to the earlier rank
+    const LmArgs& A = first_arg(extra...);
+    const LmState& LS = lm_state()[cur];
+    float tot = 0.f;
+    if (tid < nb) {
+      const float ac = lse(S.pb[tid], S.pnb[tid]);
+      float l = LS.lm[tid];
+      if (LS.whash[tid] != kHashEmpty) l += LS.spb[tid] == -INFINITY ? lm_bonus(A, kOovScore) : LS.spb[tid];
+      tot = ac + l;
+      score[tid] = tot;
+      stay_pb[tid] = ac;
+    }
+    __syncthreads();
+    if (tid < nb) {
+      orank = 0;
+      for (int s = 0; s < nb; ++s) orank += score[s] > tot || (score[s] == tot && s < tid);
+    }
+  }
   if (tid < B) {
-    const long o = (long)n * B + tid;
+    const long o = (long)n * B + orank;
     if (tid < nb) {
       const int len = S.len[tid];
       int node = S.node[tid];
@@ -404,10 +614,20 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         node = parent[node];
       }
       lens[o] = len;
-      scores[o] = -lse(S.pb[tid], S.pnb[tid]) + 0.f;
+      if constexpr (LM) {
+        scores[o] = -score[tid] + 0.f;
+        float* acoustic = first_arg(extra...).acoustic;
+        if (acoustic) acoustic[o] = -stay_pb[tid] + 0.f;
+      } else {
+        scores[o] = -lse(S.pb[tid], S.pnb[tid]) + 0.f;
+      }
     } else {
       lens[o] = 0;
       scores[o] = INFINITY;
+      if constexpr (LM) {
+        float* acoustic = first_arg(extra...).acoustic;
+        if (acoustic) acoustic[o] = INFINITY;
+      }
     }
   }
 }
@@ -431,6 +651,10 @@ WsLayout ws_layout(int N, int T, int B) {
   return L;
 }
 
+int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
+                const LmArgs* lm);
+
 }  // namespace
 
 extern "C" {
@@ -447,7 +671,47 @@ long ds2_beam_ws_bytes(int N, int T, int B) {
 int ds2_beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
                     int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws,
                     ds2_stream_t st_) {
-  hipStream_t st = (hipStream_t)st_;
+  return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
+                     (hipStream_t)st_, nullptr);
+}
+
+// The same search with a word n-gram language model (DESIGN.md "ds2_beam", language model).  space: the label that ends a word.
+// word_table / ngram_table: the open-addressing tables of lm.py, [slots][2] 64-bit words, slots a power of two, 16-byte aligned.
+// order 1 .. 5; bos: the id of <s>; lexicon != 0 drops candidates that spell no word prefix.  scores = -(acoustic + lm), the
+// quantity that ranks the beams; acoustic (may be null): -lse(pb, pnb) of the same ranks.  ws as for ds2_beam_decode.
+int ds2_beam_decode_lm(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                       int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                       const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
+                       int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
+  DS2_REQUIRE(C > 0 && space >= 0 && space < C && space != blank, DS2_ERR_ARG);
+  DS2_REQUIRE(order >= 1 && order <= BEAM_LM_MAX_ORDER && bos >= 0, DS2_ERR_ARG);
+  DS2_REQUIRE(word_table && ngram_table, DS2_ERR_ARG);
+  DS2_REQUIRE(word_slots >= 2 && word_slots <= (1l << 31) && (word_slots & (word_slots - 1)) == 0, DS2_ERR_ARG);
+  DS2_REQUIRE(ngram_slots >= 2 && ngram_slots <= (1l << 31) && (ngram_slots & (ngram_slots - 1)) == 0, DS2_ERR_ARG);
+  DS2_REQUIRE((((uintptr_t)word_table | (uintptr_t)ngram_table) & 15) == 0, DS2_ERR_ALIGN);
+  LmArgs A;
+  A.wtab = (const ulonglong2*)word_table;
+  A.gtab = (const ulonglong2*)ngram_table;
+  A.wmask = (unsigned)(word_slots - 1);
+  A.gmask = (unsigned)(ngram_slots - 1);
+  A.space = space;
+  A.order = order;
+  A.bos = bos;
+  A.lexicon = lexicon != 0;
+  A.alpha = alpha;
+  A.beta = beta;
+  A.acoustic = acoustic;
+  return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
+                     (hipStream_t)st_, &A);
+}
+
+}  // extern "C"
+
+namespace {
+
+int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
+                const LmArgs* lm) {
   DS2_REQUIRE(N > 0 && T > 0 && C > 0 && C <= BEAM_MAXC && blank >= 0 && blank < C, DS2_ERR_ARG);
   DS2_REQUIRE(B >= 1 && B <= BEAM_MAXB && cutoff_top_n >= 1, DS2_ERR_ARG);
   const int K = cutoff_top_n < C ? cutoff_top_n : C;
@@ -464,10 +728,14 @@ int ds2_beam_decode(const float* x, long stride_n, long stride_t, int N, int T, 
   hipLaunchKernelGGL(k_beam_prune, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, x, stride_n, stride_t, N, T, C, sizes, K,
                      use_cut, (double)cutoff_prob, pcnt, pcls, plp);
   DS2_CHECK_LAUNCH();
-  hipLaunchKernelGGL(k_beam_search, dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls, plp,
-                     (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores);
+  if (lm)
+    hipLaunchKernelGGL((k_beam_search<true, LmArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls, plp,
+                       (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *lm);
+  else
+    hipLaunchKernelGGL((k_beam_search<false>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls, plp,
+                       (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores);
   DS2_CHECK_LAUNCH();
   return 0;
 }
 
-}  // extern "C"
+}  // namespace

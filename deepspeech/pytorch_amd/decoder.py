@@ -4,7 +4,8 @@ decoder.py:117-181; ``deepspeech_pytorch.validation.WordErrorRate / CharErrorRat
 
 The arg-max + repeat collapse + blank removal of ``decode`` runs on the device (ds2_greedy_decode); only the surviving
 labels travel to the host.  String building and the edit distance are host-side bookkeeping, as in the reference.
-``BeamCTCDecoder`` (decoder.py:56-117) runs CTC prefix beam search on the device (ds2_beam_decode), without a language model.
+``BeamCTCDecoder`` (decoder.py:56-117) runs CTC prefix beam search on the device (ds2_beam_decode), with a word n-gram language
+model from an ARPA file when ``lm_path`` is given (ds2_beam_decode_lm, lm.py).
 When the reference's metric classes are importable the model uses THEM (with this decoder inside); the classes below are the
 stand-ins for images without torchmetrics / Levenshtein."""
 import torch
@@ -55,14 +56,20 @@ class GreedyDecoder:
 
 class BeamCTCDecoder:
     """CTC prefix beam search with the reference's interface (``deepspeech_pytorch.decoder.BeamCTCDecoder``, decoder.py:56-117),
-    run on the device (ds2_beam_decode) instead of the ctcdecode library on a host copy.  No language model: ``lm_path`` must be
-    empty; ``alpha`` / ``beta`` are ignored without one (as in ctcdecode) and ``num_processes`` is ignored (no CPU threads)."""
+    run on the device (ds2_beam_decode) instead of the ctcdecode library on a host copy.  ``lm_path`` names an ARPA text file of
+    a word n-gram model of order 1 to 5 (KenLM binaries do not load); every completed word then adds
+    ``alpha * ln P(word | context) + beta`` to its beam, and with ``lexicon=True`` (ctcdecode's dictionary, the default) only
+    beams that spell vocabulary words survive.  ``alpha`` / ``beta`` are ignored without an LM (as in ctcdecode) and
+    ``num_processes`` is ignored (no CPU threads).  ``lexicon`` is a keyword of this class only."""
 
     def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
-                 num_processes=4, blank_index=0):
+                 num_processes=4, blank_index=0, lexicon=True):
+        self.lm, self.lexicon, self._tables = None, bool(lexicon), {}
         if lm_path:
-            raise ValueError("BeamCTCDecoder: language-model scoring (lm_path=%r) is not implemented; the device beam search "
-                             "runs without a language model (lm_path=None)" % (lm_path,))
+            from . import lm as _lm
+            if ' ' not in labels or labels.index(' ') == blank_index:
+                raise ValueError("BeamCTCDecoder: a language model needs a space label other than the blank to end words")
+            self.lm = _lm.load_arpa(lm_path)     # ValueError unless it is an ARPA text file of order 1 to 5
         self.labels = labels
         self.int_to_char = dict((i, c) for (i, c) in enumerate(labels))
         self.blank_index = blank_index
@@ -76,13 +83,35 @@ class BeamCTCDecoder:
 
     def decode_beams(self, probs, sizes=None):
         """(strings, offsets, scores): strings[n] = beam_width transcripts (best first), offsets[n] = the matching int tensors of
-        frames, scores = host (N, beam_width) float tensor of -log p (lower is better; +inf where no beam is alive)."""
-        if not probs.is_cuda:              # the reference's run_transcribe passes out.cpu() (inference.py:96-98)
+        frames, scores = host (N, beam_width) float tensor of -log p, with an LM -(log p + lm) (lower is better; +inf where no
+        beam is alive).  The reference's run_transcribe passes out.cpu() (inference.py:96-98): a host tensor is moved over."""
+        return self.decode_beams_detailed(probs, sizes)[:3]
+
+    def _lm_tables(self, device):
+        """The LM's two tables on `device`: built and uploaded on first use, then kept."""
+        if device not in self._tables:
+            from . import lm as _lm
+            wt, gt = _lm.build_tables(self.lm, self.labels, self.blank_index, self.space_index)
+            self._tables[device] = (torch.from_numpy(wt).to(device), torch.from_numpy(gt).to(device))
+        return self._tables[device]
+
+    def decode_beams_detailed(self, probs, sizes=None):
+        """(strings, offsets, scores, acoustic): decode_beams' three values and the acoustic -log p of the same beams.  With an
+        LM, scores = acoustic - lm (the total that ranked the beams); without one the two are equal."""
+        if not probs.is_cuda:
             probs = probs.to("cuda")
-        toks, offs, scores = ops.beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob)
+        if self.lm is None:
+            toks, offs, scores = ops.beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
+                                                 self.cutoff_prob)
+            acoustic = scores
+        else:
+            wt, gt = self._lm_tables(probs.device)
+            toks, offs, scores, acoustic = ops.beam_decode_lm(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
+                                                              self.cutoff_prob, self.space_index, wt, gt, self.lm.order,
+                                                              self.lm.bos, self.alpha, self.beta, self.lexicon)
         strings = [[''.join(self.int_to_char[v] for v in t) for t in beams] for beams in toks]
         offsets = [[o.to(torch.int) for o in beams] for beams in offs]
-        return strings, offsets, scores
+        return strings, offsets, scores, acoustic
 
     def decode(self, probs, sizes=None):
         """probs: (N, T', C) probabilities (device or host tensor).  Returns (strings, offsets) in the reference's shapes:

@@ -903,6 +903,66 @@ def beam_decode(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob):
     return toks, offs, scores.cpu()
 
 
+BEAM_LM_MAX_ORDER = 5
+
+
+def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, word_table, ngram_table, order, bos,
+                   alpha, beta, lexicon=True):
+    """CTC prefix beam search with a word n-gram language model (ds2_beam_decode_lm).  Arguments as beam_decode, plus the space
+    label, the two tables of lm.build_tables as int64 CUDA tensors of shape (slots, 2) on the device of probs, the LM's order,
+    the id of <s>, alpha, beta and the lexicon flag.  Returns beam_decode's three values, scores being -(log p + lm), and a host
+    (N, B) float tensor of the acoustic -log p of the same beams."""
+    N, T, Cc = probs.shape
+    B, top_n = int(beam_width), int(cutoff_top_n)
+    if not 1 <= B <= BEAM_MAX_WIDTH:
+        raise ValueError("beam_width must be in [1, %d], got %d" % (BEAM_MAX_WIDTH, B))
+    if top_n < 1 or min(top_n, Cc) > BEAM_MAX_TOP_N:
+        raise ValueError("min(cutoff_top_n, number of classes) must be in [1, %d], got cutoff_top_n=%d with %d classes"
+                         % (BEAM_MAX_TOP_N, top_n, Cc))
+    if not 1 <= Cc <= BEAM_MAX_CLASSES:
+        raise ValueError("the beam decoder supports up to %d classes, got %d" % (BEAM_MAX_CLASSES, Cc))
+    if not 0 <= blank < Cc:
+        raise ValueError("blank index %d out of range for %d classes" % (blank, Cc))
+    if not 0 <= space < Cc or space == blank:
+        raise ValueError("space label %d must be one of the %d classes and differ from the blank (%d)" % (space, Cc, blank))
+    if not 1 <= int(order) <= BEAM_LM_MAX_ORDER:
+        raise ValueError("language-model order must be in [1, %d], got %d" % (BEAM_LM_MAX_ORDER, order))
+    if bos < 0:
+        raise ValueError("the id of <s> must not be negative, got %d" % bos)
+    for name, t in (("word_table", word_table), ("ngram_table", ngram_table)):
+        if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous int64 tensor of shape (slots, 2)" % name)
+        if t.shape[0] < 2 or t.shape[0] & (t.shape[0] - 1):
+            raise ValueError("%s: the number of slots must be a power of two >= 2, got %d" % (name, t.shape[0]))
+        if t.device != probs.device or not t.is_cuda:
+            raise ValueError("%s must live on the device of the probabilities (%s), not %s" % (name, probs.device, t.device))
+    if N == 0 or T == 0:             # no frames: the only beam is the empty string, score 0
+        scores = torch.full((N, B), float("inf"))
+        scores[:, 0] = 0.0
+        return [[[] for _ in range(B)] for _ in range(N)], \
+            [[torch.zeros(0, dtype=torch.int32) for _ in range(B)] for _ in range(N)], scores, scores.clone()
+    if probs.dtype != torch.float32:
+        probs = probs.float()
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    dev = probs.device
+    sz = sizes.to(dev, torch.int32) if sizes is not None else None
+    buf = torch.empty((2, N, B, T), dtype=torch.int32, device=dev)
+    lens = torch.empty((N, B), dtype=torch.int32, device=dev)
+    scores = torch.empty((2, N, B), dtype=torch.float32, device=dev)
+    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
+    call("ds2_beam_decode_lm", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob),
+         int(space), P(word_table), word_table.shape[0], P(ngram_table), ngram_table.shape[0], int(order), int(bos), float(alpha),
+         float(beta), int(bool(lexicon)), P(buf[0]), P(buf[1]), P(lens), P(scores[0]), P(scores[1]), P(ws), S())
+    ln = lens.cpu().numpy()
+    width = max(int(ln.max()), 1)
+    host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
+    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(B)] for n in range(N)]
+    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(B)] for n in range(N)]
+    sc = scores.cpu()
+    return toks, offs, sc[0], sc[1]
+
+
 CTC_RECURSION = 0    # tests / A-B tools: 0 = pair tiles (default), 1 = always the four-wave recursion kernel, 2 = the one-wave kernel up to 255 labels, 3 = rounds 3-5
 
 

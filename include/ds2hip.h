@@ -323,7 +323,7 @@ int ds2_spectrogram(const float* wav, long ldw, const int* nsamples, int N, int 
 int ds2_greedy_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank,
                       int* tokens, int* offsets, int* counts, ds2_stream_t stream);
 
-/* ---- CTC prefix beam search on the device, no language model (BeamCTCDecoder, reference decoder.py:56-117) ---------------
+/* ---- CTC prefix beam search on the device (BeamCTCDecoder, reference decoder.py:56-117) ---------------
  * x[n*stride_n + t*stride_t + c] f32 probabilities, C <= 8192; sizes [N] int32 on the device (null = T); 1 <= B <= 256,
  * cutoff_top_n >= 1 with min(cutoff_top_n, C) <= 64; cutoff_prob < 1 also cuts each frame at that cumulative probability.
  * Outputs (device): tokens / offsets [N][B][T] int32 (the first lens[n][b] entries of row (n, b): label index and its frame),
@@ -333,6 +333,20 @@ long ds2_beam_ws_bytes(int N, int T, int B);
 int ds2_beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
                     int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws,
                     ds2_stream_t stream);
+
+/* The same search with a word n-gram language model (DESIGN.md "ds2_beam", language model; tables built by lm.py).
+ * space: the label that ends a word (!= blank).  word_table / ngram_table: open-addressing tables [slots][2] of 64-bit words
+ * (key, value) in device memory, 16-byte aligned, slots a power of two in [2, 2^31]; a free slot holds ~0.
+ *   word table: key = hash of a word prefix's label string (the beam strings' recurrence), value = word id, -1 for a proper prefix
+ *   n-gram table: key = hash of the id tuple, value = fp32 bits of log10 p | fp32 bits of log10 backoff << 32
+ * order in [1, 5]; bos = id of <s>.  A word event adds alpha * ln P(word | context) + beta to the beam's lm; lexicon != 0 drops
+ * candidates whose partial word is no prefix of a vocabulary word.  scores [N][B] = -(log p + lm), the quantity that ranks the
+ * beams; acoustic [N][B] (may be null) = -log p of the same ranks.  Everything else, ws included, as for ds2_beam_decode.
+ * DS2_ERR_ARG: order or space out of range, space == blank, a null table, slots not a power of two. */
+int ds2_beam_decode_lm(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                       int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                       const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
+                       int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t stream);
 
 #ifdef __cplusplus
 }
