@@ -78,9 +78,6 @@ from .configs import AdamConfig, BiDirectionalConfig, SGDConfig, SpectConfig, Un
 
 import os  # noqa: E402
 
-# DS2_WGRAD_BESIDE_DX=1: the grouped weight-gradient launch of a layer runs beside its dX GEMM on the second stream (measured and
-# rejected as the default: 28.0 vs 27.4 ms per cfg3 step, 143.9 vs 142.4 on cfg5a -- two tile streams through one dispatcher)
-WGRAD_BESIDE_DX = os.environ.get("DS2_WGRAD_BESIDE_DX", "0") not in ("", "0")
 # the layer's dX product rides in the same launch as its weight gradients (long tiles first, the short dX tiles fill the CUs the
 # weight gradients leave idle); DS2_WGRAD_WITH_DX=0 launches them one after the other
 WGRAD_WITH_DX = os.environ.get("DS2_WGRAD_WITH_DX", "1") not in ("", "0")
@@ -461,23 +458,23 @@ def _rnn_layer_forward(mod, li, X, lens_dev, N, Tp, dtype, training, h0, c0, lpa
     return out, hn, cn, [X, Xh if has_bn else None, hext, Sv], (kind, H, D, G, I, has_bn, sv, Ht, layer.input_size)
 
 
-def _rnn_layer_backward(mod, li, meta, saved, lparams, dout, lens_dev, N, Tp, dtype, main, side, wgrad_done, rows=None, state=None):
-    """state = (h0, c0, want_dstate) when the forward was given an initial state (`hs`, reference model.py:224-230) -- the rare path:
+def _rnn_layer_backward(mod, li, meta, saved, lparams, dout, lens_dev, N, Tp, dtype, main, side, rows=None, state=None):
+    """Backward of one BatchRNN layer: (dX, gradients in the order of lparams, dstate).
+    state = (h0, c0, want_dstate) when the forward was given an initial state (`hs`, reference model.py:224-230) -- the rare path:
     the BPTT then runs on the launch-per-time-step kernels (ds2_rnn_bwd takes h0 / c0 and returns d h0 / d c0), and the first steps'
-    share of dW_hh -- h_{t-1} = h0 is not a row of the stored state sequence -- is added here.  Returns (dX, grads, wgrad_done[, dstate])."""
-    if state is None:
-        return _rnn_layer_backward_impl(mod, li, meta, saved, lparams, dout, lens_dev, N, Tp, dtype, main, side, wgrad_done, rows)
+    share of dW_hh -- h_{t-1} = h0 is not a row of the stored state sequence -- is added here.  dstate = (d h0, d c0) when
+    want_dstate, None otherwise."""
     kind, H, D, G, I, has_bn, sv, Ht, It = meta
-    h0, c0, want = state
-    h0p = _pad_cols(h0, H) if (h0 is not None and H != Ht) else h0
-    c0p = _pad_cols(c0, H) if (c0 is not None and H != Ht) else c0
-    cap = {"h0": h0p, "c0": c0p, "want": bool(want)}
-    dX, grads, wgrad_done = _rnn_layer_backward_impl(mod, li, meta, saved, lparams, dout, lens_dev, N, Tp, dtype, main, side, wgrad_done,
-                                                     rows, cap)
-    if wgrad_done is not None:
-        main.wait_event(wgrad_done)
+    if state is not None:
+        h0, c0, want = state
+        h0p = _pad_cols(h0, H) if (h0 is not None and H != Ht) else h0
+        c0p = _pad_cols(c0, H) if (c0 is not None and H != Ht) else c0
+        state = (h0p, c0p, bool(want))
+    dX, grads, rg = _rnn_layer_backward_impl(mod, li, meta, saved, lparams, dout, lens_dev, N, Tp, dtype, main, side, rows, state)
+    if state is None:
+        return dX, grads, None
     main.wait_stream(side)
-    rg, GH, po = cap["rg"], G * H, (2 if has_bn else 0)
+    GH, po = G * H, (2 if has_bn else 0)
     if h0p is not None:
         n4 = (N + 3) // 4 * 4
         ar = torch.arange(N, device=lens_dev.device)
@@ -494,250 +491,256 @@ def _rnn_layer_backward(mod, li, meta, saved, lparams, dout, lens_dev, N, Tp, dt
     dstate = None
     if want:
         dstate = (rg.dh0[..., :Ht].contiguous(), rg.dc0[..., :Ht].contiguous() if rg.dc0 is not None else None)
-    return dX, grads, None, dstate
+    return dX, grads, dstate
 
 
-def _rnn_layer_backward_impl(mod, li, meta, saved, lparams, dout, lens_dev, N, Tp, dtype, main, side, wgrad_done, rows=None, cap=None):
+def _rnn_transposed_weights(mod, li, meta, lparams, dtype):
+    """(WhhT [D][H][G*H], WihT [I][D*G*H]): the layouts the sweep and the dX product read, cached like every other one."""
+    kind, H, D, G, I, has_bn, sv, Ht, It = meta
+    po = 2 if has_bn else 0
+    wih = [lparams[po + 4 * d + 0] for d in range(D)]
+    whh = [lparams[po + 4 * d + 1] for d in range(D)]
+    WhhT = mod._cache.get(("whhT", li, dtype), whh, lambda: torch.stack(
+        [_pad_gate_rows(_pad_cols(p.detach(), H), G, Ht, H).t() for p in whh], 0).to(dtype).contiguous())
+
+    def build_ihT():
+        w = torch.cat([_pad_gate_rows(p.detach(), G, Ht, H) for p in wih], 0)
+        w = _perm_cols_to_internal(w) if li == 0 else _pad_cols(w, H)
+        return w.t().to(dtype).contiguous()
+    return WhhT, mod._cache.get(("wihT", li, dtype), wih, build_ihT)
+
+
+def _wgrad_path(dtype, kind, R, D, GH, H, Xh, rg=None):
+    """Which of the three weight-gradient strategies a layer takes:
+      "tn"        (_wgrad_tn)              bf16, the performance mode: cfg3, cfg5a, cfg5b
+      "tn_split"  (_wgrad_tn, split=True)  fp32 mode at shapes the split-operand products cover: cfg2
+      "nt"        (_wgrad_nt)              small or odd shapes, operands past the 32-bit offset limit, DS2_FP32_WGRAD_TN=0
+    Asked twice per layer.  Before the sweep (rg None), which has to know whether "tn" follows (the layer's dX may ride in that
+    launch): "tn" or None.  After it, with the sweep's RnnGrads: which of the other two."""
+    if ops.wgrad_tn_ok(dtype, R, D * GH, Xh.shape[1], lda=D * GH, ldb=Xh.stride(0)) and \
+            ops.wgrad_tn_ok(dtype, R, GH, H, lda=D * GH, ldb=H):
+        return "tn"
+    if rg is None:
+        return None
+    if ops.split3_ok(dtype, GH, H, R, leaf=True) and FP32_WGRAD_TN and Xh.shape[1] % 8 == 0 and \
+            ops.wgrad_tn_ok(torch.bfloat16, 3 * R, D * GH, Xh.shape[1]) and ops.wgrad_tn_ok(torch.bfloat16, 3 * R, GH, H) and \
+            (kind != "gru" or rg.dQ is not None or rg.dGH is not None):
+        return "tn_split"
+    return "nt"
+
+
+def _rnn_layer_backward_impl(mod, li, meta, saved, lparams, dout, lens_dev, N, Tp, dtype, main, side, rows=None, state=None):
     """Backward of one BatchRNN layer.  bf16 (the performance mode): the BPTT sweep, then ONE launch with the layer's weight
     gradients (grouped TN products over the activations as stored) and its dX, then the BatchNorm backward -- all on the caller's
     stream; nothing runs beside a sweep (a co-runner costs the latency-bound sweep the chip's clock).  fp32 /
-    small / odd shapes: the round-2 path (operand transposes + 128x128 GEMMs on the second HIP stream `side`; the caller joins the
-    streams before the gradients reach autograd).  Returns (dX, gradients in the order of lparams, wgrad_done event or None)."""
-    c = mod._cache
-    R = Tp * N
+    small / odd shapes: the weight gradients run on the second HIP stream `side` (the caller joins the streams before the gradients
+    reach autograd).  state = (h0, c0, want_dstate) at the internal width, see _rnn_layer_backward.
+    Returns (dX, gradients in the order of lparams, the sweep's RnnGrads)."""
     kind, H, D, G, I, has_bn, sv, Ht, It = meta
     X, Xh, hext, Sv = saved
     if Xh is None:
         Xh = X
-    first = li == 0
-    GH = G * H
+    R, GH = Tp * N, G * H
     grads = [None] * len(lparams)
-    po = 2 if has_bn else 0
-    wts = lparams[po:po + 4 * D]
-    wih = [wts[4 * d + 0] for d in range(D)]
-    whh = [wts[4 * d + 1] for d in range(D)]
-    WhhT = c.get(("whhT", li, dtype), list(whh), lambda: torch.stack(
-        [_pad_gate_rows(_pad_cols(p.detach(), H), G, Ht, H).t() for p in whh], 0).to(dtype).contiguous())   # [D][H][G*H]
-
-    def build_ihT():
-        w = torch.cat([_pad_gate_rows(p.detach(), G, Ht, H) for p in wih], 0)
-        w = _perm_cols_to_internal(w) if first else _pad_cols(w, H)
-        return w.t().to(dtype).contiguous()                                                             # [I][D*G*H]
-    WihT = c.get(("wihT", li, dtype), list(wih), build_ihT)
-    # ---- BPTT sweep (caller's stream).  A persistent sweep wants every CU: it starts after the weight-gradient launch of the
-    # layer above has drained (otherwise its first workgroups would spin on peers that are still waiting for a CU)
-    if wgrad_done is not None:
-        main.wait_event(wgrad_done)
-        wgrad_done = None
-    fast = ops.wgrad_tn_ok(dtype, R, D * GH, Xh.shape[1], lda=D * GH, ldb=Xh.stride(0)) and \
-        ops.wgrad_tn_ok(dtype, R, GH, H, lda=D * GH, ldb=H)
-    # one launch for the weight gradients + dX (below): every reader of the sweep's dGI / dQ then works from the row list
+    WhhT, WihT = _rnn_transposed_weights(mod, li, meta, lparams, dtype)
+    # ---- BPTT sweep (caller's stream)
+    path = _wgrad_path(dtype, kind, R, D, GH, H, Xh)
+    # "tn": ONE launch for the weight gradients + dX; every reader of the sweep's dGI / dQ then works from the row list
     n_probs = 1 + D * (2 if (kind == "gru" and (2 * H) % 256 != 0) else 1)
-    fuse_dx = fast and WGRAD_WITH_DX and not WGRAD_BESIDE_DX and n_probs < 6 and WihT.dim() == 2 and WihT.data_ptr() % 16 == 0 and \
+    fuse_dx = path == "tn" and WGRAD_WITH_DX and n_probs < 6 and WihT.dim() == 2 and WihT.data_ptr() % 16 == 0 and \
         ops.gemm8_nt_shape_ok(dtype, R, WihT.shape[0], D * GH, D * GH, WihT.stride(0))
-    if cap is None:
+    if state is None:
         rg = ops.rnn_bwd(kind, dout, WhhT, hext, Sv, lens_dev, D, N, H, Tp, pad_rows_unread=bool(fuse_dx and rows is not None))
     else:
-        rg = ops.rnn_bwd(kind, dout, WhhT, hext, Sv, lens_dev, D, N, H, Tp, h0=cap["h0"], c0=cap["c0"], want_dstate=cap["want"])
-        cap["rg"] = rg
+        rg = ops.rnn_bwd(kind, dout, WhhT, hext, Sv, lens_dev, D, N, H, Tp, h0=state[0], c0=state[1], want_dstate=state[2])
     dGI = rg.dGI
-    dXh_fused = None
-    if fast:
-        # ---- weight gradients as ONE grouped launch of TN products (contraction over the T'*N rows, both operands as the
-        # activations are stored: no transposes).  Never under a sweep: what co-resident GEMMs cost the sweeps was the
-        # chip's CLOCK (1.7 instead of 2.15 GHz while they ran, profiles/r03a_coresidency3.txt) -- a latency-bound kernel
-        # pays that one to one.  On the caller's stream, right behind the sweep (optionally beside the dX GEMM on the second
-        # stream, WGRAD_BESIDE_DX: no gain measured).
-        swept = torch.cuda.Event()
-        swept.record(main)
-        wstream = side if WGRAD_BESIDE_DX else main
-        with torch.cuda.stream(wstream):
-            if wstream is not main:
-                wstream.wait_event(swept)
-                for t_ in rg.tensors() + [Xh, hext]:
-                    t_.record_stream(wstream)
-            Iw = Xh.shape[1]
-            dWih = torch.empty((D * GH, Iw), dtype=torch.float32, device=dGI.device)
-            dWhh = torch.empty((D, GH, H), dtype=torch.float32, device=dGI.device)
-            probs = [dict(At=dGI, Bt=Xh, M=D * GH, N=Iw, lda=D * GH, ldb=Xh.stride(0), out=dWih)]
-            for d in range(D):
-                # h_{t-1} of the forward direction is slot t of the guarded buffer, h_{t+1} of the reverse direction slot t+2
-                hprev = (hext[d, 0:Tp] if d == 0 else hext[d, 2:Tp + 2]).reshape(R, H)
-                if kind == "gru" and rg.dQ is not None:
-                    # hidden-side gate gradient = [dr, dz (columns of dGI) | dQ]
-                    if (2 * H) % 256 == 0:
-                        probs.append(dict(At=dGI[:, d * GH:], At2=rg.dQ[d], lda2=H, m_split=2 * H, Bt=hprev, M=GH, N=H, lda=D * GH, ldb=H,
-                                          out=dWhh[d]))
-                    else:
-                        probs.append(dict(At=dGI[:, d * GH:], Bt=hprev, M=2 * H, N=H, lda=D * GH, ldb=H, out=dWhh[d, :2 * H]))
-                        probs.append(dict(At=rg.dQ[d], Bt=hprev, M=H, N=H, lda=H, ldb=H, out=dWhh[d, 2 * H:]))
-                elif kind == "gru":
-                    probs.append(dict(At=rg.dGH[d], Bt=hprev, M=GH, N=H, lda=GH, ldb=H, out=dWhh[d]))
-                else:
-                    probs.append(dict(At=dGI[:, d * GH:], Bt=hprev, M=GH, N=H, lda=D * GH, ldb=H, out=dWhh[d]))
-            assert not fuse_dx or ops.gemm8_nt_ok(dGI, WihT, R, WihT.shape[0], D * GH, D * GH, WihT.stride(0))
-            if fuse_dx:
-                # + the layer's dX in the same launch; with a row list the padding frames are neither contracted over nor computed
-                _, dXh_fused = ops.gemm8_tn_grouped(probs, R, dx=(dGI, WihT), rows=rows, zero_pad=(lens_dev, Tp, N))
-            else:
-                ops.gemm8_tn_grouped(probs, R, rows=rows)
-            if first:
-                dWih = torch.cat([_perm_cols_to_reference(dWih[d * GH:(d + 1) * GH], mod._rnn_in) for d in range(D)], 0)
-            if rg.bacc is not None:
-                dBih, dBhh_all = ops.rnn_bias_grads(kind, rg.bacc, D, N, H)          # one launch: [D*G*H], [D][G*H]
-                dBhh_l = [dBhh_all[d] for d in range(D)]
-            else:
-                dBih = ops.colsum(dGI)
-                dBhh_all = None
-                if kind == "gru":
-                    dBhh_l = [ops.colsum(rg.dGH[d].reshape(R, GH)) for d in range(D)]
-                else:
-                    dBhh_l = [dBih[d * GH:(d + 1) * GH] for d in range(D)]
-            for d in range(D):
-                grads[po + 4 * d:po + 4 * d + 4] = [dWih[d * GH:(d + 1) * GH], dWhh[d], dBih[d * GH:(d + 1) * GH], dBhh_l[d]]
-            sync = getattr(mod, "_grad_sync", None)
-            if sync is not None and H == Ht:
-                own = [dWih, dWhh, dBih] + ([dBhh_all] if dBhh_all is not None else
-                                            [dBhh_l[d] for d in range(D)] if kind == "gru" else [])
-                sync.layer_ready(own, lparams[po:po + 4 * D])
-            _unpad_layer_grads(grads, po, D, G, Ht, H, It, first)
-            if wstream is not main:
-                wgrad_done = torch.cuda.Event()
-                wgrad_done.record(wstream)
-    # ---- dependent chain (caller's stream): dX -> BatchNorm backward
-    s3 = ops.split3_ok(dtype, GH, H, R, leaf=True)      # fp32 mode: the weight-gradient GEMMs on split operands (ops.split3_ok)
-    if dXh_fused is not None:
-        dXh = dXh_fused
-    elif ops.split3_ok(dtype, R, H, GH):
-        WihT3 = c.get(("wihT3", li), list(wih), lambda: ops.split3(WihT, 1))
-        dXh = ops.gemm_nt(ops.split3(dGI, 0), WihT3, out_dtype=torch.float32, rows=rows, zero_pad=(lens_dev, Tp, N))
+    layer = (mod, li, meta, lparams, grads, Xh, hext, rg, N, Tp)
+    # ---- dependent chain (caller's stream): [weight gradients +] dX -> BatchNorm backward
+    if fuse_dx:
+        dXh = _wgrad_tn(*layer, rows=rows, dx=(dGI, WihT), zero_pad=(lens_dev, Tp, N))
     else:
-        dXh = ops.gemm_nt(dGI, WihT, rows=rows, zero_pad=(lens_dev, Tp, N))                             # [R][I]
+        if path == "tn":
+            _wgrad_tn(*layer, rows=rows)
+        if ops.split3_ok(dtype, R, H, GH):
+            po = 2 if has_bn else 0
+            WihT3 = mod._cache.get(("wihT3", li), [lparams[po + 4 * d] for d in range(D)], lambda: ops.split3(WihT, 1))
+            dXh = ops.gemm_nt(ops.split3(dGI, 0), WihT3, out_dtype=torch.float32, rows=rows, zero_pad=(lens_dev, Tp, N))
+        else:
+            dXh = ops.gemm_nt(dGI, WihT, rows=rows, zero_pad=(lens_dev, Tp, N))                             # [R][I]
     if has_bn:
         dX = torch.empty_like(dXh)
         grads[0], grads[1] = _bn_seq_bwd(dXh, X, dX, sv, R, It, I)
     else:
         dX = dXh
-    if fast:
-        return dX, grads, wgrad_done
+    if path == "tn":
+        return dX, grads, rg
     # the second stream starts this layer's weight gradients only once dX / BatchNorm backward are through, i.e. together
     # with the next layer's sweep: the dependent chain never competes with them for the CUs
     ready = torch.cuda.Event()
     ready.record(main)
-    # ---- weight gradients (second stream, under the next layer's sweep): contraction over the T'*N rows.  Layer 0's run
-    # under the conv backward instead, where no persistent sweep needs most of every CU's registers: the full-size tiles
-    cores = li > 0
     with torch.cuda.stream(side):
         side.wait_event(ready)
         for t in rg.tensors() + [Xh, hext]:
             t.record_stream(side)
-        if s3 and FP32_WGRAD_TN and Xh.shape[1] % 8 == 0 and ops.wgrad_tn_ok(torch.bfloat16, 3 * R, D * GH, Xh.shape[1]) and \
-                ops.wgrad_tn_ok(torch.bfloat16, 3 * R, GH, H) and (kind != "gru" or rg.dQ is not None or rg.dGH is not None):
-            # Round 6: the fp32-mode weight gradients as ONE grouped launch of TN products over the activations as stored, on
-            # row-stacked split operands ([hi; hi; lo] x [hi; lo; hi]: ops.split3_rows) -- no operand transposes, no K-segment
-            # copies, no concatenations (they were 6 transposes + 6 splits + 3 torch cat / copy kernels per layer)
-            Iw = Xh.shape[1]
-            A3 = ops.split3_rows(dGI, 0)                        # [3R][D*G*H]
-            dWih = torch.empty((D * GH, Iw), dtype=torch.float32, device=dGI.device)
-            dWhh_all = torch.empty((D, GH, H), dtype=torch.float32, device=dGI.device)
-            X3 = ops.split3_rows(Xh, 1)                         # [3R][I]
-            probs = [dict(At=A3, Bt=X3, M=D * GH, N=Iw, lda=A3.stride(0), ldb=X3.stride(0), out=dWih)]
-            for d in range(D):
-                hprev = (hext[d, 0:Tp] if d == 0 else hext[d, 2:Tp + 2]).reshape(R, H)
-                H3 = ops.split3_rows(hprev, 1)
-                if kind == "gru" and rg.dQ is not None:         # hidden-side gate gradient = [dr, dz (columns of dGI) | dQ]
-                    probs.append(dict(At=A3[:, d * GH:], Bt=H3, M=2 * H, N=H, lda=A3.stride(0), ldb=H3.stride(0), out=dWhh_all[d, :2 * H]))
-                    Q3 = ops.split3_rows(rg.dQ[d].reshape(R, H), 0)
-                    probs.append(dict(At=Q3, Bt=H3, M=H, N=H, lda=Q3.stride(0), ldb=H3.stride(0), out=dWhh_all[d, 2 * H:]))
-                elif kind == "gru":
-                    G3 = ops.split3_rows(rg.dGH[d].reshape(R, GH), 0)
-                    probs.append(dict(At=G3, Bt=H3, M=GH, N=H, lda=G3.stride(0), ldb=H3.stride(0), out=dWhh_all[d]))
-                else:
-                    probs.append(dict(At=A3[:, d * GH:], Bt=H3, M=GH, N=H, lda=A3.stride(0), ldb=H3.stride(0), out=dWhh_all[d]))
-            ops.gemm8_tn_grouped(probs, 3 * R)
-            if first:
-                dWih = torch.cat([_perm_cols_to_reference(dWih[d * GH:(d + 1) * GH], mod._rnn_in) for d in range(D)], 0)
-            if rg.bacc is not None:
-                dBih, dBhh_all = ops.rnn_bias_grads(kind, rg.bacc, D, N, H)
-                dBhh_l = [dBhh_all[d] for d in range(D)]
-            else:
-                dBih = ops.colsum(dGI)
-                dBhh_all = None
-                dBhh_l = [ops.colsum(rg.dGH[d].reshape(R, GH)) for d in range(D)] if kind == "gru" else \
-                    [dBih[d * GH:(d + 1) * GH] for d in range(D)]
-            for d in range(D):
-                grads[po + 4 * d:po + 4 * d + 4] = [dWih[d * GH:(d + 1) * GH], dWhh_all[d], dBih[d * GH:(d + 1) * GH], dBhh_l[d]]
-            sync = getattr(mod, "_grad_sync", None)
-            if sync is not None and H == Ht:
-                own = [dWih, dWhh_all, dBih] + ([dBhh_all] if dBhh_all is not None else
-                                                [dBhh_l[d] for d in range(D)] if kind == "gru" else [])
-                sync.layer_ready(own, lparams[po:po + 4 * D])
-            _unpad_layer_grads(grads, po, D, G, Ht, H, It, first)
-            return dX, grads, None
-        dGI_T = ops.transpose(dGI)                              # [D*G*H][ldT]
-        Xh_T = ops.transpose(Xh)                                # [I][ldT]
-        ldT = dGI_T.shape[1]
-        dGI_T3 = ops.split3(dGI_T, 0) if s3 else None           # [D*G*H][3*ldT]
-        if s3:
-            dWih = ops.gemm_nt(dGI_T3, ops.split3(Xh_T, 1), out_dtype=torch.float32, coresident=cores)
+        if _wgrad_path(dtype, kind, R, D, GH, H, Xh, rg) == "tn_split":
+            _wgrad_tn(*layer, split=True)
         else:
-            dWih = ops.gemm_nt(dGI_T, Xh_T, out_dtype=torch.float32, splitk=_wgrad_splitk(dGI_T.shape[0], Xh_T.shape[0], ldT),
-                               coresident=cores)
-        del Xh_T
-        if first:
-            dWih = torch.cat([_perm_cols_to_reference(dWih[d * GH:(d + 1) * GH], mod._rnn_in) for d in range(D)], 0)
-        # bias gradients: from the sweep's own per-sample sums (persistent kernels: a [N][NB*H] reduction instead of
-        # column sums over the T'*N rows of dGI / dGH), else column sums
-        bsum = None
-        if rg.bacc is not None:
-            bsum = [ops.colsum(rg.bacc[d]) for d in range(D)]                   # [NB*H] per direction
-            dBih = torch.cat([b[:GH] for b in bsum], 0)
-        else:
-            dBih = ops.colsum(dGI)
-        for d in range(D):
-            # h_{t-1} of the forward direction is slot t of the guarded buffer, h_{t+1} of the reverse direction slot t+2
-            hprev = hext[d, 0:Tp] if d == 0 else hext[d, 2:Tp + 2]
-            Hp_T = ops.transpose(hprev.reshape(R, H))           # [H][ldT]
-            if kind == "gru" and rg.dQ is not None:
-                # hidden-side gate gradient = [dr, dz (rows of dGI^T) | dQ^T]: one GEMM whose A operand is two row blocks
-                dQ_T = ops.transpose(rg.dQ[d].reshape(R, H))   # [H][ldT]
-                if s3:
-                    A3 = torch.empty((GH, 3 * ldT), dtype=torch.bfloat16, device=dGI.device)
-                    A3[:2 * H].copy_(dGI_T3[d * GH:d * GH + 2 * H])
-                    ops.split3(dQ_T, 0, out=A3[2 * H:])
-                    dWhh = ops.gemm_nt(A3, ops.split3(Hp_T, 1), out_dtype=torch.float32, coresident=cores)
-                else:
-                    dWhh = ops.gemm_nt_rows2(dGI_T[d * GH:d * GH + 2 * H], dQ_T, 2 * H, Hp_T, GH, H, ldT, ldT, ldT,
-                                             splitk=_wgrad_splitk(GH, H, ldT), coresident=cores)
-                dBhh = torch.cat([bsum[d][:2 * H], bsum[d][3 * H:4 * H]], 0) if bsum is not None else \
-                    torch.cat([dBih[d * GH:d * GH + 2 * H], ops.colsum(rg.dQ[d].reshape(R, H))], 0)
+            _wgrad_nt(*layer)
+    return dX, grads, rg
+
+
+def _h_prev(hext, d, Tp, R, H):
+    """[R][H]: h_{t-1} of the forward direction is slot t of the guarded buffer, h_{t+1} of the reverse direction slot t+2."""
+    return (hext[d, 0:Tp] if d == 0 else hext[d, 2:Tp + 2]).reshape(R, H)
+
+
+def _wgrad_problems(kind, rg, Xh, hext, Tp, operand, two_block, dWih, dWhh):
+    """The products of ONE grouped launch (ops.gemm8_tn_grouped) for a layer's weight gradients, contraction over the T'*N rows:
+    dW_ih = dGI^T Xh, then per direction dW_hh = (hidden-side gate gradient)^T h_prev.  operand(matrix [R][.], 0 or 1) is the form
+    in which the launch reads it as its At / Bt operand: the matrix itself, or its row-stacked split (ops.split3_rows).
+    two_block: a GRU's [dr, dz | dQ] goes as one product whose At operand is two row blocks."""
+    D, GH, H = dWhh.shape
+    R = rg.dGI.shape[0]
+    A, B = operand(rg.dGI, 0), operand(Xh, 1)
+    lda = A.stride(0)
+    probs = [dict(At=A, Bt=B, M=D * GH, N=Xh.shape[1], lda=lda, ldb=B.stride(0), out=dWih)]
+    for d in range(D):
+        Hp = operand(_h_prev(hext, d, Tp, R, H), 1)
+        hh = dict(Bt=Hp, N=H, ldb=Hp.stride(0))
+        if kind == "gru" and rg.dQ is not None:
+            # hidden-side gate gradient = [dr, dz (columns of dGI) | dQ]
+            Q = operand(rg.dQ[d].reshape(R, H), 0)
+            if two_block:
+                probs.append(dict(hh, At=A[:, d * GH:], At2=Q, lda2=Q.stride(0), m_split=2 * H, M=GH, lda=lda, out=dWhh[d]))
             else:
-                if kind == "gru":
-                    dGH_T = ops.transpose(rg.dGH[d].reshape(R, GH))    # [G*H][ldT]
-                    dBhh = ops.colsum(rg.dGH[d].reshape(R, GH))
-                else:
-                    dGH_T = dGI_T[d * GH:(d + 1) * GH]
-                    dBhh = dBih[d * GH:(d + 1) * GH]
-                if s3:
-                    A3 = ops.split3(dGH_T, 0) if kind == "gru" else dGI_T3[d * GH:(d + 1) * GH]
-                    dWhh = ops.gemm_nt(A3, ops.split3(Hp_T, 1), out_dtype=torch.float32, coresident=cores)
-                else:
-                    dWhh = ops.gemm_nt(dGH_T, Hp_T, out_dtype=torch.float32, M=GH, N=H, K=ldT, lda=ldT, ldb=ldT,
-                                       splitk=_wgrad_splitk(GH, H, ldT), coresident=cores)
-            grads[po + 4 * d:po + 4 * d + 4] = [dWih[d * GH:(d + 1) * GH].contiguous(), dWhh,
-                                                dBih[d * GH:(d + 1) * GH].contiguous(), dBhh.contiguous()]
-        del dGI_T
-        sync = getattr(mod, "_grad_sync", None)
-        if sync is not None and H == Ht:
-            # data parallel with the opt-in early hand-off (dist.OverlappedGradSync): this layer's gradients start
-            # their all-reduce now, ordered after the GEMMs above, under the sweeps of the layers below.  The
-            # returned gradients are views of dWih / dBih (and of dBih for the biases of LSTM / RNN cells).
-            own = [dWih, dBih] + [grads[po + 4 * d + 1] for d in range(D)]
+                probs.append(dict(hh, At=A[:, d * GH:], M=2 * H, lda=lda, out=dWhh[d, :2 * H]))
+                probs.append(dict(hh, At=Q, M=H, lda=Q.stride(0), out=dWhh[d, 2 * H:]))
+        elif kind == "gru":
+            Gd = operand(rg.dGH[d].reshape(R, GH), 0)
+            probs.append(dict(hh, At=Gd, M=GH, lda=Gd.stride(0), out=dWhh[d]))
+        else:
+            probs.append(dict(hh, At=A[:, d * GH:], M=GH, lda=lda, out=dWhh[d]))
+    return probs
+
+
+def _rnn_bias_grads(kind, rg, D, N, H):
+    """(dBih [D*G*H], dBhh [D][G*H] or None, dBhh direction by direction): from the sweep's own per-sample sums where a persistent
+    sweep left them (one launch), else column sums over the T'*N rows of dGI / dGH."""
+    R, GH = rg.dGI.shape[0], rg.dGI.shape[1] // D
+    if rg.bacc is not None:
+        dBih, dBhh_all = ops.rnn_bias_grads(kind, rg.bacc, D, N, H)
+        return dBih, dBhh_all, [dBhh_all[d] for d in range(D)]
+    dBih = ops.colsum(rg.dGI)
+    if kind == "gru":
+        return dBih, None, [ops.colsum(rg.dGH[d].reshape(R, GH)) for d in range(D)]
+    return dBih, None, [dBih[d * GH:(d + 1) * GH] for d in range(D)]
+
+
+def _deliver_layer_grads(mod, li, meta, lparams, grads, per_dir, own):
+    """per_dir[d] = (dWih, dWhh, dBih, dBhh) of direction d at the internal width -> `grads`, in the order of lparams and at the
+    parameters' own width.  own: the tensors whose memory those are (the entries of per_dir may be views of them).  Data parallel
+    with the opt-in early hand-off (dist.OverlappedGradSync): this layer's gradients start their all-reduce now, ordered after the
+    GEMMs that made them, under the sweeps of the layers below."""
+    kind, H, D, G, I, has_bn, sv, Ht, It = meta
+    po = 2 if has_bn else 0
+    for d in range(D):
+        grads[po + 4 * d:po + 4 * d + 4] = per_dir[d]
+    sync = getattr(mod, "_grad_sync", None)
+    if sync is not None and H == Ht:
+        sync.layer_ready(own, lparams[po:po + 4 * D])
+    _unpad_layer_grads(grads, po, D, G, Ht, H, It, li == 0)
+
+
+def _wgrad_tn(mod, li, meta, lparams, grads, Xh, hext, rg, N, Tp, split=False, rows=None, dx=None, zero_pad=None):
+    """Strategies "tn" and "tn_split": a layer's weight gradients as ONE grouped launch of TN products (_wgrad_problems) over both
+    operands as the activations are stored -- no transposes --, then the bias gradients.
+    "tn": on the caller's stream, right behind the sweep, never under one: what co-resident GEMMs cost the sweeps was the chip's
+    CLOCK (1.7 instead of 2.15 GHz while they ran, profiles/r03a_coresidency3.txt) -- a latency-bound kernel pays that one to one.
+    dx = (dGI, WihT): + the layer's dX in the same launch, returned; with a row list the padding frames are neither contracted
+    over nor computed.
+    "tn_split" (split): the fp32-mode weight gradients as the same launch on row-stacked split operands ([hi; hi; lo] x
+    [hi; lo; hi]: ops.split3_rows) -- no K-segment copies, no concatenations either."""
+    kind, H, D, G = meta[:4]
+    GH, dev = G * H, rg.dGI.device
+    K = (3 if split else 1) * Tp * N                        # rows the launch contracts over
+    dWih = torch.empty((D * GH, Xh.shape[1]), dtype=torch.float32, device=dev)
+    dWhh = torch.empty((D, GH, H), dtype=torch.float32, device=dev)
+    probs = _wgrad_problems(kind, rg, Xh, hext, Tp, ops.split3_rows if split else (lambda t, mode: t),
+                            not split and (2 * H) % 256 == 0, dWih, dWhh)
+    dXh = None
+    if dx is not None:
+        assert ops.gemm8_nt_ok(dx[0], dx[1], K, dx[1].shape[0], D * GH, D * GH, dx[1].stride(0))
+        _, dXh = ops.gemm8_tn_grouped(probs, K, dx=dx, rows=rows, zero_pad=zero_pad)
+    else:
+        ops.gemm8_tn_grouped(probs, K, rows=rows)
+    if li == 0:
+        dWih = torch.cat([_perm_cols_to_reference(dWih[d * GH:(d + 1) * GH], mod._rnn_in) for d in range(D)], 0)
+    dBih, dBhh_all, dBhh_l = _rnn_bias_grads(kind, rg, D, N, H)
+    per_dir = [(dWih[d * GH:(d + 1) * GH], dWhh[d], dBih[d * GH:(d + 1) * GH], dBhh_l[d]) for d in range(D)]
+    own = [dWih, dWhh, dBih] + ([dBhh_all] if dBhh_all is not None else dBhh_l if kind == "gru" else [])
+    _deliver_layer_grads(mod, li, meta, lparams, grads, per_dir, own)
+    return dXh
+
+
+def _wgrad_nt(mod, li, meta, lparams, grads, Xh, hext, rg, N, Tp):
+    """Strategy "nt": operand transposes + 128x128 NT GEMMs, contraction over the T'*N rows (on split operands in fp32 mode where
+    the shapes allow).  Runs under the next layer's sweep; layer 0's under the conv backward instead, where no persistent sweep
+    needs most of every CU's registers: the full-size tiles."""
+    kind, H, D, G = meta[:4]
+    R, GH, dGI, cores = Tp * N, G * H, rg.dGI, li > 0
+    s3 = ops.split3_ok(dGI.dtype, GH, H, R, leaf=True)
+    dGI_T = ops.transpose(dGI)                              # [D*G*H][ldT]
+    Xh_T = ops.transpose(Xh)                                # [I][ldT]
+    ldT = dGI_T.shape[1]
+    dGI_T3 = ops.split3(dGI_T, 0) if s3 else None           # [D*G*H][3*ldT]
+    if s3:
+        dWih = ops.gemm_nt(dGI_T3, ops.split3(Xh_T, 1), out_dtype=torch.float32, coresident=cores)
+    else:
+        dWih = ops.gemm_nt(dGI_T, Xh_T, out_dtype=torch.float32, splitk=_wgrad_splitk(dGI_T.shape[0], Xh_T.shape[0], ldT),
+                           coresident=cores)
+    del Xh_T
+    if li == 0:
+        dWih = torch.cat([_perm_cols_to_reference(dWih[d * GH:(d + 1) * GH], mod._rnn_in) for d in range(D)], 0)
+    # bias gradients: column sums of the sweep's per-sample sums / of dGI, dGH, dQ (not ops.rnn_bias_grads: another summation order)
+    bsum = None
+    if rg.bacc is not None:
+        bsum = [ops.colsum(rg.bacc[d]) for d in range(D)]                   # [NB*H] per direction
+        dBih = torch.cat([b[:GH] for b in bsum], 0)
+    else:
+        dBih = ops.colsum(dGI)
+    per_dir = []
+    for d in range(D):
+        Hp_T = ops.transpose(_h_prev(hext, d, Tp, R, H))    # [H][ldT]
+        if kind == "gru" and rg.dQ is not None:
+            # hidden-side gate gradient = [dr, dz (rows of dGI^T) | dQ^T]: one GEMM whose A operand is two row blocks
+            dQ_T = ops.transpose(rg.dQ[d].reshape(R, H))   # [H][ldT]
+            if s3:
+                A3 = torch.empty((GH, 3 * ldT), dtype=torch.bfloat16, device=dGI.device)
+                A3[:2 * H].copy_(dGI_T3[d * GH:d * GH + 2 * H])
+                ops.split3(dQ_T, 0, out=A3[2 * H:])
+                dWhh = ops.gemm_nt(A3, ops.split3(Hp_T, 1), out_dtype=torch.float32, coresident=cores)
+            else:
+                dWhh = ops.gemm_nt_rows2(dGI_T[d * GH:d * GH + 2 * H], dQ_T, 2 * H, Hp_T, GH, H, ldT, ldT, ldT,
+                                         splitk=_wgrad_splitk(GH, H, ldT), coresident=cores)
+            dBhh = torch.cat([bsum[d][:2 * H], bsum[d][3 * H:4 * H]], 0) if bsum is not None else \
+                torch.cat([dBih[d * GH:d * GH + 2 * H], ops.colsum(rg.dQ[d].reshape(R, H))], 0)
+        else:
             if kind == "gru":
-                own += [grads[po + 4 * d + 3] for d in range(D)]
-            sync.layer_ready(own, lparams[po:po + 4 * D])
-        _unpad_layer_grads(grads, po, D, G, Ht, H, It, first)
-    return dX, grads, None
+                dGH_T = ops.transpose(rg.dGH[d].reshape(R, GH))    # [G*H][ldT]
+                dBhh = ops.colsum(rg.dGH[d].reshape(R, GH))
+            else:
+                dGH_T = dGI_T[d * GH:(d + 1) * GH]
+                dBhh = dBih[d * GH:(d + 1) * GH]
+            if s3:
+                A3 = ops.split3(dGH_T, 0) if kind == "gru" else dGI_T3[d * GH:(d + 1) * GH]
+                dWhh = ops.gemm_nt(A3, ops.split3(Hp_T, 1), out_dtype=torch.float32, coresident=cores)
+            else:
+                dWhh = ops.gemm_nt(dGH_T, Hp_T, out_dtype=torch.float32, M=GH, N=H, K=ldT, lda=ldT, ldb=ldT,
+                                   splitk=_wgrad_splitk(GH, H, ldT), coresident=cores)
+        per_dir.append((dWih[d * GH:(d + 1) * GH].contiguous(), dWhh, dBih[d * GH:(d + 1) * GH].contiguous(), dBhh.contiguous()))
+    # the returned gradients are views of dWih / dBih (and of dBih for the biases of LSTM / RNN cells)
+    own = [dWih, dBih] + [p[1] for p in per_dir] + ([p[3] for p in per_dir] if kind == "gru" else [])
+    _deliver_layer_grads(mod, li, meta, lparams, grads, per_dir, own)
 
 
 class _RnnLayerFn(torch.autograd.Function):
@@ -772,22 +775,17 @@ class _RnnLayerFn(torch.autograd.Function):
         lparams = st[1 + ctx.n_saved:]
         main = torch.cuda.current_stream()
         side = mod._wgrad_stream(dout.device)
-        dstate = None
+        state = None
         if ctx.had_state:
-            # round 6: backward through a forward that was given `hs` (reference model.py:224-230; the reference itself only passes
-            # hs in inference) -- launch-per-time-step BPTT with the initial state, d h0 / d c0 returned to autograd
+            # backward through a forward that was given `hs` (reference model.py:224-230; the reference itself only passes hs in
+            # inference) -- launch-per-time-step BPTT with the initial state, d h0 / d c0 returned to autograd
             want = bool(ctx.needs_input_grad[8] or (len(ctx.needs_input_grad) > 9 and ctx.needs_input_grad[9]))
-            dX, grads, wgrad_done, dstate = _rnn_layer_backward(mod, ctx.li, ctx.meta, saved, lparams, dout.contiguous().to(dtype), st[0],
-                                                                N, Tp, dtype, main, side, None, rows=ctx.rows,
-                                                                state=(ctx.h0, ctx.c0, want))
-        else:
-            dX, grads, wgrad_done = _rnn_layer_backward(mod, ctx.li, ctx.meta, saved, lparams, dout.contiguous().to(dtype), st[0], N, Tp,
-                                                        dtype, main, side, None, rows=ctx.rows)
+            state = (ctx.h0, ctx.c0, want)
+        dX, grads, dstate = _rnn_layer_backward(mod, ctx.li, ctx.meta, saved, lparams, dout.contiguous().to(dtype), st[0], N, Tp, dtype,
+                                                main, side, rows=ctx.rows, state=state)
         # the gradients leave this node now (AccumulateGrad, DDP's reducer): whatever the second stream produced must be complete.
         # The early all-reduces of the opt-in OverlappedGradSync are NOT waited for here -- that is their point -- but at the end
         # of backward (its finish callback)
-        if wgrad_done is not None:
-            main.wait_event(wgrad_done)
         main.wait_stream(side)
         for g in grads:
             if g is not None:
@@ -846,14 +844,11 @@ class _RnnStackFn(torch.autograd.Function):
             pos += _layer_param_count(mod.rnns[li])
         grads = [None] * len(params)
         dout = dout.contiguous().to(dtype)
-        wgrad_done = None
         for li in reversed(range(L)):
             n = _layer_param_count(mod.rnns[li])
-            dout, lg, wgrad_done = _rnn_layer_backward(mod, li, ctx.meta[li], list(saved[4 * li:4 * li + 4]), params[offs[li]:offs[li] + n],
-                                                       dout, lens_dev, N, Tp, dtype, main, side, wgrad_done, rows=ctx.rows)
+            dout, lg, _ = _rnn_layer_backward(mod, li, ctx.meta[li], list(saved[4 * li:4 * li + 4]), params[offs[li]:offs[li] + n],
+                                              dout, lens_dev, N, Tp, dtype, main, side, rows=ctx.rows)
             grads[offs[li]:offs[li] + n] = lg
-        if wgrad_done is not None:
-            main.wait_event(wgrad_done)
         if getattr(ctx, "defer_join", False):
             ctx.pending = (main, side, grads, mod)     # the composite node joins after the conv backward
         else:
