@@ -81,6 +81,10 @@ SIGNATURES = {
     "ds2_beam_decode": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ds2_beam_decode_lm": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _f, _f, _i,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_beam_grid_ws_bytes": (_l, [_i, _i, _i, _i]),
+    "ds2_beam_decode_lm_grid": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _vp,
+                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_error_counts": (_i, [_vp, _l, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ds2_ctc_ws_floats": (_l, [_i, _i, _i, _i]),
     "ds2_ctc_loss_grad": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _l, _vp, _i, _vp]),
 }

@@ -35,9 +35,12 @@
 // word table once per new candidate and drops the ones that spell no word prefix.  The tables are built on the host (lm.py).
 // k_beam_search<false> is the code without any of it: every addition sits under `if constexpr (LM)`, and the LM state and
 // arguments exist only in the LM instantiation.
+// k_beam_search<true, LmArgs, GridArgs> (ds2_beam_decode_lm_grid) is the LM search on (N, G) workgroups for G weight points: one
+// prune launch, workgroup (n, g) takes alphas[g] / betas[g] and node pool g, and writes its top beam only.
 #include <float.h>
 
 #include "ds2_common.h"
+#include "ds2_strhash.h"
 
 #define BEAM_MAXB 256
 #define BEAM_MAXK 64
@@ -46,22 +49,9 @@
 #define BEAM_TABLE 512   // >= 2 * BEAM_MAXB: load factor <= 1/2
 #define BEAM_TIE_CLASS_BITS 14
 #define BEAM_LM_MAX_ORDER 5
+#define BEAM_MAX_POINTS 65535   // grid dimension y
 
 namespace {
-
-constexpr uint64_t kM61 = (1ull << 61) - 1;          // prime modulus of the string hash
-constexpr uint64_t kHashBase = 0x0b7e151628aed2a7ull;  // fixed base < kM61
-constexpr uint64_t kHashEmpty = 0x1f3d5b79a2c4e6f8ull % kM61;
-
-// hash(s + c) = (hash(s) * base + c + 1) mod (2^61 - 1)
-__device__ __forceinline__ uint64_t hash_ext(uint64_t h, int c) {
-  const uint64_t lo = h * kHashBase, hi = __umul64hi(h, kHashBase);
-  uint64_t r = (lo & kM61) + ((lo >> 61) | (hi << 3));
-  r = (r & kM61) + (r >> 61);
-  r += (uint64_t)(c + 1);
-  r = (r & kM61) + (r >> 61);
-  return r >= kM61 ? r - kM61 : r;
-}
 
 __device__ __forceinline__ int hash_slot(uint64_t h, int len) {
   return (int)(((uint32_t)h ^ (uint32_t)(h >> 29) ^ ((uint32_t)len * 0x9e3779b9u)) & (BEAM_TABLE - 1));
@@ -197,8 +187,25 @@ __device__ __forceinline__ LmState* lm_state() {
   return s;
 }
 
-template <class A, class... R>
-__device__ __forceinline__ const A& first_arg(const A& a, const R&...) { return a; }
+// A grid of (alpha, beta) points (ds2_beam_decode_lm_grid): workgroup (n, g) searches sample n with the weights of point g in a
+// node pool of its own, and only its top beam leaves the kernel.
+struct GridArgs {
+  const float* alphas;      // [G]
+  const float* betas;       // [G]
+  long pool_stride;         // nodes between the pools of two points
+};
+
+// what the kernel's trailing arguments say about the language model: nothing, the LmArgs, or the LmArgs with this point's weights
+struct NoLm {};
+__device__ __forceinline__ NoLm lm_args() { return {}; }
+__device__ __forceinline__ LmArgs lm_args(const LmArgs& a) { return a; }
+__device__ __forceinline__ LmArgs lm_args(const LmArgs& a, const GridArgs& g) {
+  LmArgs r = a;
+  r.alpha = g.alphas[blockIdx.y];
+  r.beta = g.betas[blockIdx.y];
+  return r;
+}
+__device__ __forceinline__ long grid_pool(const LmArgs&, const GridArgs& g) { return (long)blockIdx.y * g.pool_stride; }
 
 // ---- per-frame pruning --------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_beam_prune(const float* __restrict__ x, long stride_n, long stride_t, int N, int T, int C,
@@ -274,7 +281,7 @@ __device__ __forceinline__ uint64_t cand_key(float s, int i, int cls1) {
   return ((uint64_t)ord_bits(s) << 32) | (uint32_t)~(((uint32_t)i << BEAM_TIE_CLASS_BITS) | (uint32_t)cls1);
 }
 
-// Extra is empty (LM = false) or one LmArgs (LM = true)
+// Extra is empty (LM = false), one LmArgs (LM = true) or LmArgs, GridArgs (LM = true, launched as (N, G) workgroups)
 template <bool LM, class... Extra>
 __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, const int* __restrict__ sizes, int blank, int B, int K,
                                                               const int* __restrict__ pcnt, const int* __restrict__ pcls,
@@ -296,11 +303,14 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
   __shared__ uint64_t s_prefix, s_mask;
   __shared__ unsigned s_need;
 
+  constexpr bool GRID = sizeof...(Extra) == 2;
+  [[maybe_unused]] const auto A = lm_args(extra...);
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   int size = sizes ? sizes[n] : T;
   size = size < 0 ? 0 : (size > T ? T : size);
   const long fbase = (long)n * T;
-  const long pool = (long)n * (T + 1) * B;
+  long pool = (long)n * (T + 1) * B;
+  if constexpr (GRID) pool += grid_pool(extra...);
   int* parent = parent_ + pool;
   int* label = label_ + pool;
   int* frame = frame_ + pool;
@@ -316,7 +326,6 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
     st[0].last[0] = -1;
     st[0].node[0] = -1;
     if constexpr (LM) {
-      const LmArgs& A = first_arg(extra...);
       LmState* L = lm_state();
       L[0].lm[0] = 0.f;
       L[0].spb[0] = A.lexicon ? -INFINITY : 0.f;
@@ -390,7 +399,6 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         } else {
           s = mass;
           if constexpr (LM) {
-            const LmArgs& A = first_arg(extra...);
             const LmState& LS = lm_state()[cur];
             float l = LS.lm[i];
             if (c == A.space) l += LS.spb[i];   // a word event; 0 (open mode) or -inf (lexicon mode) where it is none
@@ -539,7 +547,6 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         label[id] = c;
         frame[id] = t;
         if constexpr (LM) {
-          const LmArgs& A = first_arg(extra...);
           const LmState& LS = lm_state()[cur];
           LmState& LD = lm_state()[cur ^ 1];
           int cx[BEAM_LM_MAX_ORDER - 1];
@@ -584,7 +591,6 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
   if constexpr (LM) {
     // end of utterance: a beam that ends inside a word gets that word's bonus too (a mere prefix counts as out of vocabulary in
     // lexicon mode); the beams are re-ranked by the total, ties to the earlier rank
-    const LmArgs& A = first_arg(extra...);
     const LmState& LS = lm_state()[cur];
     float tot = 0.f;
     if (tid < nb) {
@@ -601,23 +607,24 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
       for (int s = 0; s < nb; ++s) orank += score[s] > tot || (score[s] == tot && s < tid);
     }
   }
-  if (tid < B) {
-    const long o = (long)n * B + orank;
+  // every rank writes its row; in a grid only rank 0 does (thread 0 where no beam is alive), at row (g, n)
+  const bool emit = GRID ? orank == 0 : true;
+  if (tid < B && emit) {
+    const long o = GRID ? (long)blockIdx.y * gridDim.x + n : (long)n * B + orank;
     if (tid < nb) {
       const int len = S.len[tid];
       int node = S.node[tid];
       int* tok = tokens + o * T;
-      int* off = offsets + o * T;
+      int* off = GRID && !offsets ? nullptr : offsets + o * T;
       for (int pos = len - 1; pos >= 0 && node >= 0; --pos) {
         tok[pos] = label[node];
-        off[pos] = frame[node];
+        if (!GRID || off) off[pos] = frame[node];
         node = parent[node];
       }
       lens[o] = len;
       if constexpr (LM) {
         scores[o] = -score[tid] + 0.f;
-        float* acoustic = first_arg(extra...).acoustic;
-        if (acoustic) acoustic[o] = -stay_pb[tid] + 0.f;
+        if (A.acoustic) A.acoustic[o] = -stay_pb[tid] + 0.f;
       } else {
         scores[o] = -lse(S.pb[tid], S.pnb[tid]) + 0.f;
       }
@@ -625,8 +632,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
       lens[o] = 0;
       scores[o] = INFINITY;
       if constexpr (LM) {
-        float* acoustic = first_arg(extra...).acoustic;
-        if (acoustic) acoustic[o] = INFINITY;
+        if (A.acoustic) A.acoustic[o] = INFINITY;
       }
     }
   }
@@ -635,25 +641,50 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 long align256(long b) { return (b + 255) / 256 * 256; }
 
 struct WsLayout {
-  long cnt, cls, lp, parent, label, frame, total;
+  long cnt, cls, lp, parent, label, frame, total, pool;   // byte offsets; pool = bytes of one point's node pool, per array
 };
 
-WsLayout ws_layout(int N, int T, int B) {
+// the kept lists once, then G node pools per array (G = 1 outside a grid)
+WsLayout ws_layout(int N, int T, int B, int G = 1) {
   WsLayout L;
   const long frames = (long)N * T, nodes = (long)N * (T + 1) * B;
+  L.pool = align256(nodes * 4);
   L.cnt = 0;
   L.cls = L.cnt + align256(frames * 4);
   L.lp = L.cls + align256(frames * BEAM_MAXK * 4);
   L.parent = L.lp + align256(frames * BEAM_MAXK * 4);
-  L.label = L.parent + align256(nodes * 4);
-  L.frame = L.label + align256(nodes * 4);
-  L.total = L.frame + align256(nodes * 4);
+  L.label = L.parent + G * L.pool;
+  L.frame = L.label + G * L.pool;
+  L.total = L.frame + G * L.pool;
   return L;
 }
 
 int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
                 int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
-                const LmArgs* lm);
+                const LmArgs* lm, int G = 1, const float* alphas = nullptr, const float* betas = nullptr);
+
+// the checks and the fields that ds2_beam_decode_lm and its grid form share; alpha and beta are left to the caller
+int lm_args_from(LmArgs& A, int C, int blank, int space, const void* word_table, long word_slots, const void* ngram_table,
+                 long ngram_slots, int order, int bos, int lexicon, float* acoustic) {
+  DS2_REQUIRE(C > 0 && space >= 0 && space < C && space != blank, DS2_ERR_ARG);
+  DS2_REQUIRE(order >= 1 && order <= BEAM_LM_MAX_ORDER && bos >= 0, DS2_ERR_ARG);
+  DS2_REQUIRE(word_table && ngram_table, DS2_ERR_ARG);
+  DS2_REQUIRE(word_slots >= 2 && word_slots <= (1l << 31) && (word_slots & (word_slots - 1)) == 0, DS2_ERR_ARG);
+  DS2_REQUIRE(ngram_slots >= 2 && ngram_slots <= (1l << 31) && (ngram_slots & (ngram_slots - 1)) == 0, DS2_ERR_ARG);
+  DS2_REQUIRE((((uintptr_t)word_table | (uintptr_t)ngram_table) & 15) == 0, DS2_ERR_ALIGN);
+  A.wtab = (const ulonglong2*)word_table;
+  A.gtab = (const ulonglong2*)ngram_table;
+  A.wmask = (unsigned)(word_slots - 1);
+  A.gmask = (unsigned)(ngram_slots - 1);
+  A.space = space;
+  A.order = order;
+  A.bos = bos;
+  A.lexicon = lexicon != 0;
+  A.alpha = 0.f;
+  A.beta = 0.f;
+  A.acoustic = acoustic;
+  return 0;
+}
 
 }  // namespace
 
@@ -683,26 +714,35 @@ int ds2_beam_decode_lm(const float* x, long stride_n, long stride_t, int N, int 
                        int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
                        const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
                        int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
-  DS2_REQUIRE(C > 0 && space >= 0 && space < C && space != blank, DS2_ERR_ARG);
-  DS2_REQUIRE(order >= 1 && order <= BEAM_LM_MAX_ORDER && bos >= 0, DS2_ERR_ARG);
-  DS2_REQUIRE(word_table && ngram_table, DS2_ERR_ARG);
-  DS2_REQUIRE(word_slots >= 2 && word_slots <= (1l << 31) && (word_slots & (word_slots - 1)) == 0, DS2_ERR_ARG);
-  DS2_REQUIRE(ngram_slots >= 2 && ngram_slots <= (1l << 31) && (ngram_slots & (ngram_slots - 1)) == 0, DS2_ERR_ARG);
-  DS2_REQUIRE((((uintptr_t)word_table | (uintptr_t)ngram_table) & 15) == 0, DS2_ERR_ALIGN);
   LmArgs A;
-  A.wtab = (const ulonglong2*)word_table;
-  A.gtab = (const ulonglong2*)ngram_table;
-  A.wmask = (unsigned)(word_slots - 1);
-  A.gmask = (unsigned)(ngram_slots - 1);
-  A.space = space;
-  A.order = order;
-  A.bos = bos;
-  A.lexicon = lexicon != 0;
+  const int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  if (rc) return rc;
   A.alpha = alpha;
   A.beta = beta;
-  A.acoustic = acoustic;
   return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
                      (hipStream_t)st_, &A);
+}
+
+long ds2_beam_grid_ws_bytes(int G, int N, int T, int B) {
+  if (G <= 0 || N <= 0 || T <= 0 || B <= 0) return 0;
+  return ws_layout(N, T, B, G).total;
+}
+
+// ds2_beam_decode_lm for G points (alphas[g], betas[g]) at once: the frames are pruned once, then G x N workgroups search.  Of
+// every (point, sample) only the top beam after the end-of-utterance re-rank is written: tokens / offsets [G][N][T] (offsets may
+// be null), lens / scores / acoustic [G][N] (acoustic may be null).  Row (g, n) equals rank 0 of sample n of ds2_beam_decode_lm
+// with alpha = alphas[g], beta = betas[g], bit for bit.  ws: ds2_beam_grid_ws_bytes(G, N, T, B) bytes, 256-byte aligned.
+int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                            int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                            const void* ngram_table, long ngram_slots, int order, int bos, int lexicon, int G, const float* alphas,
+                            const float* betas, int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws,
+                            ds2_stream_t st_) {
+  DS2_REQUIRE(G >= 1 && G <= BEAM_MAX_POINTS && alphas && betas, DS2_ERR_ARG);
+  LmArgs A;
+  const int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  if (rc) return rc;
+  return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
+                     (hipStream_t)st_, &A, G, alphas, betas);
 }
 
 }  // extern "C"
@@ -711,14 +751,14 @@ namespace {
 
 int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
                 int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
-                const LmArgs* lm) {
+                const LmArgs* lm, int G, const float* alphas, const float* betas) {
   DS2_REQUIRE(N > 0 && T > 0 && C > 0 && C <= BEAM_MAXC && blank >= 0 && blank < C, DS2_ERR_ARG);
   DS2_REQUIRE(B >= 1 && B <= BEAM_MAXB && cutoff_top_n >= 1, DS2_ERR_ARG);
   const int K = cutoff_top_n < C ? cutoff_top_n : C;
   DS2_REQUIRE(K <= BEAM_MAXK, DS2_ERR_ARG);
-  DS2_REQUIRE(x && tokens && offsets && lens && scores && ws, DS2_ERR_ARG);
+  DS2_REQUIRE(x && tokens && (offsets || alphas) && lens && scores && ws, DS2_ERR_ARG);
   DS2_REQUIRE(((uintptr_t)ws & 255) == 0, DS2_ERR_ALIGN);
-  const WsLayout L = ws_layout(N, T, B);
+  const WsLayout L = ws_layout(N, T, B, G);
   char* w = (char*)ws;
   int* pcnt = (int*)(w + L.cnt);
   int* pcls = (int*)(w + L.cls);
@@ -728,7 +768,12 @@ int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int 
   hipLaunchKernelGGL(k_beam_prune, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, x, stride_n, stride_t, N, T, C, sizes, K,
                      use_cut, (double)cutoff_prob, pcnt, pcls, plp);
   DS2_CHECK_LAUNCH();
-  if (lm)
+  if (lm && alphas) {
+    const GridArgs grid = {alphas, betas, L.pool / 4};
+    hipLaunchKernelGGL((k_beam_search<true, LmArgs, GridArgs>), dim3(N, G), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt,
+                       pcls, plp, (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *lm,
+                       grid);
+  } else if (lm)
     hipLaunchKernelGGL((k_beam_search<true, LmArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls, plp,
                        (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *lm);
   else

@@ -113,6 +113,33 @@ class BeamCTCDecoder:
         offsets = [[o.to(torch.int) for o in beams] for beams in offs]
         return strings, offsets, scores, acoustic
 
+    def decode_grid_device(self, probs, sizes, points, max_ws_bytes=1 << 30):
+        """The top beam at every (alpha, beta) of `points`, left on the device: ops.beam_decode_lm_grid's five tensors
+        (tokens [G, N, T'], offsets, lens [G, N], scores, acoustic).  ``self.alpha`` / ``self.beta`` play no part."""
+        if self.lm is None:
+            raise ValueError("BeamCTCDecoder.decode_grid searches language-model weights: it needs lm_path")
+        points = [(float(a), float(b)) for a, b in points]
+        if not points:
+            raise ValueError("decode_grid needs at least one (alpha, beta) point")
+        if not probs.is_cuda:
+            probs = probs.to("cuda")
+        wt, gt = self._lm_tables(probs.device)
+        return ops.beam_decode_lm_grid(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
+                                       self.space_index, wt, gt, self.lm.order, self.lm.bos, [a for a, _ in points],
+                                       [b for _, b in points], self.lexicon, max_ws_bytes)
+
+    def decode_grid(self, probs, sizes, points):
+        """decode's best transcript at every (alpha, beta) of `points`, from one launch: strings[g][n], offsets[g][n] (int tensor
+        of frames) and a host (G, N) float tensor of scores, equal to decode_beams' rank 0 with alpha, beta = points[g]."""
+        toks, offs, lens, scores, _ = self.decode_grid_device(probs, sizes, points)
+        ln = lens.cpu().numpy()
+        G, N = ln.shape
+        width = max(int(ln.max()), 1) if ln.size else 1
+        th, oh = toks[:, :, :width].cpu().numpy(), offs[:, :, :width].cpu()
+        strings = [[''.join(self.int_to_char[v] for v in th[g, n, :ln[g, n]].tolist()) for n in range(N)] for g in range(G)]
+        offsets = [[oh[g, n, :ln[g, n]].to(torch.int) for n in range(N)] for g in range(G)]
+        return strings, offsets, scores.cpu()
+
     def decode(self, probs, sizes=None):
         """probs: (N, T', C) probabilities (device or host tensor).  Returns (strings, offsets) in the reference's shapes:
         strings[n] is a list of beam_width transcripts, offsets[n] the matching list of int tensors."""

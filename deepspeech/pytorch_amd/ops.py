@@ -912,30 +912,8 @@ def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, s
     label, the two tables of lm.build_tables as int64 CUDA tensors of shape (slots, 2) on the device of probs, the LM's order,
     the id of <s>, alpha, beta and the lexicon flag.  Returns beam_decode's three values, scores being -(log p + lm), and a host
     (N, B) float tensor of the acoustic -log p of the same beams."""
+    B, top_n = _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos)
     N, T, Cc = probs.shape
-    B, top_n = int(beam_width), int(cutoff_top_n)
-    if not 1 <= B <= BEAM_MAX_WIDTH:
-        raise ValueError("beam_width must be in [1, %d], got %d" % (BEAM_MAX_WIDTH, B))
-    if top_n < 1 or min(top_n, Cc) > BEAM_MAX_TOP_N:
-        raise ValueError("min(cutoff_top_n, number of classes) must be in [1, %d], got cutoff_top_n=%d with %d classes"
-                         % (BEAM_MAX_TOP_N, top_n, Cc))
-    if not 1 <= Cc <= BEAM_MAX_CLASSES:
-        raise ValueError("the beam decoder supports up to %d classes, got %d" % (BEAM_MAX_CLASSES, Cc))
-    if not 0 <= blank < Cc:
-        raise ValueError("blank index %d out of range for %d classes" % (blank, Cc))
-    if not 0 <= space < Cc or space == blank:
-        raise ValueError("space label %d must be one of the %d classes and differ from the blank (%d)" % (space, Cc, blank))
-    if not 1 <= int(order) <= BEAM_LM_MAX_ORDER:
-        raise ValueError("language-model order must be in [1, %d], got %d" % (BEAM_LM_MAX_ORDER, order))
-    if bos < 0:
-        raise ValueError("the id of <s> must not be negative, got %d" % bos)
-    for name, t in (("word_table", word_table), ("ngram_table", ngram_table)):
-        if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of shape (slots, 2)" % name)
-        if t.shape[0] < 2 or t.shape[0] & (t.shape[0] - 1):
-            raise ValueError("%s: the number of slots must be a power of two >= 2, got %d" % (name, t.shape[0]))
-        if t.device != probs.device or not t.is_cuda:
-            raise ValueError("%s must live on the device of the probabilities (%s), not %s" % (name, probs.device, t.device))
     if N == 0 or T == 0:             # no frames: the only beam is the empty string, score 0
         scores = torch.full((N, B), float("inf"))
         scores[:, 0] = 0.0
@@ -961,6 +939,137 @@ def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, s
     offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(B)] for n in range(N)]
     sc = scores.cpu()
     return toks, offs, sc[0], sc[1]
+
+
+def _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos):
+    """The argument checks of beam_decode_lm, for its grid form; returns (B, top_n)."""
+    N, T, Cc = probs.shape
+    B, top_n = int(beam_width), int(cutoff_top_n)
+    if not 1 <= B <= BEAM_MAX_WIDTH:
+        raise ValueError("beam_width must be in [1, %d], got %d" % (BEAM_MAX_WIDTH, B))
+    if top_n < 1 or min(top_n, Cc) > BEAM_MAX_TOP_N:
+        raise ValueError("min(cutoff_top_n, number of classes) must be in [1, %d], got cutoff_top_n=%d with %d classes"
+                         % (BEAM_MAX_TOP_N, top_n, Cc))
+    if not 1 <= Cc <= BEAM_MAX_CLASSES:
+        raise ValueError("the beam decoder supports up to %d classes, got %d" % (BEAM_MAX_CLASSES, Cc))
+    if not 0 <= blank < Cc:
+        raise ValueError("blank index %d out of range for %d classes" % (blank, Cc))
+    if not 0 <= space < Cc or space == blank:
+        raise ValueError("space label %d must be one of the %d classes and differ from the blank (%d)" % (space, Cc, blank))
+    if not 1 <= int(order) <= BEAM_LM_MAX_ORDER:
+        raise ValueError("language-model order must be in [1, %d], got %d" % (BEAM_LM_MAX_ORDER, order))
+    if bos < 0:
+        raise ValueError("the id of <s> must not be negative, got %d" % bos)
+    for name, t in (("word_table", word_table), ("ngram_table", ngram_table)):
+        if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous int64 tensor of shape (slots, 2)" % name)
+        if t.shape[0] < 2 or t.shape[0] & (t.shape[0] - 1):
+            raise ValueError("%s: the number of slots must be a power of two >= 2, got %d" % (name, t.shape[0]))
+        if t.device != probs.device or not t.is_cuda:
+            raise ValueError("%s must live on the device of the probabilities (%s), not %s" % (name, probs.device, t.device))
+    return B, top_n
+
+
+BEAM_GRID_MAX_POINTS = 65535     # points of one ds2_beam_decode_lm_grid launch
+
+
+def plan_grid_chunks(G, bytes_one, bytes_per_point, max_ws_bytes, max_points=BEAM_GRID_MAX_POINTS):
+    """Splits the points 0 .. G-1 of a grid decode into consecutive chunks [(start, count), ...] whose workspace,
+    bytes_one + (count - 1) * bytes_per_point, fits max_ws_bytes; as few chunks as that allows, the earlier ones full.
+    ValueError when one point alone does not fit."""
+    G, bytes_one, bytes_per_point, max_ws_bytes = int(G), int(bytes_one), int(bytes_per_point), int(max_ws_bytes)
+    if G < 1:
+        raise ValueError("the grid needs at least one point, got %d" % G)
+    if bytes_one > max_ws_bytes:
+        raise ValueError("max_ws_bytes=%d is below the workspace of a single point (%d bytes)" % (max_ws_bytes, bytes_one))
+    per = max_points if bytes_per_point <= 0 else min(max_points, 1 + (max_ws_bytes - bytes_one) // bytes_per_point)
+    return [(g, min(per, G - g)) for g in range(0, G, per)]
+
+
+def _weights(name, w, dev):
+    t = torch.as_tensor(w, dtype=torch.float32)
+    if t.dim() != 1:
+        raise ValueError("%s must be a one-dimensional sequence of floats, got shape %s" % (name, tuple(t.shape)))
+    return t.to(dev).contiguous()
+
+
+def beam_decode_lm_grid(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, word_table, ngram_table, order, bos,
+                        alphas, betas, lexicon=True, max_ws_bytes=1 << 30):
+    """beam_decode_lm at G weight points (alphas[g], betas[g]) in one launch of G x N workgroups (ds2_beam_decode_lm_grid); the
+    frames are pruned once.  Returns DEVICE tensors of every point's top beam: tokens [G, N, T'] and offsets [G, N, T'] int32 (the
+    first lens[g, n] entries of a row are valid, the rest 0), lens [G, N] int32, scores [G, N] = -(log p + lm) and acoustic [G, N]
+    f32; row (g, n) is rank 0 of beam_decode_lm(alpha=alphas[g], beta=betas[g]) bit for bit.  The grid is cut into chunks of
+    points whose workspace fits max_ws_bytes (plan_grid_chunks); the cut does not change the result."""
+    B, top_n = _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos)
+    if not probs.is_cuda:
+        raise ValueError("probs must be a HIP device tensor")
+    N, T, Cc = probs.shape
+    dev = probs.device
+    al, be = _weights("alphas", alphas, dev), _weights("betas", betas, dev)
+    G = al.shape[0]
+    if G < 1 or be.shape[0] != G:
+        raise ValueError("alphas and betas must have the same length >= 1, got %d and %d" % (G, be.shape[0]))
+    buf = torch.zeros((2, G, N, T), dtype=torch.int32, device=dev)
+    lens = torch.zeros((G, N), dtype=torch.int32, device=dev)
+    scores = torch.zeros((2, G, N), dtype=torch.float32, device=dev)
+    if N == 0 or T == 0:             # no frames: the only beam is the empty string, score 0
+        return buf[0], buf[1], lens, scores[0], scores[1]
+    one = query("ds2_beam_grid_ws_bytes", 1, N, T, B)
+    chunks = plan_grid_chunks(G, one, query("ds2_beam_grid_ws_bytes", 2, N, T, B) - one, max_ws_bytes)
+    if probs.dtype != torch.float32:
+        probs = probs.float()
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    sz = sizes.to(dev, torch.int32) if sizes is not None else None
+    ws = torch.empty(query("ds2_beam_grid_ws_bytes", max(c for _, c in chunks), N, T, B), dtype=torch.uint8, device=dev)
+    for g0, cnt in chunks:
+        g1 = g0 + cnt
+        call("ds2_beam_decode_lm_grid", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n,
+             float(cutoff_prob), int(space), P(word_table), word_table.shape[0], P(ngram_table), ngram_table.shape[0], int(order),
+             int(bos), int(bool(lexicon)), cnt, P(al[g0:g1]), P(be[g0:g1]), P(buf[0, g0:g1]), P(buf[1, g0:g1]), P(lens[g0:g1]),
+             P(scores[0, g0:g1]), P(scores[1, g0:g1]), P(ws), S())
+    return buf[0], buf[1], lens, scores[0], scores[1]
+
+
+ERROR_COUNTS_MAX_LEN = 4096      # ds2_error_counts: labels of one hypothesis or reference
+
+
+def error_counts(hyp, hyp_lens, targets, target_sizes, space):
+    """Character and word error counts on the device (ds2_error_counts), with the semantics of decoder.CharErrorRate /
+    WordErrorRate.  hyp: (..., L) int32 CUDA tensor of label rows (P rows in all), hyp_lens: (...) their lengths; targets: the flat
+    concatenation of the R references' labels, target_sizes: [R] their lengths, on the host or on the device.  Row p is compared
+    with reference p % R.  Returns four device int32 tensors: char_err [P], word_err [P], ref_chars [R], ref_words [R].
+    ValueError when a string is longer than ERROR_COUNTS_MAX_LEN labels (one scalar is read back for lengths that live on the
+    device and are not bounded by the shapes)."""
+    if not (torch.is_tensor(hyp) and hyp.is_cuda and hyp.dim() >= 1):
+        raise ValueError("hyp must be a HIP device tensor of label rows")
+    dev = hyp.device
+    L = hyp.shape[-1]
+    hyp = hyp.to(torch.int32).reshape(-1, L).contiguous()
+    P_ = hyp.shape[0]
+    hl = torch.as_tensor(hyp_lens).to(dev, torch.int32).reshape(-1).contiguous()
+    if hl.shape[0] != P_:
+        raise ValueError("hyp_lens has %d entries for %d hypotheses" % (hl.shape[0], P_))
+    ts = torch.as_tensor(target_sizes).reshape(-1)
+    R = ts.shape[0]
+    if R < 1 or P_ < R or P_ % R:
+        raise ValueError("the number of hypotheses (%d) must be a positive multiple of the number of references (%d)" % (P_, R))
+    longest_ref = int(ts.max()) if R else 0               # a scalar read when target_sizes lives on the device
+    if longest_ref > ERROR_COUNTS_MAX_LEN or int(ts.min()) < 0:
+        raise ValueError("a reference has %d labels; error_counts takes 0 to %d" % (longest_ref, ERROR_COUNTS_MAX_LEN))
+    if L > ERROR_COUNTS_MAX_LEN:                           # otherwise the row width bounds every hypothesis
+        longest = int(hl.max())
+        if longest > ERROR_COUNTS_MAX_LEN:
+            raise ValueError("a hypothesis has %d labels; error_counts takes up to %d" % (longest, ERROR_COUNTS_MAX_LEN))
+    tg = torch.as_tensor(targets).to(dev, torch.int32).reshape(-1).contiguous()
+    offs = torch.zeros(R + 1, dtype=torch.int32, device=dev)
+    offs[1:] = torch.cumsum(ts.to(dev, torch.int64), 0)
+    if int(ts.sum()) > tg.shape[0]:
+        raise ValueError("target_sizes add up to %d labels, targets has %d" % (int(ts.sum()), tg.shape[0]))
+    out = torch.empty(2 * P_ + 2 * R, dtype=torch.int32, device=dev)
+    ce, we, rc, rw = out[:P_], out[P_:2 * P_], out[2 * P_:2 * P_ + R], out[2 * P_ + R:]
+    call("ds2_error_counts", P(hyp), L, P(hl), P_, P(tg), P(offs), R, int(space), P(ce), P(we), P(rc), P(rw), S())
+    return ce, we, rc, rw
 
 
 CTC_RECURSION = 0    # tests / A-B tools: 0 = pair tiles (default), 1 = always the four-wave recursion kernel, 2 = the one-wave kernel up to 255 labels, 3 = rounds 3-5

@@ -348,6 +348,34 @@ int ds2_beam_decode_lm(const float* x, long stride_n, long stride_t, int N, int 
                        const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
                        int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t stream);
 
+/* ds2_beam_decode_lm for a grid of G weight points (alphas[g], betas[g]), both device f32 [G], 1 <= G <= 65535: the frames are
+ * pruned once and G x N workgroups search, each in a node pool of its own.  Of every (point, sample) only the top beam after the
+ * end-of-utterance re-rank is written: tokens / offsets [G][N][T] int32 (offsets may be null), lens / scores / acoustic [G][N]
+ * (acoustic may be null).  Row (g, n) equals rank 0 of sample n of ds2_beam_decode_lm(alpha = alphas[g], beta = betas[g]), bit for
+ * bit.  ws: ds2_beam_grid_ws_bytes(G, N, T, B) bytes, 256-byte aligned; ds2_beam_grid_ws_bytes(1, ..) == ds2_beam_ws_bytes(..) and
+ * every further point adds the node pools only (affine in G).  DS2_ERR_ARG: G out of range, null alphas or betas, and all of
+ * ds2_beam_decode_lm's. */
+long ds2_beam_grid_ws_bytes(int G, int N, int T, int B);
+int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                            int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                            const void* ngram_table, long ngram_slots, int order, int bos, int lexicon, int G, const float* alphas,
+                            const float* betas, int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws,
+                            ds2_stream_t stream);
+
+/* ---- character / word error counts on the device (the edit distances of validation.py:66-132, decoder.CharErrorRate /
+ * WordErrorRate) ----
+ * hyp: P rows of int32 labels, row p at hyp + p * hyp_stride with hyp_lens[p] labels; ref: the references' labels back to back,
+ * reference r = ref[ref_offsets[r] .. ref_offsets[r + 1]), ref_offsets [R + 1] int32.  Pair p compares hypothesis p with reference
+ * p % R (the [G][N] rows of ds2_beam_decode_lm_grid against N references).  All pointers are device memory; labels are >= 0.
+ *   char_err [P]: Levenshtein distance of the label strings without the space label; ref_chars [R]: the reference's length without it
+ *   word_err [P]: Levenshtein distance over words (maximal runs of non-space labels, identified by the beam search's 61-bit string
+ *                 hash); ref_words [R]: the reference's number of words
+ * A string may have up to 4096 labels.  The lengths live on the device, so the entry cannot refuse a longer one: the kernel reads
+ * nothing of such a pair and writes -1 to its outputs (ops.error_counts checks the lengths and raises).
+ * DS2_ERR_ARG: P < 1, R < 1, R > P, hyp_stride < 0, a null pointer. */
+int ds2_error_counts(const int* hyp, long hyp_stride, const int* hyp_lens, int P, const int* ref, const int* ref_offsets, int R,
+                     int space, int* char_err, int* word_err, int* ref_chars, int* ref_words, ds2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,12 @@ Each call is timed with HIP events after warm-up, median of --runs calls (the ho
 With --lm the same widths are also timed through ops.beam_decode_lm (lexicon mode unless --open), and the one-off cost of parsing
 the ARPA file and of building and uploading the two tables is reported.  To make word events happen on random rows the space
 label's logit is raised (--space-boost) in both the plain and the LM run.
+
+    python tools/bench_beam.py --lm tests/golden/lm/toy3.arpa --grid 1,8,64 [--widths 10,128]
+
+With --grid the weight search is timed at G points: one ops.beam_decode_lm_grid call plus ops.error_counts ("grid"), against G
+sequential ops.beam_decode_lm calls, each followed by the host metrics on the best transcripts ("loop", the path without the grid
+entry).  Both are reported as the whole call and as its device kernels alone (the raw entries on a preallocated workspace).
 """
 import argparse
 import json
@@ -39,6 +45,72 @@ def timed(fn, runs, warmup=3):
     return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
 
 
+def grid_rows(a, probs, sizes, wt, gt, model, C):
+    """the weight search at G points: the grid entry + error_counts against G single-point calls + the host metrics"""
+    from deepspeech.pytorch_amd import decoder as D
+    from deepspeech.pytorch_amd.configs import LABELS
+    from deepspeech.pytorch_amd.ops import P, S, call, query
+    N, T, _ = probs.shape
+    rng = np.random.default_rng(1)
+    tsz = rng.integers(60, 140, size=N)
+    targets = torch.from_numpy(rng.integers(1, C, size=int(tsz.sum())).astype(np.int32))
+    tsz = torch.from_numpy(tsz.astype(np.int32))
+    tgt_strings = D.GreedyDecoder(LABELS).convert_to_strings(list(torch.split(targets, tsz.tolist())))
+    sz = sizes.cuda()
+    rows = []
+    for B in [int(w) for w in a.widths.split(",")]:
+        for G in [int(g) for g in a.grid.split(",")]:
+            al = np.linspace(0.0, 2.0, G).astype(np.float32)
+            be = np.linspace(2.0, 0.0, G).astype(np.float32)
+            lm_args = (0, B, a.top_n, 1.0, C - 1, wt, gt, model.order, model.bos)
+
+            def grid_call():
+                toks, _, lens, _, _ = ops.beam_decode_lm_grid(probs, sizes, *lm_args, al, be, not a.open)
+                return ops.error_counts(toks, lens, targets, tsz, C - 1)
+
+            def loop_call():
+                for g in range(G):
+                    toks, _, _, _ = ops.beam_decode_lm(probs, sizes, *lm_args, float(al[g]), float(be[g]), not a.open)
+                    wer, cer = D.WordErrorRate(None, None), D.CharErrorRate(None, None)
+                    for n in range(N):
+                        hyp = ''.join(LABELS[v] for v in toks[n][0])
+                        wer.calculate_metric(hyp, tgt_strings[n][0])
+                        cer.calculate_metric(hyp, tgt_strings[n][0])
+
+            # the kernels alone: raw entries, everything allocated beforehand
+            ws = torch.empty(query("ds2_beam_grid_ws_bytes", G, N, T, B), dtype=torch.uint8, device="cuda")
+            gbuf = torch.zeros((2, G, N, T), dtype=torch.int32, device="cuda")
+            glen = torch.zeros((G, N), dtype=torch.int32, device="cuda")
+            gsc = torch.zeros((2, G, N), dtype=torch.float32, device="cuda")
+            bbuf = torch.zeros((2, N, B, T), dtype=torch.int32, device="cuda")
+            blen = torch.zeros((N, B), dtype=torch.int32, device="cuda")
+            bsc = torch.zeros((2, N, B), dtype=torch.float32, device="cuda")
+            ald, bed = torch.from_numpy(al).cuda(), torch.from_numpy(be).cuda()
+            tg = targets.cuda()
+            offs = torch.zeros(N + 1, dtype=torch.int32, device="cuda")
+            offs[1:] = torch.cumsum(tsz.cuda(), 0)
+            cnt = torch.zeros(2 * G * N + 2 * N, dtype=torch.int32, device="cuda")
+            head = (P(probs), probs.stride(0), probs.stride(1), N, T, C, P(sz), 0, B, a.top_n, 1.0, C - 1, P(wt), wt.shape[0], P(gt),
+                    gt.shape[0], model.order, model.bos)
+
+            def grid_kernels():
+                call("ds2_beam_decode_lm_grid", *head, int(not a.open), G, P(ald), P(bed), P(gbuf[0]), P(gbuf[1]), P(glen), P(gsc[0]),
+                     P(gsc[1]), P(ws), S())
+                call("ds2_error_counts", P(gbuf[0]), T, P(glen), G * N, P(tg), P(offs), N, C - 1, P(cnt[:G * N]), P(cnt[G * N:]),
+                     P(cnt[2 * G * N:]), P(cnt[2 * G * N + N:]), S())
+
+            def loop_kernels():
+                for g in range(G):
+                    call("ds2_beam_decode_lm", *head, float(al[g]), float(be[g]), int(not a.open), P(bbuf[0]), P(bbuf[1]), P(blen),
+                         P(bsc[0]), P(bsc[1]), P(ws), S())
+
+            for name, whole, kernels in (("grid", grid_call, grid_kernels), ("loop", loop_call, loop_kernels)):
+                med, lo, hi = timed(whole, a.runs, warmup=2)
+                kmed, _, _ = timed(kernels, a.runs, warmup=2)
+                rows.append(dict(decoder=name, B=B, G=G, ms_per_call=med, min_ms=lo, max_ms=hi, kernel_ms=kmed, ms_per_point=med / G))
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=20)
@@ -51,6 +123,7 @@ def main():
     ap.add_argument("--beta", type=float, default=1.0)
     ap.add_argument("--open", action="store_true", help="open mode (lexicon=False)")
     ap.add_argument("--space-boost", type=float, default=0.0)
+    ap.add_argument("--grid", default=None, help="with --lm: numbers of (alpha, beta) points, e.g. 1,8,64")
     a = ap.parse_args()
     assert a.runs >= 10
     assert torch.cuda.is_available(), "bench_beam needs a HIP device"
@@ -88,9 +161,15 @@ def main():
             med, lo, hi = timed(lambda: ops.beam_decode_lm(probs, sizes, 0, B, a.top_n, 1.0, C - 1, wt, gt, model.order, model.bos,
                                                            a.alpha, a.beta, not a.open), a.runs)
             rows.append(dict(decoder="beam+lm", B=B, ms_per_batch=med, min_ms=lo, max_ms=hi, us_per_step=1e3 * med / T))
+    if a.lm and a.grid:
+        rows += grid_rows(a, probs, sizes, wt, gt, model, C)
     lines = notes + ["# tools/bench_beam.py: N=%d T'=%d C=%d cutoff_top_n=%d softmax(normal * %.1f), median of %d calls after warm-up, %s"
              % (N, T, C, a.top_n, a.scale, a.runs, torch.cuda.get_device_name(0))]
     for r in rows:
+        if r["decoder"] in ("grid", "loop"):
+            lines.append("%-7s B=%-4d G=%-3d %10.3f ms/call (min %.3f, max %.3f)  kernels %10.3f ms  %8.3f ms/point" %
+                         (r["decoder"], r["B"], r["G"], r["ms_per_call"], r["min_ms"], r["max_ms"], r["kernel_ms"], r["ms_per_point"]))
+            continue
         lines.append("%-7s B=%-4s %9.3f ms/batch (min %.3f, max %.3f)  %8.2f us/step" %
                      (r["decoder"], r["B"] if r["B"] else "-", r["ms_per_batch"], r["min_ms"], r["max_ms"], r["us_per_step"]))
     lines.append(json.dumps(rows))
