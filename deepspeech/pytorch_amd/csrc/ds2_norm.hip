@@ -189,10 +189,11 @@ __global__ void k_bn_eval_coeffs(int C, const float* __restrict__ gamma, const f
 // SEQ_OUT: additionally the output is written in sequence layout X0[(t*N + n)][f*32 + c] (the collapse+transpose of
 // model.py:219-221 fused into the store; the internal feature order f*32+c is undone on the weight side).
 // ---------------------------------------------------------------------------------------------------------
-template <typename T, bool CONV, bool SEQ_OUT>
+template <typename T, bool CONV, bool SEQ_OUT, bool CENTRED = false>
 __global__ void __launch_bounds__(256) k_bn_apply(const T* __restrict__ X, T* __restrict__ Y, long R, int C, long ldx,
                                                    long ldy, const float* __restrict__ scale,
-                                                   const float* __restrict__ shift, RowMap rm,
+                                                   const float* __restrict__ shift, const float* __restrict__ mean,
+                                                   const float* __restrict__ beta, RowMap rm,
                                                    const int* __restrict__ lens, int N) {
   constexpr int V = Vec16<T>::N;
   const int chunks = C / V;
@@ -211,7 +212,9 @@ __global__ void __launch_bounds__(256) k_bn_apply(const T* __restrict__ X, T* __
       Vec16<T>::load(X + r * ldx + c0, v);
 #pragma unroll
       for (int i = 0; i < V; ++i) {
-        float y = bn_affine(v[i], scale[c0 + i], shift[c0 + i]);
+        // CENTRED (a batch of ONE row: every variance is 0 and rstd = eps^-1/2, so x * scale + shift would round at the size of
+        // mean * scale, ~1e3 times the result): (x - mean) * scale + beta.  Every other launch keeps the scale/shift form.
+        float y = CENTRED ? __builtin_fmaf(v[i] - mean[c0 + i], scale[c0 + i], beta[c0 + i]) : bn_affine(v[i], scale[c0 + i], shift[c0 + i]);
         if (CONV) y = fminf(fmaxf(y, 0.f), 20.f);
         v[i] = y;
       }
@@ -509,15 +512,18 @@ int ds2_bn_fwd(int dtype, int mode, int training, const void* X, void* Y, long R
   DS2_REQUIRE(C % V == 0 && ldx % V == 0 && ldy % V == 0, DS2_ERR_ALIGN);
   dim3 g(apply_grid(R * (C / V))), b(256);
 #define LAUNCH_APPLY(TT)                                                                                              \
-  if (mode == 0)                                                                                                      \
+  if (mode == 0 && training && R == 1)                                                                                \
+    hipLaunchKernelGGL((k_bn_apply<TT, false, false, true>), g, b, 0, st, (const TT*)X, (TT*)Y, R, C, ldx, ldy,        \
+                       save_scale, save_shift, save_mean, beta, rm, lens, N);                                         \
+  else if (mode == 0)                                                                                                 \
     hipLaunchKernelGGL((k_bn_apply<TT, false, false>), g, b, 0, st, (const TT*)X, (TT*)Y, R, C, ldx, ldy, save_scale,  \
-                       save_shift, rm, lens, N);                                                                      \
+                       save_shift, save_mean, beta, rm, lens, N);                                                     \
   else if (mode == 1)                                                                                                 \
     hipLaunchKernelGGL((k_bn_apply<TT, true, false>), g, b, 0, st, (const TT*)X, (TT*)Y, R, C, ldx, ldy, save_scale,   \
-                       save_shift, rm, lens, N);                                                                      \
+                       save_shift, save_mean, beta, rm, lens, N);                                                     \
   else                                                                                                                \
     hipLaunchKernelGGL((k_bn_apply<TT, true, true>), g, b, 0, st, (const TT*)X, (TT*)Y, R, C, ldx, ldy, save_scale,    \
-                       save_shift, rm, lens, N);
+                       save_shift, save_mean, beta, rm, lens, N);
   if (dtype == DS2_F32) {
     LAUNCH_APPLY(float)
   } else {

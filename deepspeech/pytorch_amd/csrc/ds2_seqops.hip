@@ -442,9 +442,11 @@ __global__ void __launch_bounds__(256) k_softmax_rows(const float* __restrict__ 
     const float* x = in + r * ldi;
     float m = -INFINITY;
     for (int c = 0; c < C; ++c) m = fmaxf(m, x[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += expf(x[c] - m);
-    const float inv = 1.f / s;
+    // the denominator in fp64: a sequential fp32 sum of C terms is off by ~sqrt(C) * 2^-25 relative, which at a few hundred classes
+    // is the whole 1e-6 that the probabilities (and their row sums) are held to
+    double s = 0.0;
+    for (int c = 0; c < C; ++c) s += (double)expf(x[c] - m);
+    const float inv = (float)(1.0 / s);
     for (int c = 0; c < C; ++c) out[r * ldo + c] = expf(x[c] - m) * inv;
   }
 }

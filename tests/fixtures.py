@@ -5,10 +5,37 @@ import json
 import os
 
 import numpy as np
+import torch
 
 from deepspeech.pytorch_amd import synth
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+# ---- helpers of the kernel-level GPU tests (test_gpu_kernels.py, test_gpu_norm.py, test_gpu_seqops.py) -------------------------
+DEV = "cuda"
+
+
+def cu(a, dtype=torch.float32):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV).to(dtype).contiguous()
+
+
+def rnd(a, dtype):
+    """what the device sees after storing `a` in `dtype` (numpy float64 in, float64 out)"""
+    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(torch.float64).numpy()
+
+
+def np64(t):
+    return t.detach().to(torch.float64).cpu().numpy()
+
+
+def relerr(got, ref):
+    return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-30)
+
+
+# fp32 storage: tight (the 1e-3 north-star bar with margin); bf16 storage: rounding of the stored outputs (2^-8 relative) plus
+# accumulation noise
+TOL = {torch.float32: 2e-5, torch.bfloat16: 1.2e-2}
 
 
 def fixture_names():

@@ -5,11 +5,10 @@ import numpy as np
 import pytest
 import torch
 
+from fixtures import DEV, TOL, cu, np64, relerr, rnd
 from oracle import ds2_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda"
 
 
 def ops():
@@ -17,25 +16,7 @@ def ops():
     return _ops
 
 
-def cu(a, dtype=torch.float32):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV).to(dtype).contiguous()
-
-
-def rnd(a, dtype):
-    """what the device sees after storing `a` in `dtype` (numpy float64 in, float64 out)"""
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dtype).to(torch.float64).numpy()
-
-
-def np64(t):
-    return t.detach().to(torch.float64).cpu().numpy()
-
-
-def relerr(got, ref):
-    return np.abs(got - ref).max() / max(np.abs(ref).max(), 1e-30)
-
-
 DTYPES = [torch.float32, torch.bfloat16]
-TOL = {torch.float32: 2e-5, torch.bfloat16: 1.2e-2}
 
 
 # ---------------------------------------------------------------------------------------------------------------
