@@ -76,6 +76,9 @@ SIGNATURES = {
     "ds2_spect_frames": (_i, [_i]),
     "ds2_spect_ws_bytes": (_l, [_i, _i]),
     "ds2_spectrogram": (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
+    "ds2_spectrogram_aug": (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "ds2_spec_augment_coef": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "ds2_spec_augment": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "ds2_greedy_decode": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ds2_beam_ws_bytes": (_l, [_i, _i, _i]),
     "ds2_beam_decode": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

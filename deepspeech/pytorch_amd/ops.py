@@ -1072,6 +1072,61 @@ def error_counts(hyp, hyp_lens, targets, target_sizes, space):
     return ce, we, rc, rw
 
 
+SPEC_AUGMENT_MAX_MASKS = 4       # ds2_spec_augment / ds2_spectrogram_aug: masks per axis and clip
+
+
+def _aug_batch(x, frames):
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 4 and x.shape[1] == 1 and x.dtype == torch.float32):
+        raise ValueError("spec_augment takes a float32 HIP device batch of shape (N, 1, F, Tmax)")
+    fr = torch.as_tensor(frames).to(x.device, torch.int32).reshape(-1).contiguous()
+    if fr.shape[0] != x.shape[0]:
+        raise ValueError("frames has %d entries for %d clips" % (fr.shape[0], x.shape[0]))
+    return x.contiguous(), fr
+
+
+def aug_masks(m, N, dev, what):
+    """(N, M, 2) int32 device tensor of [start, width] pairs (None = no masks) -> (tensor or None, M)."""
+    if m is None:
+        return None, 0
+    m = torch.as_tensor(m)
+    if m.dim() != 3 or m.shape[0] != N or m.shape[2] != 2:
+        raise ValueError("%s must have shape (N, masks, 2) = [start, width] per mask; got %s" % (what, tuple(m.shape)))
+    if m.shape[1] > SPEC_AUGMENT_MAX_MASKS:
+        raise ValueError("%s holds %d masks per clip; the kernels take up to %d" % (what, m.shape[1], SPEC_AUGMENT_MAX_MASKS))
+    if m.shape[1] == 0:
+        return None, 0
+    return m.to(dev, torch.int32).contiguous(), m.shape[1]
+
+
+def spec_augment_coef(x, frames, warp_draw, W=5):
+    """Flow coefficients [N][3] (a_f, a_t, a_0) of the reference's time warp for the clips of x (N, 1, F, Tmax) from the draws
+    warp_draw [N][12] (SpecAugment.draw): ds2_spec_augment_coef."""
+    x, fr = _aug_batch(x, frames)
+    N, _, F, Tmax = x.shape
+    wd = torch.as_tensor(warp_draw).to(x.device, torch.float32).contiguous()
+    if tuple(wd.shape) != (N, 12):
+        raise ValueError("warp_draw must have shape (N, 12); got %s" % (tuple(wd.shape),))
+    coef = torch.empty((N, 3), dtype=torch.float32, device=x.device)
+    call("ds2_spec_augment_coef", P(x), N, F, Tmax, P(fr), P(wd), int(W), P(coef), S())
+    return coef
+
+
+def spec_augment(x, frames, coef, fmask, tmask):
+    """The reference's spec_augment (time warp with the flow coefficients coef [N][3], all zero = none; frequency masks fmask and
+    time masks tmask, (N, M, 2) [start, width], None = none) on every clip of the batch x (N, 1, F, Tmax), clip n = its first
+    frames[n] frames.  Returns a new tensor; frames beyond a clip's own are zero.  ds2_spec_augment."""
+    x, fr = _aug_batch(x, frames)
+    N, _, F, Tmax = x.shape
+    coef = torch.as_tensor(coef).to(x.device, torch.float32).contiguous()
+    if tuple(coef.shape) != (N, 3):
+        raise ValueError("coef must have shape (N, 3); got %s" % (tuple(coef.shape),))
+    fm, MF = aug_masks(fmask, N, x.device, "fmask")
+    tm, MT = aug_masks(tmask, N, x.device, "tmask")
+    out = torch.empty_like(x)
+    call("ds2_spec_augment", P(x), P(out), N, F, Tmax, P(fr), P(coef), P(fm), MF, P(tm), MT, S())
+    return out
+
+
 CTC_RECURSION = 0    # tests / A-B tools: 0 = pair tiles (default), 1 = always the four-wave recursion kernel, 2 = the one-wave kernel up to 255 labels, 3 = rounds 3-5
 
 

@@ -316,6 +316,27 @@ long ds2_spect_ws_bytes(int N, int Lmax);
 int ds2_spectrogram(const float* wav, long ldw, const int* nsamples, int N, int Lmax, const float* basis, int reflect,
                     int normalize, float* out, void* ws, ds2_stream_t stream);
 
+/* ---- SpecAugment on the device (spec_augment, loader/spec_augment.py:68-115: time_warp :48-65 -> sparse_image_warp,
+ * loader/sparse_image_warp.py:88-111, then frequency masks :98-104 and time masks :107-113; what `augmentation.spec_augment: True`
+ * runs per clip, after normalisation and before _collate_fn).  With its single control point the reference's dense flow is zero
+ * along frequency and affine along time: flow_t(f, t) = a_f f + a_t t + a_0; out[f][t] interpolates row f linearly at t - flow_t
+ * with floor clamped to [0, T - 2] and the weight to [0, 1] (interpolate_bilinear, :357-408), T the clip's own frame count.
+ *   warp_draw [N][12] f32 (device; null = no warp): i = randrange(W, T - W) (negative = no warp for the clip), d = randrange(-W, W),
+ *     the nine values of randn(3, 3) / 1e10 (sparse_image_warp.py:170, row major), one pad.  Clips with T <= 2W frames are not
+ *     warped (the reference raises ValueError there); W is time_warp's (default 5).
+ *   fmask [N][MF][2], tmask [N][MT][2] int32 (device): start and width of every mask, width <= 0 = none; MF, MT <= 4; null iff 0.
+ *   coef [N][3] f32 (device): (a_f, a_t, a_0); all zero = the clip is not warped.
+ * ds2_spectrogram_aug = ds2_spectrogram with the augmentation folded into its write kernel (same ws; coef_out optional).
+ * ds2_spec_augment_coef / ds2_spec_augment: the same two steps for a batch (N, 1, F, Tmax) f32 that exists already, any F, clip n
+ * = the first frames[n] frames (device int32); out != in, frames >= frames[n] of out are zero. */
+int ds2_spectrogram_aug(const float* wav, long ldw, const int* nsamples, int N, int Lmax, const float* basis, int reflect,
+                        int normalize, float* out, void* ws, const float* warp_draw, int W, const int* fmask, int MF,
+                        const int* tmask, int MT, float* coef_out, ds2_stream_t stream);
+int ds2_spec_augment_coef(const float* x, int N, int F, int Tmax, const int* frames, const float* warp_draw, int W, float* coef,
+                          ds2_stream_t stream);
+int ds2_spec_augment(const float* in, float* out, int N, int F, int Tmax, const int* frames, const float* coef, const int* fmask,
+                     int MF, const int* tmask, int MT, ds2_stream_t stream);
+
 /* ---- greedy CTC decoding on the device (validation_step, model.py:256 -> GreedyDecoder.decode, decoder.py:164-181) -------
  * x[n*stride_n + t*stride_t + c] f32 scores (probabilities or logits), C <= 64; sizes [N] int32 on the device (null = T).
  * Per sample: arg-max per frame (first maximum), repeats collapsed, blanks dropped.  tokens / offsets [N][T] int32 (the first
