@@ -79,7 +79,13 @@ SIGNATURES = {
     "ds2_spectrogram_aug": (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "ds2_spec_augment_coef": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "ds2_spec_augment": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
-    "ds2_greedy_decode": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ds2_wsola_segments": (_i, [_i, _f]),
+    "ds2_wsola_out_len": (_l, [_i, _f]),
+    "ds2_wsola": (_i, [_vp, _l, _vp, _vp, _i, _vp, _l, _vp, _vp, _i, _vp]),
+    "ds2_wave_ws_bytes": (_l, [_i]),
+    "ds2_wave_energy": (_i, [_vp, _l, _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
+    "ds2_wave_mix": (_i, [_vp, _l, _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _l, _vp]),
+    "ds2_greedy_decode":(_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ds2_beam_ws_bytes": (_l, [_i, _i, _i]),
     "ds2_beam_decode": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ds2_beam_decode_lm": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _f, _f, _i,

@@ -10,7 +10,18 @@ that block is part of the draw.  This is what models trained with the reference'
 reproduced.
 
 Deviation: a clip with T <= 2W frames (0.1 s) makes the reference's ``randrange(W, T - W)`` raise ValueError; here it is left
-unwarped (masks still apply)."""
+unwarped (masks still apply).
+
+``WaveAugment`` covers what the loader does to the SAMPLES before the STFT (loader/data_loader.py:151-159): the tempo / gain
+perturbation of ``load_randomly_augmented_audio`` (:392-404, ``augmentation.speed_volume_perturb``) and ``NoiseInjection``
+(:97-128, ``augmentation.noise_dir`` / ``noise_prob`` / ``noise_min`` / ``noise_max``).  Again the draws are made here, in the
+reference's order, and the samples are touched on the device only (csrc/ds2_waveaug.hip).  The tempo change is the project's own
+WSOLA with sox's default ``tempo`` parameters; its length rule is mirrored here (``wsola_out_len``) so that the frame counts of a
+batch are known without reading anything back.  Deviations from the reference: no sample parity with sox,
+no 16-bit requantisation or dither, a clip longer than its noise recording gets no noise (the reference's assertion fails), a
+noise crop without energy adds nothing (the reference produces NaN)."""
+import math
+
 import numpy as np
 
 MAX_MASKS = 4           # masks per axis and clip that the kernels take
@@ -59,3 +70,137 @@ class SpecAugment:
             fmask[n] = self._masks(rng, self.frequency_mask_num, self.frequency_masking_para, int(n_bins))
             tmask[n] = self._masks(rng, self.time_mask_num, self.time_masking_para, T)
         return warp, fmask, tmask
+
+
+# ---- waveform augmentation -------------------------------------------------------------------------------------------------
+WSOLA_SEGMENT, WSOLA_SEARCH, WSOLA_OVERLAP = 1312, 234, 192      # sox `tempo` defaults at 16 kHz: 82 ms, 14.68 ms, 12 ms
+WSOLA_ADVANCE = WSOLA_SEGMENT - WSOLA_OVERLAP
+
+
+def wsola_start(k, tempo):
+    """nominal first input sample of segment k: floor(k * tempo * 1120) in fp64, tempo an fp32 value."""
+    return math.floor(k * float(np.float32(tempo)) * float(WSOLA_ADVANCE))
+
+
+def wsola_segments(nsamples, tempo):
+    """ds2_wsola_segments: the number of k with wsola_start(k) + overlap <= nsamples; 0 = the clip is copied unchanged (shorter
+    than segment + search, or a tempo outside [0.1, 10])."""
+    L, t = int(nsamples), float(np.float32(tempo))
+    if not (L >= WSOLA_SEGMENT + WSOLA_SEARCH and np.float32(0.1) <= np.float32(tempo) <= np.float32(10.0)):
+        return 0
+    k = int((L - WSOLA_OVERLAP) / (t * float(WSOLA_ADVANCE)))
+    while wsola_start(k + 1, t) + WSOLA_OVERLAP <= L:
+        k += 1
+    while k > 0 and wsola_start(k, t) + WSOLA_OVERLAP > L:
+        k -= 1
+    return k + 1
+
+
+def wsola_out_len(nsamples, tempo):
+    """ds2_wsola_out_len: (S - 1) * 1120 + min(1312, nsamples - wsola_start(S - 1)); nsamples itself for a copied clip."""
+    S = wsola_segments(nsamples, tempo)
+    if S == 0:
+        return max(int(nsamples), 0)
+    return (S - 1) * WSOLA_ADVANCE + min(WSOLA_SEGMENT, int(nsamples) - wsola_start(S - 1, tempo))
+
+
+class NoiseBank:
+    """The noise recordings of ``augmentation.noise_dir`` as ONE device buffer (fp32, back to back) with their offsets.  Reading
+    audio files stays with the caller: hand the decoded mono waveforms (at the front-end's sample rate, on the [-1, 1] scale of
+    load_audio) to ``from_waveforms``."""
+
+    def __init__(self, samples, offsets):
+        self.samples = samples                                   # device float32 [total]
+        self.offsets = np.asarray(offsets, np.int64)             # [R + 1]: recording r = samples[offsets[r]:offsets[r + 1]]
+
+    @classmethod
+    def from_waveforms(cls, waveforms, device="cuda"):
+        import torch
+        arrays = [np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1)) for w in waveforms]
+        if not arrays or any(a.size == 0 for a in arrays):
+            raise ValueError("a noise bank needs at least one recording, and none of them empty")
+        offsets = np.concatenate([[0], np.cumsum([a.size for a in arrays])])
+        return cls(torch.from_numpy(np.concatenate(arrays)).to(device), offsets)
+
+    def __len__(self):
+        return len(self.offsets) - 1
+
+    def length(self, r):
+        return int(self.offsets[r + 1] - self.offsets[r])
+
+
+class WaveDraws:
+    """One batch's draws of WaveAugment.  tempo / gain / level [N] float32 (None = that step is off for the batch; gain holds the
+    LINEAR factor 10^(dB / 20), gain_db the drawn value), noise_off [N] int64 (-1 = no noise for the clip) and noise_start [N] int32
+    with level; nsamples [N] int64 = the sample counts after the tempo change, segments [N] = the clips' WSOLA segment counts."""
+
+    def __init__(self, tempo, gain, gain_db, level, noise_off, noise_start, nsamples, segments):
+        self.tempo, self.gain, self.gain_db, self.level = tempo, gain, gain_db, level
+        self.noise_off, self.noise_start, self.nsamples, self.segments = noise_off, noise_start, nsamples, segments
+
+    def take(self, order):
+        """the draws of the clips `order`, in that order."""
+        pick = lambda a: None if a is None else a[np.asarray(order, np.int64)]      # noqa: E731
+        return WaveDraws(*[pick(a) for a in (self.tempo, self.gain, self.gain_db, self.level, self.noise_off, self.noise_start,
+                                             self.nsamples, self.segments)])
+
+    def arrays(self):
+        """the arrays that go to the device, the 8-byte one first (SpectrogramFrontEnd.upload_draws keeps that order)."""
+        return [self.noise_off, self.tempo, self.gain, self.level, self.noise_start]
+
+
+class WaveAugment:
+    def __init__(self, speed_volume_perturb=False, tempo_range=(0.85, 1.15), gain_range=(-6, 8), noise_bank=None, noise_prob=0.4,
+                 noise_levels=(0.0, 0.5), sample_rate=16000):
+        self.speed_volume_perturb = bool(speed_volume_perturb)
+        self.tempo_range, self.gain_range = tuple(tempo_range), tuple(gain_range)
+        self.noise_bank, self.noise_prob, self.noise_levels = noise_bank, float(noise_prob), tuple(noise_levels)
+        self.sample_rate = int(sample_rate)
+        if not 0.1 <= min(self.tempo_range) <= max(self.tempo_range) <= 10.0:
+            raise ValueError("tempo_range must lie in [0.1, 10]; got %r" % (self.tempo_range,))
+
+    @classmethod
+    def from_config(cls, aug_cfg, noise_bank=None, sample_rate=16000):
+        """From the reference's AugmentationConfig (configs/train_config.py:25-31; duck typed).  noise_bank: the recordings of
+        ``aug_cfg.noise_dir`` as a NoiseBank -- required when noise_dir is set, since no file is read here."""
+        if getattr(aug_cfg, "noise_dir", "") and noise_bank is None:
+            raise ValueError("augmentation.noise_dir is set: pass its recordings as a NoiseBank (NoiseBank.from_waveforms)")
+        return cls(speed_volume_perturb=getattr(aug_cfg, "speed_volume_perturb", False),
+                   noise_bank=noise_bank if getattr(aug_cfg, "noise_dir", "") else None,
+                   noise_prob=getattr(aug_cfg, "noise_prob", 0.4),
+                   noise_levels=(getattr(aug_cfg, "noise_min", 0.0), getattr(aug_cfg, "noise_max", 0.5)), sample_rate=sample_rate)
+
+    @property
+    def active(self):
+        return self.speed_volume_perturb or self.noise_bank is not None
+
+    def draw(self, nsamples, rng):
+        """All draws of a batch on the host, from a numpy.random.Generator or RandomState, per clip in the reference's order:
+        tempo and gain (load_randomly_augmented_audio, data_loader.py:398-401; both go to sox as '{:.3f}', :383, so they are rounded
+        to three decimals here too), binomial(1, noise_prob) (:157), and for a clip that gets noise the recording (:114), the level
+        (:115) and rand() for the start (:121: start = rand * (noise_len - data_len) seconds, truncated to samples here; data_len is
+        the length AFTER the tempo change).  A clip longer than its recording gets no noise.  Returns a WaveDraws."""
+        ns = np.asarray(nsamples, np.int64).reshape(-1)
+        N, bank, sr = len(ns), self.noise_bank, float(self.sample_rate)
+        tempo = np.ones(N, np.float32) if self.speed_volume_perturb else None
+        gain_db = np.zeros(N, np.float64) if self.speed_volume_perturb else None
+        level = np.zeros(N, np.float32) if bank is not None else None
+        noise_off = np.full(N, -1, np.int64) if bank is not None else None
+        noise_start = np.zeros(N, np.int32) if bank is not None else None
+        out_ns, segments = ns.copy(), np.zeros(N, np.int64)
+        for n in range(N):
+            if self.speed_volume_perturb:
+                tempo[n] = float("%.3f" % rng.uniform(low=self.tempo_range[0], high=self.tempo_range[1]))
+                gain_db[n] = float("%.3f" % rng.uniform(low=self.gain_range[0], high=self.gain_range[1]))
+                segments[n], out_ns[n] = wsola_segments(ns[n], tempo[n]), wsola_out_len(ns[n], tempo[n])
+            if bank is not None and rng.binomial(1, self.noise_prob):
+                r = int(rng.choice(len(bank)))
+                lv = rng.uniform(*self.noise_levels)
+                u = rng.random()
+                noise_len, data_len = bank.length(r), int(out_ns[n])
+                if data_len > noise_len:
+                    continue
+                start = int(u * (noise_len / sr - data_len / sr) * sr)
+                level[n], noise_off[n], noise_start[n] = lv, bank.offsets[r], min(max(start, 0), noise_len - data_len)
+        gain = np.power(10.0, gain_db / 20.0).astype(np.float32) if gain_db is not None else None
+        return WaveDraws(tempo, gain, gain_db, level, noise_off, noise_start, out_ns, segments)

@@ -1143,3 +1143,85 @@ def ctc_loss_grad(logits, targets_i32, target_offsets, input_lengths, target_len
          P(target_lengths), Tp, N, Cc, blank, max_target_len, 1.0, P(nll), P(loss), P(dlogits), ldg, P(ws),
          int(CTC_RECURSION if recursion is None else recursion), S())
     return loss, nll, dlogits
+
+
+# ---- waveform augmentation (csrc/ds2_waveaug.hip) ---------------------------------------------------------------------------
+def _wave_batch(wav, nsamples):
+    if not (torch.is_tensor(wav) and wav.is_cuda and wav.dim() == 2 and wav.dtype == torch.float32):
+        raise ValueError("the waveform kernels take a float32 HIP device batch of shape (N, Lmax)")
+    ns = torch.as_tensor(nsamples).to(wav.device, torch.int32).reshape(-1).contiguous()
+    if ns.shape[0] != wav.shape[0]:
+        raise ValueError("nsamples has %d entries for %d clips" % (ns.shape[0], wav.shape[0]))
+    return wav.contiguous(), ns
+
+
+def _per_clip(a, N, dev, dtype, what):
+    if a is None:
+        return None
+    a = torch.as_tensor(a).to(dev, dtype).reshape(-1).contiguous()
+    if a.shape[0] != N:
+        raise ValueError("%s has %d entries for %d clips" % (what, a.shape[0], N))
+    return a
+
+
+def wsola(wav, nsamples, tempo, ldo, Smax, out=None):
+    """Tempo change at constant pitch of every clip of wav (N, Lmax) (clip n = its first nsamples[n] samples) by the per-clip
+    factors tempo [N] (None = copy): ds2_wsola.  ldo / Smax: row length of the output and of the offsets (the largest
+    augment.wsola_out_len / wsola_segments of the batch).  Returns (out (N, ldo), nsamples_out [N] int32, offsets (N, Smax) int32),
+    all on the device; entries of out beyond a clip's own samples are zero."""
+    wav, ns = _wave_batch(wav, nsamples)
+    N = wav.shape[0]
+    tp = _per_clip(tempo, N, wav.device, torch.float32, "tempo")
+    if out is None:
+        out = torch.empty((N, int(ldo)), dtype=torch.float32, device=wav.device)
+    if tuple(out.shape) != (N, int(ldo)) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("out must be a contiguous float32 (N, ldo) tensor")
+    ns_out = torch.empty(N, dtype=torch.int32, device=wav.device)
+    offsets = torch.empty((N, int(Smax)), dtype=torch.int32, device=wav.device)
+    call("ds2_wsola", P(wav), wav.stride(0), P(ns), P(tp), N, P(out), int(ldo), P(ns_out), P(offsets) if Smax else P(None), int(Smax), S())
+    return out, ns_out, offsets
+
+
+def _noise_args(N, dev, level, bank, noise_off, noise_start):
+    lv = _per_clip(level, N, dev, torch.float32, "level")
+    if lv is None:
+        return None, None, 0, None, None
+    if bank is None or noise_off is None or noise_start is None:
+        raise ValueError("noise levels need a noise bank with per-clip offsets and starts")
+    if not (bank.is_cuda and bank.dtype == torch.float32 and bank.dim() == 1 and bank.is_contiguous()):
+        raise ValueError("the noise bank is a contiguous 1-D float32 HIP device tensor")
+    return (lv, bank, bank.numel(), _per_clip(noise_off, N, dev, torch.int64, "noise_off"),
+            _per_clip(noise_start, N, dev, torch.int32, "noise_start"))
+
+
+def wave_energy(wav, nsamples, gain=None, level=None, bank=None, noise_off=None, noise_start=None):
+    """Per clip the sum of squares of clamp(gain * x) and of its noise crop as fixed-order fp64 partials (N, 8, 2): ds2_wave_energy.
+    Their sum over axis 1 is (data energy, noise energy); the noise column is zero for a clip without noise."""
+    wav, ns = _wave_batch(wav, nsamples)
+    N = wav.shape[0]
+    g = _per_clip(gain, N, wav.device, torch.float32, "gain")
+    lv, bank, blen, off, start = _noise_args(N, wav.device, level, bank, noise_off, noise_start)
+    nbytes = query("ds2_wave_ws_bytes", N)
+    partial = torch.empty((N, nbytes // (16 * N), 2), dtype=torch.float64, device=wav.device)
+    call("ds2_wave_energy", P(wav), wav.stride(0), P(ns), N, P(g), P(lv), P(bank), blen, P(off), P(start), P(partial), S())
+    return partial
+
+
+def wave_mix(wav, nsamples, gain=None, level=None, bank=None, noise_off=None, noise_start=None, partial=None, out=None):
+    """out = clamp(gain * x, -1, 1) + level * rms(data) / rms(noise) * noise crop for every clip of wav (N, Lmax): ds2_wave_energy
+    (unless its `partial` is handed in, or no clip gets noise) + ds2_wave_mix.  gain [N] LINEAR factors (None = samples unchanged
+    and not clamped), level [N] (None = no noise), bank = the 1-D device noise buffer, noise_off [N] int64 (negative = no noise for
+    the clip), noise_start [N].  Returns a new (N, Lmax) tensor (or fills `out`, (N, ldo)), zero beyond a clip's own samples."""
+    wav, ns = _wave_batch(wav, nsamples)
+    N = wav.shape[0]
+    g = _per_clip(gain, N, wav.device, torch.float32, "gain")
+    lv, bank, blen, off, start = _noise_args(N, wav.device, level, bank, noise_off, noise_start)
+    if lv is not None and partial is None:
+        partial = wave_energy(wav, ns, g, lv, bank, off, start)
+    if out is None:
+        out = torch.empty_like(wav)
+    if out.dim() != 2 or out.shape[0] != N or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("out must be a contiguous float32 (N, ldo) tensor")
+    call("ds2_wave_mix", P(wav), wav.stride(0), P(ns), N, P(g), P(lv), P(bank), blen, P(off), P(start),
+         P(partial if lv is not None else None), P(out), out.shape[1], S())
+    return out

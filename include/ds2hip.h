@@ -337,6 +337,43 @@ int ds2_spec_augment_coef(const float* x, int N, int F, int Tmax, const int* fra
 int ds2_spec_augment(const float* in, float* out, int N, int F, int Tmax, const int* frames, const float* coef, const int* fmask,
                      int MF, const int* tmask, int MT, ds2_stream_t stream);
 
+/* ---- waveform augmentation on the device (what SpectrogramParser.parse_audio does to the samples before the STFT,
+ * loader/data_loader.py:151-159: load_randomly_augmented_audio, :377-404 = sox `tempo t gain g`, then NoiseInjection.inject_noise,
+ * :97-128).  Every entry works on a batch wav [N][ldw] f32 (clip n = the first nsamples[n] entries of row n; nsamples [N] int32 on
+ * the device), writes out of place into out [N][ldo] and writes the entries of a row beyond the clip's own samples as zero.  The
+ * random draws are the caller's (augment.WaveAugment.draw).
+ * Tempo = the project's own WSOLA with sox's default `tempo` parameters at 16 kHz: segment 1312, 234 candidate offsets, overlap 192;
+ * ADV = 1120.  start(k) = floor(k * tempo * 1120) in fp64; S = the number of k with start(k) + 192 <= nsamples;
+ * out_len = (S - 1) * 1120 + min(1312, nsamples - start(S - 1)).  Segment 0 sits at p(0) = 0; segment k >= 1 at p(k) = start(k) + d,
+ * d in [0, 234) the lowest arg-max of the fp32 dot product of x[p(k-1) + 1120 + j] with x[start(k) + d + j], j in [0, 192); reads at or
+ * beyond nsamples are zero.  out[1120 k + j] = x[p(k) + j], cross-faded over j < 192 as a + (j / 192) (x[p(k) + j] - a) with
+ * a = x[p(k-1) + 1120 + j]; the last segment runs to out_len.  A clip with nsamples < 1546 or a tempo outside [0.1, 10] is copied.
+ *   tempo [N] f32 (device; null = every clip is copied; exactly 1.0f still runs the algorithm)
+ *   nsamples_out [N] int32 (device): min(out_len, ldo), the sample counts of out
+ *   offsets [N][Smax] int32 (device; may be null with Smax 0): the chosen d of every segment (0 for segment 0), -1 beyond S
+ * ds2_wsola_segments / ds2_wsola_out_len: S (0 = copied) and out_len of one clip, host-only queries.  DS2_ERR_ARG: a null wav,
+ * nsamples, out or nsamples_out, wav == out, N, ldw or ldo < 1, ldo >= 2^31, Smax < 0.
+ * Gain and noise: y = clamp(gain[n] * x, -1, 1) (gain [N] f32 LINEAR factors, 10^(dB / 20); null = x unchanged, not clamped), then
+ * out = y + scale * noise[noise_off[n] + noise_start[n] + i] with scale = level[n] * sqrt(sum y^2 / sum noise^2), both sums over the
+ * clip's own samples (data_loader.py:125-127, rms(data) / rms(noise)).  bank: bank_len f32 noise samples (recordings back to back),
+ * noise_off [N] int64 the recording's first sample (negative = no noise for the clip), noise_start [N] int32 the crop's first sample
+ * inside it, level [N] f32 (<= 0 = no noise for the clip; a null level = no noise at all, bank / noise_off / noise_start unused).
+ * Reads outside the bank are zero; a crop without energy adds nothing.
+ * ds2_wave_energy writes the sums as fixed-order fp64 partials [N][8][2] (data, noise; block b of a clip sums the samples
+ * i with (i / 256) % 8 == b) into ws, ds2_wave_ws_bytes(N) bytes, 8-byte aligned; ds2_wave_mix reads them (ws may be null when level
+ * is).  DS2_ERR_ARG: a null wav, nsamples or out, wav == out, N < 1 or > 65535, a level without bank, offsets, starts or ws. */
+int ds2_wsola_segments(int nsamples, float tempo);
+long ds2_wsola_out_len(int nsamples, float tempo);
+int ds2_wsola(const float* wav, long ldw, const int* nsamples, const float* tempo, int N, float* out, long ldo, int* nsamples_out,
+              int* offsets, int Smax, ds2_stream_t stream);
+long ds2_wave_ws_bytes(int N);
+int ds2_wave_energy(const float* wav, long ldw, const int* nsamples, int N, const float* gain, const float* level,
+                    const float* bank, long bank_len, const long long* noise_off, const int* noise_start, void* ws,
+                    ds2_stream_t stream);
+int ds2_wave_mix(const float* wav, long ldw, const int* nsamples, int N, const float* gain, const float* level, const float* bank,
+                 long bank_len, const long long* noise_off, const int* noise_start, const void* ws, float* out, long ldo,
+                 ds2_stream_t stream);
+
 /* ---- greedy CTC decoding on the device (validation_step, model.py:256 -> GreedyDecoder.decode, decoder.py:164-181) -------
  * x[n*stride_n + t*stride_t + c] f32 scores (probabilities or logits), C <= 64; sizes [N] int32 on the device (null = T).
  * Per sample: arg-max per frame (first maximum), repeats collapsed, blanks dropped.  tokens / offsets [N][T] int32 (the first
