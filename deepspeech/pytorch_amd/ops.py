@@ -1145,6 +1145,77 @@ def ctc_loss_grad(logits, targets_i32, target_offsets, input_lengths, target_len
     return loss, nll, dlogits
 
 
+CTC_ALIGN_MAX_TARGET_LEN = 2047      # ds2_ctc_align: labels of one target
+CTC_ALIGN_MODES = {"logits": 0, "probs": 1, "log_probs": 2}
+
+
+def ctc_align(x, sizes, targets, target_lengths, blank=0, mode="probs", max_target_len=None):
+    """CTC forced alignment (ds2_ctc_align): the best path of every clip's KNOWN target through the network's outputs.
+    x: (N, T', C) float32 CUDA tensor, any strides with a contiguous class dimension (the transposed view DeepSpeech.forward returns
+    is read in place); mode: what x holds, "logits", "probs" or "log_probs" (or 0, 1, 2).  sizes: [N] valid frames; targets: the
+    flat concatenation of the clips' labels; target_lengths: [N]; each on the host or on the device.
+    Returns device tensors (frame_state (N, T') int32, tok_start, tok_end int32 and tok_logp float32 flat like targets, score [N]
+    float32); a clip without a path has score -inf, frame_state / tok_start / tok_end -1 and tok_logp 0 (include/ds2hip.h).
+    No host synchronisation: with target_lengths on the host the longest target is known; with target_lengths on the device pass
+    max_target_len, or the lattice is sized for min(len(targets), CTC_ALIGN_MAX_TARGET_LEN) labels.  A clip longer than that bound
+    comes back without a path.  Host lengths are checked to add up to len(targets); lengths that live on the device cannot be
+    checked without reading them back, so that they are >= 0 and add up to at most len(targets) is the CALLER's contract there:
+    the kernel reads targets and writes the label outputs at the offsets the lengths give."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32):
+        raise ValueError("ctc_align takes a float32 HIP device tensor of shape (N, T', C)")
+    N, Tp, Cc = x.shape
+    if N < 1 or Tp < 1 or Cc < 1:
+        raise ValueError("ctc_align needs at least one clip, one frame and one class; got shape %s" % (tuple(x.shape),))
+    m = CTC_ALIGN_MODES.get(mode, mode)
+    if m not in (0, 1, 2):
+        raise ValueError("mode must be one of %s, got %r" % (sorted(CTC_ALIGN_MODES), mode))
+    if not 0 <= int(blank) < Cc:
+        raise ValueError("blank index %d out of range for %d classes" % (blank, Cc))
+    if x.stride(2) != 1:
+        x = x.contiguous()
+    dev = x.device
+    sz = torch.as_tensor(sizes).reshape(-1)
+    tlh = torch.as_tensor(target_lengths).reshape(-1)
+    tg = torch.as_tensor(targets).reshape(-1)
+    if sz.shape[0] != N or tlh.shape[0] != N:
+        raise ValueError("sizes has %d and target_lengths %d entries for %d clips" % (sz.shape[0], tlh.shape[0], N))
+    total = tg.shape[0]
+    prefill = False
+    if not tlh.is_cuda:                                    # host lengths: checked here, nothing is read back
+        longest = int(tlh.max())
+        if int(tlh.min()) < 0 or longest > CTC_ALIGN_MAX_TARGET_LEN:
+            raise ValueError("a target has %d labels; ctc_align takes 0 to %d" % (longest, CTC_ALIGN_MAX_TARGET_LEN))
+        if int(tlh.sum()) != total:
+            raise ValueError("target_lengths add up to %d labels, targets has %d" % (int(tlh.sum()), total))
+        if max_target_len is None:
+            max_target_len = longest
+        elif max_target_len < longest:
+            raise ValueError("max_target_len is %d, the longest target has %d labels" % (max_target_len, longest))
+    elif max_target_len is None:
+        max_target_len = min(total, CTC_ALIGN_MAX_TARGET_LEN)
+        prefill = total > CTC_ALIGN_MAX_TARGET_LEN         # a clip beyond the cap leaves its label entries untouched
+    if not 0 <= int(max_target_len) <= CTC_ALIGN_MAX_TARGET_LEN:
+        raise ValueError("max_target_len must be in [0, %d], got %d" % (CTC_ALIGN_MAX_TARGET_LEN, max_target_len))
+    max_target_len = int(max_target_len)
+    sz = sz.to(dev, torch.int32).contiguous()
+    tl = tlh.to(dev, torch.int32).contiguous()
+    tg = tg.to(dev, torch.int32).contiguous()
+    if total == 0:                                         # every target is empty: the entry still takes a non-null pointer
+        tg = torch.zeros(1, dtype=torch.int32, device=dev)
+    offs = (torch.cumsum(tl, 0, dtype=torch.int32) - tl).contiguous()
+    frame_state = torch.empty((N, Tp), dtype=torch.int32, device=dev)
+    tok = torch.empty((2, max(total, 1)), dtype=torch.int32, device=dev)
+    tok_logp = torch.empty(max(total, 1), dtype=torch.float32, device=dev)
+    if prefill:
+        tok.fill_(-1)
+        tok_logp.zero_()
+    score = torch.empty(N, dtype=torch.float32, device=dev)
+    ws = torch.empty(query("ds2_ctc_align_ws_bytes", Tp, N, max_target_len), dtype=torch.uint8, device=dev)
+    call("ds2_ctc_align", P(x), x.stride(0), x.stride(1), N, Tp, Cc, m, P(sz), P(tg), P(offs), P(tl), max_target_len, int(blank),
+         P(frame_state), P(tok[0]), P(tok[1]), P(tok_logp), P(score), P(ws), S())
+    return frame_state, tok[0, :total], tok[1, :total], tok_logp[:total], score
+
+
 # ---- waveform augmentation (csrc/ds2_waveaug.hip) ---------------------------------------------------------------------------
 def _wave_batch(wav, nsamples):
     if not (torch.is_tensor(wav) and wav.is_cuda and wav.dim() == 2 and wav.dtype == torch.float32):

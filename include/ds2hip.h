@@ -434,6 +434,33 @@ int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N,
 int ds2_error_counts(const int* hyp, long hyp_stride, const int* hyp_lens, int P, const int* ref, const int* ref_offsets, int R,
                      int space, int* char_err, int* word_err, int* ref_chars, int* ref_words, ds2_stream_t stream);
 
+/* ---- CTC forced alignment on the device: the best (Viterbi) path of a KNOWN transcript and per-label frame spans --------------
+ * x[n*stride_n + t*stride_t + c] f32, addressed as the decoders address it; mode 0: logits (log-softmax over the C classes in fp32,
+ * with ds2_ctc_loss_grad's summation order), 1: probabilities (logf; a probability of 0 is -inf), 2: log-probabilities as they
+ * are.  sizes [N] int32 on the device (null = Tp); targets / target_offsets / target_lengths as for ds2_ctc_loss_grad.
+ * Lattice over ext[2i] = blank, ext[2i+1] = target[i] (S = 2L + 1 states), fp32, unreachable states exactly -inf:
+ *   v[0][0] = lp[0][blank], v[0][1] = lp[0][ext[1]];  v[t][s] = lp[t][ext[s]] + max(v[t-1][s], v[t-1][s-1], v[t-1][s-2]),
+ *   the s-2 predecessor only when ext[s] is a label that differs from ext[s-2].
+ * Tie rule: among equal predecessors s, then s-1, then s-2; at the end an equal value goes to state 2L rather than 2L - 1.
+ * Outputs (device; EVERY element is written on every call):
+ *   frame_state [N][Tp] int32: the lattice state of every frame (label index = state >> 1 for an odd state, blank for an even
+ *                 one); -1 for t >= sizes[n] and for a clip without a path
+ *   tok_start / tok_end (flat like targets) int32: first / last frame (inclusive) of every label; tok_logp f32: the sum of the
+ *                 label's frame log-probabilities in increasing frame order
+ *   score [N] f32: log-probability of the best path; -inf when no path exists (sizes[n] = 0, fewer frames than labels plus
+ *                 adjacent equal labels, a best value of -inf, a label outside [0, C)): then the clip's frame_state, tok_start and
+ *                 tok_end are -1 and its tok_logp 0.
+ * max_target_len: at least max over target_lengths, at most 2047.  A clip whose target_lengths[n] lies outside
+ * [0, max_target_len] gets score -inf and frame_state -1 and its tok entries are NOT touched (the length cannot be trusted).
+ * ws: ds2_ctc_align_ws_bytes(Tp, N, max_target_len) bytes, 4-byte aligned ([N][Tp] f32 log-normalisers, then one back-pointer
+ * byte per (n, t, state) with a row stride of 2 max_target_len + 1 rounded up to 4); -1 for arguments ds2_ctc_align refuses.
+ * Same bits on every launch.  DS2_ERR_ARG: N, Tp or C < 1, blank outside [0, C), mode outside [0, 2], max_target_len outside
+ * [0, 2047], a null pointer other than sizes. */
+long ds2_ctc_align_ws_bytes(int Tp, int N, int max_target_len);
+int ds2_ctc_align(const float* x, long stride_n, long stride_t, int N, int Tp, int C, int mode, const int* sizes, const int* targets,
+                  const int* target_offsets, const int* target_lengths, int max_target_len, int blank, int* frame_state,
+                  int* tok_start, int* tok_end, float* tok_logp, float* score, void* ws, ds2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
