@@ -5,7 +5,8 @@
 //
 // The 320-point real DFT of every frame is one fp32 MFMA GEMM: the frames of an utterance are the rows of a matrix with row
 // stride = hop (overlapping rows of the centre-padded waveform, no frame copy), the basis [2*161][320] carries the window.
-//   k_spect_pad   : waveform -> centre-padded copy (zeros = librosa >= 0.10 default, or reflect = older default)
+//   k_spect_pad   : waveform -> centre-padded copy (zeros = librosa >= 0.10 default, or reflect = older default: np.pad's
+//                   "reflect", which keeps folding when the clip is shorter than the 160-sample pad)
 //   ds2_gemm_nt   : C[t][0:161] = Re, C[t][161:322] = Im      (v_mfma_f32_32x32x2_f32, exact fp32 products)
 //   k_spect_stats : per utterance sum / sum of squares of log1p(|X|) over its own frames (fp64 partials, fixed order)
 //   k_spect_write : normalise, transpose to [f][t] through LDS, zero the padding frames
@@ -37,9 +38,15 @@ __global__ void __launch_bounds__(256) k_spect_pad(const float* __restrict__ wav
   long s = i - NFFT / 2;
   float v = 0.f;
   if (i < (long)L + NFFT) {              // inside this utterance's padded extent
-    if (reflect) {
-      if (s < 0) s = -s;
-      if (s >= L) s = 2 * ((long)L - 1) - s;
+    if (reflect && (s < 0 || s >= L)) {  // np.pad(mode = "reflect"): fold with period 2 (L - 1) as often as a short clip needs
+      const long p = 2 * ((long)L - 1);
+      if (p == 0) {
+        s = 0;                           // a single sample repeats
+      } else {
+        s %= p;
+        if (s < 0) s += p;
+        if (s >= L) s = p - s;
+      }
     }
     if (s >= 0 && s < L) v = wav[(long)n * ldw + s];
   }

@@ -9,7 +9,9 @@ to come from elsewhere); the window type follows ``SpectConfig.window`` (enums.p
 data_loader.py:151-159) on the device, so one call covers everything ``parse_audio`` does.
 
 The reference's STFT lives in a third-party dependency that is not vendored and not pinned (``librosa``, requirements.txt:4):
-``center=True`` padding is zeros in librosa >= 0.10 (``pad_mode="constant"``, the default here) and reflection before."""
+``center=True`` padding is zeros in librosa >= 0.10 (``pad_mode="constant"``, the default here) and reflection before
+(``pad_mode="reflect"`` = ``np.pad(y, 160, "reflect")`` for every length >= 1: a clip shorter than the pad is folded as often as
+it takes, a single sample repeats)."""
 import math
 
 import numpy as np

@@ -684,6 +684,10 @@ def spect_window(name="hamming", n=320):
         return 0.54 - 0.46 * np.cos(2 * np.pi * k / n)
     if name == "hann":
         return 0.5 - 0.5 * np.cos(2 * np.pi * k / n)
+    if name == "blackman":
+        return 0.42 - 0.5 * np.cos(2 * np.pi * k / n) + 0.08 * np.cos(4 * np.pi * k / n)
+    if name == "bartlett":
+        return 1.0 - np.abs(2.0 * k / n - 1.0)
     raise ValueError(name)
 
 

@@ -165,3 +165,50 @@ def test_log_spectrogram_oracle_against_torch_stft(pad_mode):
         t = torch.from_numpy(ref)
         refn = ((t - t.mean()) / t.std()).numpy()
         assert np.abs(O.log_spectrogram(y, pad_mode=pad_mode) - refn).max() < 1e-9
+
+
+@pytest.mark.parametrize("name", ["hamming", "hann", "blackman", "bartlett"])
+def test_oracle_windows_equal_scipy(name):
+    """The oracle's own window table (the reference of the device front-end's window tests) against scipy's periodic windows."""
+    import scipy.signal as ss
+    assert np.abs(O.spect_window(name, 320) - ss.get_window(name, 320, fftbins=True)).max() < 1e-12
+
+
+def test_log_spectrogram_oracle_reflect_against_torch_stft_at_short_lengths():
+    """torch.stft's reflect padding needs a clip longer than the 160-sample pad; from 161 samples on it is a second implementation
+    of the centre padding for clips of two and three frames."""
+    import torch
+    rs = np.random.RandomState(5)
+    win = torch.hamming_window(320, periodic=True, dtype=torch.float64)
+    for n in (161, 163, 319, 320, 321):
+        y = rs.standard_normal(n) * 0.3 + 0.01
+        Z = torch.stft(torch.from_numpy(y), n_fft=320, hop_length=160, win_length=320, window=win, center=True, pad_mode="reflect",
+                       return_complex=True)
+        raw = O.log_spectrogram(y, normalize=False, pad_mode="reflect")
+        assert raw.shape == tuple(Z.shape) == (161, 1 + n // 160)
+        assert np.abs(raw - torch.log1p(Z.abs()).numpy()).max() < 1e-9
+
+
+@pytest.mark.parametrize("L", [1, 2, 80, 81, 160])
+def test_log_spectrogram_oracle_reflect_folds_short_clips_as_np_pad_does(L):
+    """Clips no longer than the pad (and the two-frame clip of 160 samples, whose last frame reads padded index 319) need more
+    than one fold.  Padded sample i is y[tri(i - 160)] with tri the triangle wave of period 2 (L - 1) -- stated here index by
+    index, checked against np.pad, then transformed frame by frame with scipy's window."""
+    import scipy.signal as ss
+    y = np.random.RandomState(L).standard_normal(L) * 0.3 + 0.01
+    s = np.arange(L + 320) - 160
+    if L == 1:
+        idx = np.zeros_like(s)
+    else:
+        p = 2 * (L - 1)
+        idx = np.mod(s, p)
+        idx = np.where(idx >= L, p - idx, idx)
+    yp = y[idx]
+    assert np.array_equal(yp, np.pad(y, 160, mode="reflect"))
+    T = 1 + L // 160
+    w = ss.get_window("hamming", 320, fftbins=True)
+    ref = np.stack([np.log1p(np.abs(np.fft.rfft(yp[160 * t:160 * t + 320] * w))) for t in range(T)], 1)
+    raw = O.log_spectrogram(y, normalize=False, pad_mode="reflect")
+    assert raw.shape == ref.shape == (161, T)
+    assert np.abs(raw - ref).max() < 1e-12
+    assert np.abs(O.log_spectrogram(y, pad_mode="reflect") - (ref - ref.mean()) / ref.std(ddof=1)).max() < 1e-9
