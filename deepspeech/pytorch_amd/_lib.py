@@ -93,6 +93,14 @@ SIGNATURES = {
     "ds2_beam_grid_ws_bytes": (_l, [_i, _i, _i, _i]),
     "ds2_beam_decode_lm_grid": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_greedy_stream_feed": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_beam_stream_bytes": (_l, [_i, _i, _i, _i]),
+    "ds2_beam_stream_ws_bytes": (_l, [_i, _i]),
+    "ds2_beam_stream_state_stride": (_l, [_i, _i]),
+    "ds2_beam_stream_reset": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "ds2_beam_stream_feed": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp]),
+    "ds2_beam_stream_feed_lm": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _f, _f, _i,
+                                     _vp, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp]),
     "ds2_error_counts": (_i, [_vp, _l, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ds2_ctc_ws_floats": (_l, [_i, _i, _i, _i]),
     "ds2_ctc_loss_grad": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _l, _vp, _i, _vp]),

@@ -37,6 +37,9 @@
 // arguments exist only in the LM instantiation.
 // k_beam_search<true, LmArgs, GridArgs> (ds2_beam_decode_lm_grid) is the LM search on (N, G) workgroups for G weight points: one
 // prune launch, workgroup (n, g) takes alphas[g] / betas[g] and node pool g, and writes its top beam only.
+// k_beam_search<false, StreamArgs> / <true, LmArgs, StreamArgs> (ds2_beam_stream_feed / _feed_lm) is the resumable search: workgroup
+// n loads the state of stream n (nb, BeamState, LmState) from a device buffer, runs this chunk's frames numbered from the start of
+// the stream in a node pool that outlives the launch, and stores the state back; the output stage is optional and changes nothing.
 #include <float.h>
 
 #include "ds2_common.h"
@@ -207,6 +210,32 @@ __device__ __forceinline__ LmArgs lm_args(const LmArgs& a, const GridArgs& g) {
 }
 __device__ __forceinline__ long grid_pool(const LmArgs&, const GridArgs& g) { return (long)blockIdx.y * g.pool_stride; }
 
+// A resumable search (ds2_beam_stream_feed, ds2_beam_stream_feed_lm): workgroup n continues stream n from the state that the
+// previous feed stored.  Per stream the state is a header of four ints (frames consumed, live beams nb, overflow flag, unused)
+// followed by the beams' fields as arrays of B entries each: hash, pb, pnb, lpc, len, last, node, and with an LM whash, lm, spb, wid,
+// ctx[0 .. 3].  The node pool [N][max_frames + 1][B] belongs to the session; frames, node slots and offsets count from the start of
+// the stream.
+struct StreamArgs {
+  char* state;              // [N] x state_stride bytes
+  long state_stride;
+  int max_frames;
+  long row_stride;          // ints between two rows of tokens / offsets (>= the largest consumed count)
+  int out_ranks;            // the output stage writes the best out_ranks beams of every stream (1 .. B)
+};
+constexpr int kStreamHeader = 16;                      // bytes
+constexpr int kStreamBeamBytes = 8 + 6 * 4;            // per beam: hash; pb, pnb, lpc, len, last, node
+constexpr int kStreamLmBytes = 8 + (3 + BEAM_LM_MAX_ORDER - 1) * 4;   // whash; lm, spb, wid, ctx[]
+
+__device__ __forceinline__ NoLm lm_args(const StreamArgs&) { return {}; }
+__device__ __forceinline__ LmArgs lm_args(const LmArgs& a, const StreamArgs&) { return a; }
+__device__ __forceinline__ const StreamArgs& stream_args(const StreamArgs& s) { return s; }
+__device__ __forceinline__ const StreamArgs& stream_args(const LmArgs&, const StreamArgs& s) { return s; }
+
+// whether the last of the kernel's trailing argument types is X
+template <class X, class... Extra> struct LastIs { static constexpr bool value = false; };
+template <class X, class A> struct LastIs<X, A> { static constexpr bool value = __is_same(A, X); };
+template <class X, class A, class B, class... Extra> struct LastIs<X, A, B, Extra...> : LastIs<X, B, Extra...> {};
+
 // ---- per-frame pruning --------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_beam_prune(const float* __restrict__ x, long stride_n, long stride_t, int N, int T, int C,
                                                     const int* __restrict__ sizes, int K, int use_cut, double cutoff_prob,
@@ -281,7 +310,8 @@ __device__ __forceinline__ uint64_t cand_key(float s, int i, int cls1) {
   return ((uint64_t)ord_bits(s) << 32) | (uint32_t)~(((uint32_t)i << BEAM_TIE_CLASS_BITS) | (uint32_t)cls1);
 }
 
-// Extra is empty (LM = false), one LmArgs (LM = true) or LmArgs, GridArgs (LM = true, launched as (N, G) workgroups)
+// Extra is empty (LM = false), one LmArgs (LM = true), LmArgs, GridArgs (LM = true, launched as (N, G) workgroups), or either of
+// the first two followed by StreamArgs (the resumable form)
 template <bool LM, class... Extra>
 __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, const int* __restrict__ sizes, int blank, int B, int K,
                                                               const int* __restrict__ pcnt, const int* __restrict__ pcls,
@@ -303,14 +333,31 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
   __shared__ uint64_t s_prefix, s_mask;
   __shared__ unsigned s_need;
 
-  constexpr bool GRID = sizeof...(Extra) == 2;
+  constexpr bool GRID = LastIs<GridArgs, Extra...>::value, STREAM = LastIs<StreamArgs, Extra...>::value;
   [[maybe_unused]] const auto A = lm_args(extra...);
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   int size = sizes ? sizes[n] : T;
   size = size < 0 ? 0 : (size > T ? T : size);
-  const long fbase = (long)n * T;
+  long fbase = (long)n * T;                            // kept list of frame t at fbase + t
   long pool = (long)n * (T + 1) * B;
   if constexpr (GRID) pool += grid_pool(extra...);
+  int t0 = 0;                                          // frames before this launch's first one (a stream's consumed count)
+  long rows = T;                                       // ints between two rows of tokens / offsets
+  [[maybe_unused]] int* hdr = nullptr;
+  if constexpr (STREAM) {
+    const StreamArgs& SA = stream_args(extra...);
+    hdr = (int*)(SA.state + (long)n * SA.state_stride);
+    t0 = hdr[0];
+    if (t0 < 0 || (long)t0 + size > SA.max_frames) {   // the chunk does not fit the pool: nothing is consumed
+      if (size > 0 && tid == 0) hdr[2] = 1;
+      size = 0;
+      t0 = t0 < 0 ? 0 : t0;
+    }
+    fbase -= t0;
+    pool = (long)n * (SA.max_frames + 1) * B;
+    rows = SA.row_stride;
+  }
+  const int tend = t0 + size;
   int* parent = parent_ + pool;
   int* label = label_ + pool;
   int* frame = frame_ + pool;
@@ -336,19 +383,49 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
     }
   }
   int nb = 1, cur = 0;
+  if constexpr (STREAM) {
+    if (t0 > 0) {                                      // a stream under way: the state that the previous feed stored
+      nb = hdr[1];
+      nb = nb < 0 ? 0 : (nb > B ? B : nb);
+      if (tid < nb) {
+        const char* sp = (const char*)hdr + kStreamHeader;
+        const float* sf = (const float*)(sp + 8l * B);
+        const int* si = (const int*)(sf + 3l * B);
+        st[0].hash[tid] = ((const uint64_t*)sp)[tid];
+        st[0].pb[tid] = sf[tid];
+        st[0].pnb[tid] = sf[B + tid];
+        st[0].lpc[tid] = sf[2 * B + tid];
+        st[0].len[tid] = si[tid];
+        st[0].last[tid] = si[B + tid];
+        st[0].node[tid] = si[2 * B + tid];
+        if constexpr (LM) {
+          LmState* L = lm_state();
+          const char* lp = sp + (long)kStreamBeamBytes * B;
+          const float* lf = (const float*)(lp + 8l * B);
+          const int* li = (const int*)(lf + 2l * B);
+          L[0].whash[tid] = ((const uint64_t*)lp)[tid];
+          L[0].lm[tid] = lf[tid];
+          L[0].spb[tid] = lf[B + tid];
+          L[0].wid[tid] = li[tid];
+#pragma unroll
+          for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) L[0].ctx[m][tid] = li[(1 + m) * B + tid];
+        }
+      }
+    }
+  }
   // kept list of the next frame, in registers of wave 0 (lane k holds slot k)
   int pf_cnt = 0, pf_c = 0;
   float pf_lp = 0.f;
   if (size > 0) {
-    pf_cnt = pcnt[fbase];
+    pf_cnt = pcnt[fbase + t0];
     if (tid < K) {
-      pf_c = pcls[fbase * BEAM_MAXK + tid];
-      pf_lp = plp[fbase * BEAM_MAXK + tid];
+      pf_c = pcls[(fbase + t0) * BEAM_MAXK + tid];
+      pf_lp = plp[(fbase + t0) * BEAM_MAXK + tid];
     }
   }
   __syncthreads();
 
-  for (int t = 0; t < size; ++t) {
+  for (int t = t0; t < tend; ++t) {
     const BeamState& S = st[cur];
     BeamState& D = st[cur ^ 1];
     // ---- P1
@@ -374,7 +451,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
     if (tid == 0) s_nsel = 0;
     __syncthreads();
     // prefetch the next frame's kept list (hidden behind this step)
-    if (t + 1 < size) {
+    if (t + 1 < tend) {
       pf_cnt = pcnt[fbase + t + 1];
       if (tid < K) {
         pf_c = pcls[(fbase + t + 1) * BEAM_MAXK + tid];
@@ -582,6 +659,40 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
     __syncthreads();
   }
 
+  if constexpr (STREAM) {
+    if (size > 0) {                                    // the state after this chunk, for the next feed
+      const BeamState& E = st[cur];
+      if (tid < nb) {
+        char* sp = (char*)hdr + kStreamHeader;
+        float* sf = (float*)(sp + 8l * B);
+        int* si = (int*)(sf + 3l * B);
+        ((uint64_t*)sp)[tid] = E.hash[tid];
+        sf[tid] = E.pb[tid];
+        sf[B + tid] = E.pnb[tid];
+        sf[2 * B + tid] = E.lpc[tid];
+        si[tid] = E.len[tid];
+        si[B + tid] = E.last[tid];
+        si[2 * B + tid] = E.node[tid];
+        if constexpr (LM) {
+          const LmState& LE = lm_state()[cur];
+          char* lp = sp + (long)kStreamBeamBytes * B;
+          float* lf = (float*)(lp + 8l * B);
+          int* li = (int*)(lf + 2l * B);
+          ((uint64_t*)lp)[tid] = LE.whash[tid];
+          lf[tid] = LE.lm[tid];
+          lf[B + tid] = LE.spb[tid];
+          li[tid] = LE.wid[tid];
+#pragma unroll
+          for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) li[(1 + m) * B + tid] = LE.ctx[m][tid];
+        }
+      }
+      if (tid == 0) {
+        hdr[0] = tend;
+        hdr[1] = nb;
+      }
+    }
+    if (!tokens) return;                               // a feed without the output stage
+  }
   // ---- output: one thread per rank walks the parent links
   __threadfence();
   __syncthreads();
@@ -608,15 +719,23 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
     }
   }
   // every rank writes its row; in a grid only rank 0 does (thread 0 where no beam is alive), at row (g, n)
-  const bool emit = GRID ? orank == 0 : true;
+  bool emit = GRID ? orank == 0 : true;
+  if constexpr (STREAM) emit = orank < stream_args(extra...).out_ranks;   // a stream writes its best out_ranks beams only
   if (tid < B && emit) {
-    const long o = GRID ? (long)blockIdx.y * gridDim.x + n : (long)n * B + orank;
+    long o = GRID ? (long)blockIdx.y * gridDim.x + n : (long)n * B + orank;
+    if constexpr (STREAM) o = (long)n * stream_args(extra...).out_ranks + orank;
     if (tid < nb) {
       const int len = S.len[tid];
       int node = S.node[tid];
-      int* tok = tokens + o * T;
-      int* off = GRID && !offsets ? nullptr : offsets + o * T;
+      int* tok = tokens + o * rows;
+      int* off = GRID && !offsets ? nullptr : offsets + o * rows;
       for (int pos = len - 1; pos >= 0 && node >= 0; --pos) {
+        if constexpr (STREAM) {
+          if (pos >= rows) {                           // a row shorter than the string: never written past
+            node = parent[node];
+            continue;
+          }
+        }
         tok[pos] = label[node];
         if (!GRID || off) off[pos] = frame[node];
         node = parent[node];
@@ -662,6 +781,41 @@ WsLayout ws_layout(int N, int T, int B, int G = 1) {
 int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
                 int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
                 const LmArgs* lm, int G = 1, const float* alphas = nullptr, const float* betas = nullptr);
+
+// A stream session's buffer: the states, then the node pool's three arrays
+struct StreamLayout {
+  long state_stride, parent, label, frame, total;   // bytes
+};
+
+StreamLayout stream_layout(int N, int B, int max_frames, bool lm) {
+  StreamLayout L;
+  L.state_stride = align256(kStreamHeader + (long)B * (kStreamBeamBytes + (lm ? kStreamLmBytes : 0)));
+  const long pool = align256((long)N * ((long)max_frames + 1) * B * 4);
+  L.parent = (long)N * L.state_stride;
+  L.label = L.parent + pool;
+  L.frame = L.label + pool;
+  L.total = L.frame + pool;
+  return L;
+}
+
+// the kept lists of one chunk
+WsLayout stream_ws_layout(int N, int Tc) {
+  WsLayout L = {};
+  const long frames = (long)N * Tc;
+  L.cls = align256(frames * 4);
+  L.lp = L.cls + align256(frames * BEAM_MAXK * 4);
+  L.total = L.lp + align256(frames * BEAM_MAXK * 4);
+  return L;
+}
+
+__global__ void k_beam_stream_reset(char* state, long state_stride, int N, const int* __restrict__ mask) {
+  const int n = blockIdx.x * blockDim.x + threadIdx.x;
+  if (n < N && (!mask || mask[n])) *(int4*)(state + (long)n * state_stride) = make_int4(0, 0, 0, 0);
+}
+
+int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                     int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets, long row_stride,
+                     int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm);
 
 // the checks and the fields that ds2_beam_decode_lm and its grid form share; alpha and beta are left to the caller
 int lm_args_from(LmArgs& A, int C, int blank, int space, const void* word_table, long word_slots, const void* ngram_table,
@@ -723,6 +877,67 @@ int ds2_beam_decode_lm(const float* x, long stride_n, long stride_t, int N, int 
                      (hipStream_t)st_, &A);
 }
 
+long ds2_beam_stream_bytes(int N, int B, int max_frames, int lm) {
+  if (N <= 0 || B <= 0 || max_frames <= 0) return 0;
+  return stream_layout(N, B, max_frames, lm != 0).total;
+}
+
+// bytes between two streams' states at the front of a session's buffer
+long ds2_beam_stream_state_stride(int B, int lm) {
+  if (B <= 0) return 0;
+  return stream_layout(1, B, 1, lm != 0).state_stride;
+}
+
+long ds2_beam_stream_ws_bytes(int N, int Tc) {
+  if (N <= 0 || Tc <= 0) return 0;
+  return stream_ws_layout(N, Tc).total;
+}
+
+// state: the session's buffer, ds2_beam_stream_bytes(N, B, max_frames, lm) bytes, 256-byte aligned.  mask: [N] device int32, a
+// stream with a non-zero entry starts again from the empty beam (null = every stream); the others are untouched.  A new buffer is
+// reset as a whole before its first feed.
+int ds2_beam_stream_reset(void* state, int N, int B, int max_frames, int lm, const int* mask, ds2_stream_t st_) {
+  DS2_REQUIRE(state && N > 0 && B >= 1 && B <= BEAM_MAXB && max_frames > 0, DS2_ERR_ARG);
+  DS2_REQUIRE(((uintptr_t)state & 255) == 0, DS2_ERR_ALIGN);
+  const StreamLayout L = stream_layout(N, B, max_frames, lm != 0);
+  hipLaunchKernelGGL(k_beam_stream_reset, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)st_, (char*)state,
+                     L.state_stride, N, mask);
+  DS2_CHECK_LAUNCH();
+  return 0;
+}
+
+// One chunk of every stream: x is the chunk (N, Tc, C) with ds2_beam_decode's strides, sizes [N] (device int32, null = Tc) the
+// frames of it that each stream takes, 0 leaving that stream as it is.  A stream whose consumed count would pass max_frames
+// takes nothing and has its overflow flag (the third int of its state) set.  tokens / offsets / lens / scores are either all null
+// (no output stage) or all given: then rows (n, b), b < out_ranks <= B, of tokens / offsets, row_stride ints apart with row_stride
+// >= the largest consumed count, lens [N][out_ranks] and scores [N][out_ranks] are the best out_ranks beams that ds2_beam_decode
+// gives on the frames consumed so far, bit for bit, and the state is left as the feed left it.  Tc == 0 (x, sizes and ws unused) only runs the output stage.
+// ws: ds2_beam_stream_ws_bytes(N, Tc) bytes, 256-byte aligned.  B, max_frames, blank and the cutoffs are the session's: the same
+// in every call on one state buffer.
+int ds2_beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                         int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets,
+                         long row_stride, int out_ranks, int* lens, float* scores, void* ws, ds2_stream_t st_) {
+  return beam_stream_feed(x, stride_n, stride_t, N, Tc, C, sizes, blank, B, cutoff_top_n, cutoff_prob, state, max_frames, tokens,
+                          offsets, row_stride, out_ranks, lens, scores, ws, (hipStream_t)st_, nullptr);
+}
+
+// ds2_beam_stream_feed with the language model of ds2_beam_decode_lm (the same tables and weights in every call on one state
+// buffer, which was sized with lm = 1).  The output stage includes the end-of-utterance bonus and re-rank, which read the state
+// and leave it unchanged; acoustic [N][out_ranks] may be null.
+int ds2_beam_stream_feed_lm(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                            int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                            const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
+                            void* state, int max_frames, int* tokens, int* offsets, long row_stride, int out_ranks, int* lens,
+                            float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
+  LmArgs A;
+  const int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  if (rc) return rc;
+  A.alpha = alpha;
+  A.beta = beta;
+  return beam_stream_feed(x, stride_n, stride_t, N, Tc, C, sizes, blank, B, cutoff_top_n, cutoff_prob, state, max_frames, tokens,
+                          offsets, row_stride, out_ranks, lens, scores, ws, (hipStream_t)st_, &A);
+}
+
 long ds2_beam_grid_ws_bytes(int G, int N, int T, int B) {
   if (G <= 0 || N <= 0 || T <= 0 || B <= 0) return 0;
   return ws_layout(N, T, B, G).total;
@@ -779,6 +994,45 @@ int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int 
   else
     hipLaunchKernelGGL((k_beam_search<false>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls, plp,
                        (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores);
+  DS2_CHECK_LAUNCH();
+  return 0;
+}
+
+int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                     int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets, long row_stride,
+                     int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm) {
+  DS2_REQUIRE(N > 0 && Tc >= 0 && C > 0 && C <= BEAM_MAXC && blank >= 0 && blank < C, DS2_ERR_ARG);
+  DS2_REQUIRE(B >= 1 && B <= BEAM_MAXB && cutoff_top_n >= 1, DS2_ERR_ARG);
+  const int K = cutoff_top_n < C ? cutoff_top_n : C;
+  DS2_REQUIRE(K <= BEAM_MAXK, DS2_ERR_ARG);
+  DS2_REQUIRE(state && max_frames > 0 && ((long)max_frames + 1) * B <= 0x7fffffffl, DS2_ERR_ARG);
+  const bool out = tokens != nullptr;
+  DS2_REQUIRE(out == (offsets != nullptr) && out == (lens != nullptr) && out == (scores != nullptr), DS2_ERR_ARG);
+  DS2_REQUIRE(!out || (row_stride >= 0 && out_ranks >= 1 && out_ranks <= B), DS2_ERR_ARG);
+  DS2_REQUIRE(Tc > 0 ? (x && ws) : out, DS2_ERR_ARG);
+  DS2_REQUIRE((((uintptr_t)ws | (uintptr_t)state) & 255) == 0, DS2_ERR_ALIGN);
+  const StreamLayout SL = stream_layout(N, B, max_frames, lm != nullptr);
+  const WsLayout L = stream_ws_layout(N, Tc);
+  char* w = (char*)ws;
+  char* sb = (char*)state;
+  int* pcnt = (int*)(w + L.cnt);
+  int* pcls = (int*)(w + L.cls);
+  float* plp = (float*)(w + L.lp);
+  if (Tc > 0) {
+    const int use_cut = cutoff_prob < 1.0f;
+    const long frames = (long)N * Tc;
+    hipLaunchKernelGGL(k_beam_prune, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, x, stride_n, stride_t, N, Tc, C, sizes, K,
+                       use_cut, (double)cutoff_prob, pcnt, pcls, plp);
+    DS2_CHECK_LAUNCH();
+  }
+  const StreamArgs SA = {sb, SL.state_stride, max_frames, row_stride, out_ranks};
+  if (lm)
+    hipLaunchKernelGGL((k_beam_search<true, LmArgs, StreamArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, Tc, C, sizes, blank, B, K, pcnt,
+                       pcls, plp, (int*)(sb + SL.parent), (int*)(sb + SL.label), (int*)(sb + SL.frame), tokens, offsets, lens, scores,
+                       *lm, SA);
+  else
+    hipLaunchKernelGGL((k_beam_search<false, StreamArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, Tc, C, sizes, blank, B, K, pcnt, pcls,
+                       plp, (int*)(sb + SL.parent), (int*)(sb + SL.label), (int*)(sb + SL.frame), tokens, offsets, lens, scores, SA);
   DS2_CHECK_LAUNCH();
   return 0;
 }

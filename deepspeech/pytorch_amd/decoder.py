@@ -53,6 +53,61 @@ class GreedyDecoder:
         strings = [[''.join(' ' if v == self.space_index else self.int_to_char[v] for v in t)] for t in toks]
         return strings, [[o.to(torch.int)] for o in offs]
 
+    def stream(self, num_streams, device="cuda"):
+        """A GreedyStream: decode for num_streams streams that arrive chunk by chunk."""
+        return GreedyStream(self, num_streams, device)
+
+
+def _stream_sizes(sizes, N, Tc):
+    """the host ints of a feed's sizes (None = the whole chunk for every stream)"""
+    if sizes is None:
+        return [Tc] * N
+    sz = [int(v) for v in (sizes.tolist() if hasattr(sizes, "tolist") else sizes)]
+    if len(sz) != N or any(not 0 <= v <= Tc for v in sz):
+        raise ValueError("sizes must be %d ints in [0, %d] (the chunk's frames), got %s" % (N, Tc, sz))
+    return sz
+
+
+class GreedyStream:
+    """GreedyDecoder.decode on streams that arrive in chunks (ds2_greedy_stream_feed): the previous frame's arg-max and the frame
+    count of every stream stay on the device, so a repeated label or a run of blanks across a chunk boundary is collapsed as in the
+    whole utterance.  ``text[n]`` is the transcript so far, ``offsets[n]`` its frames, ``frames[n]`` the frames consumed."""
+
+    def __init__(self, decoder, num_streams, device="cuda"):
+        self.decoder, self.num_streams = decoder, int(num_streams)
+        self._carry = torch.zeros((self.num_streams, 2), dtype=torch.int32, device=device)
+        self.reset()
+
+    def reset(self, streams=None):
+        """Streams `streams` (None = all) start again."""
+        if streams is None:
+            self._carry.zero_()
+            self.text = [''] * self.num_streams
+            self.offsets = [torch.zeros(0, dtype=torch.int) for _ in range(self.num_streams)]
+            self.frames = [0] * self.num_streams
+        else:
+            for n in streams:
+                self._carry[n].zero_()
+                self.text[n], self.offsets[n], self.frames[n] = '', torch.zeros(0, dtype=torch.int), 0
+
+    def feed(self, probs, sizes=None):
+        """probs: (N, Tc, C) scores of the next chunk (device or host tensor); sizes: host ints per stream (None = Tc), 0 leaving a
+        stream as it is.  Returns (strings, offsets) of what the chunk adds: strings[n] a str, offsets[n] an int tensor of frames
+        counted from the start of the stream."""
+        d = self.decoder
+        if not probs.is_cuda:
+            probs = probs.to(self._carry.device)
+        sz = _stream_sizes(sizes, self.num_streams, probs.shape[1])
+        toks, offs = ops.greedy_stream_feed(probs, None if sizes is None else torch.tensor(sz, dtype=torch.int32), d.blank_index,
+                                            self._carry)
+        strings = [''.join(' ' if v == d.space_index else d.int_to_char[v] for v in t) for t in toks]
+        offs = [o.to(torch.int) for o in offs]
+        for n in range(self.num_streams):
+            self.text[n] += strings[n]
+            self.offsets[n] = torch.cat([self.offsets[n], offs[n]])
+            self.frames[n] += sz[n]
+        return strings, offs
+
 
 class BeamCTCDecoder:
     """CTC prefix beam search with the reference's interface (``deepspeech_pytorch.decoder.BeamCTCDecoder``, decoder.py:56-117),
@@ -145,6 +200,65 @@ class BeamCTCDecoder:
         strings[n] is a list of beam_width transcripts, offsets[n] the matching list of int tensors."""
         strings, offsets, _ = self.decode_beams(probs, sizes)
         return strings, offsets
+
+    def stream(self, num_streams, max_frames, device="cuda"):
+        """A BeamStream: this decoder's search for num_streams streams that arrive chunk by chunk, up to max_frames frames each
+        (the node pool costs 12 * beam_width bytes per frame and stream)."""
+        return BeamStream(self, num_streams, max_frames, device)
+
+
+class BeamStream:
+    """Resumable beam search (ds2_beam_stream_*): after any sequence of feeds, ``result()`` equals ``decode_beams`` on the frames
+    consumed so far, bit for bit.  The beam state and the node pool stay on the device; a feed does not wait for it (its host
+    sizes reach the device through pinned memory in a queued copy; a host ``probs`` is copied first, which does wait).
+    ``frames[n]`` counts the frames that stream n has consumed."""
+
+    def __init__(self, decoder, num_streams, max_frames, device="cuda"):
+        d = self.decoder = decoder
+        self.num_streams, self.max_frames = int(num_streams), int(max_frames)
+        dev = torch.empty(0, device=device).device
+        lm = None
+        if d.lm is not None:
+            wt, gt = d._lm_tables(dev)
+            lm = dict(space=d.space_index, word_table=wt, ngram_table=gt, order=d.lm.order, bos=d.lm.bos, alpha=d.alpha,
+                      beta=d.beta, lexicon=d.lexicon)
+        self._h = ops.beam_stream_open(self.num_streams, self.max_frames, len(d.labels), d.blank_index, d.beam_width,
+                                       d.cutoff_top_n, d.cutoff_prob, dev, lm)
+        self.frames = [0] * self.num_streams
+
+    def feed(self, probs, sizes=None):
+        """probs: (N, Tc, C) probabilities of the next chunk (device or host tensor); sizes: host ints per stream (None = Tc), 0
+        leaving a stream as it is.  ValueError, before anything is launched, when a stream would pass max_frames."""
+        sz = _stream_sizes(sizes, self.num_streams, probs.shape[1])
+        for n, v in enumerate(sz):
+            if self.frames[n] + v > self.max_frames:
+                raise ValueError("stream %d: %d frames consumed + %d fed pass max_frames=%d"
+                                 % (n, self.frames[n], v, self.max_frames))
+        if not probs.is_cuda:
+            probs = probs.to(self._h.device)
+        ops.beam_stream_feed(self._h, probs, None if sizes is None else torch.tensor(sz, dtype=torch.int32))
+        self.frames = [f + v for f, v in zip(self.frames, sz)]
+
+    def _strings(self, res):
+        d = self.decoder
+        strings = [[''.join(d.int_to_char[v] for v in t) for t in beams] for beams in res[0]]
+        return strings, [[o.to(torch.int) for o in beams] for beams in res[1]], res[2]
+
+    def result(self):
+        """(strings, offsets, scores) in decode_beams' shapes, for the frames consumed so far; feeding can go on afterwards."""
+        return self._strings(ops.beam_stream_result(self._h, max(self.frames)))
+
+    def best(self):
+        """The top beam alone: (strings[n], offsets[n]) of every stream; only rank 0 travels to the host."""
+        strings, offsets, _ = self._strings(ops.beam_stream_result(self._h, max(self.frames), top_only=True))
+        return [s[0] for s in strings], [o[0] for o in offsets]
+
+    def reset(self, streams=None):
+        """Streams `streams` (None = all) start again from the empty beam."""
+        streams = list(range(self.num_streams)) if streams is None else [int(n) for n in streams]
+        ops.beam_stream_reset(self._h, streams)
+        for n in streams:
+            self.frames[n] = 0
 
 
 def _edit_distance(a, b):

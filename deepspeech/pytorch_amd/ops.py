@@ -868,16 +868,7 @@ def beam_decode(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob):
     of beam b, best first), offsets[n][b] (int tensor of their frames) and a host (N, B) float tensor of scores (-log p, ctcdecode's
     convention; +inf where fewer than B beams are alive).  Only the surviving labels, their frames and the scores travel."""
     N, T, Cc = probs.shape
-    B, top_n = int(beam_width), int(cutoff_top_n)
-    if not 1 <= B <= BEAM_MAX_WIDTH:
-        raise ValueError("beam_width must be in [1, %d], got %d" % (BEAM_MAX_WIDTH, B))
-    if top_n < 1 or min(top_n, Cc) > BEAM_MAX_TOP_N:
-        raise ValueError("min(cutoff_top_n, number of classes) must be in [1, %d], got cutoff_top_n=%d with %d classes"
-                         % (BEAM_MAX_TOP_N, top_n, Cc))
-    if not 1 <= Cc <= BEAM_MAX_CLASSES:
-        raise ValueError("the beam decoder supports up to %d classes, got %d" % (BEAM_MAX_CLASSES, Cc))
-    if not 0 <= blank < Cc:
-        raise ValueError("blank index %d out of range for %d classes" % (blank, Cc))
+    B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
     if N == 0 or T == 0:             # no frames: the only beam is the empty string, score 0
         scores = torch.full((N, B), float("inf"))
         scores[:, 0] = 0.0
@@ -943,17 +934,13 @@ def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, s
 
 def _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos):
     """The argument checks of beam_decode_lm, for its grid form; returns (B, top_n)."""
-    N, T, Cc = probs.shape
-    B, top_n = int(beam_width), int(cutoff_top_n)
-    if not 1 <= B <= BEAM_MAX_WIDTH:
-        raise ValueError("beam_width must be in [1, %d], got %d" % (BEAM_MAX_WIDTH, B))
-    if top_n < 1 or min(top_n, Cc) > BEAM_MAX_TOP_N:
-        raise ValueError("min(cutoff_top_n, number of classes) must be in [1, %d], got cutoff_top_n=%d with %d classes"
-                         % (BEAM_MAX_TOP_N, top_n, Cc))
-    if not 1 <= Cc <= BEAM_MAX_CLASSES:
-        raise ValueError("the beam decoder supports up to %d classes, got %d" % (BEAM_MAX_CLASSES, Cc))
-    if not 0 <= blank < Cc:
-        raise ValueError("blank index %d out of range for %d classes" % (blank, Cc))
+    return _beam_lm_checks_for(probs.shape[2], probs.device, beam_width, cutoff_top_n, blank, space, word_table, ngram_table,
+                               order, bos)
+
+
+def _beam_lm_checks_for(Cc, device, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos):
+    """_beam_lm_checks for Cc classes on `device`, which is all that it looks at of the probabilities (beam_stream_open has none)"""
+    B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
     if not 0 <= space < Cc or space == blank:
         raise ValueError("space label %d must be one of the %d classes and differ from the blank (%d)" % (space, Cc, blank))
     if not 1 <= int(order) <= BEAM_LM_MAX_ORDER:
@@ -965,8 +952,8 @@ def _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, n
             raise ValueError("%s must be a contiguous int64 tensor of shape (slots, 2)" % name)
         if t.shape[0] < 2 or t.shape[0] & (t.shape[0] - 1):
             raise ValueError("%s: the number of slots must be a power of two >= 2, got %d" % (name, t.shape[0]))
-        if t.device != probs.device or not t.is_cuda:
-            raise ValueError("%s must live on the device of the probabilities (%s), not %s" % (name, probs.device, t.device))
+        if t.device != device or not t.is_cuda:
+            raise ValueError("%s must live on the device of the probabilities (%s), not %s" % (name, device, t.device))
     return B, top_n
 
 
@@ -1029,6 +1016,184 @@ def beam_decode_lm_grid(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_pr
              int(bos), int(bool(lexicon)), cnt, P(al[g0:g1]), P(be[g0:g1]), P(buf[0, g0:g1]), P(buf[1, g0:g1]), P(lens[g0:g1]),
              P(scores[0, g0:g1]), P(scores[1, g0:g1]), P(ws), S())
     return buf[0], buf[1], lens, scores[0], scores[1]
+
+
+class BeamStreamHandle:
+    """The device state of N resumable beam searches (ds2_beam_stream_*): one buffer with every stream's beam state and node pool,
+    and the session's settings.  Made by beam_stream_open."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def beam_stream_open(num_streams, max_frames, num_classes, blank, beam_width, cutoff_top_n, cutoff_prob, device="cuda", lm=None):
+    """Opens N = num_streams resumable CTC prefix beam searches of up to max_frames frames each.  lm: None, or the dict of
+    beam_decode_lm's language-model arguments (space, word_table, ngram_table, order, bos, alpha, beta, lexicon).  The checks and
+    messages are beam_decode's / beam_decode_lm's.  The handle owns ds2_beam_stream_bytes(...) bytes of device memory: the
+    states and the node pool, 12 * beam_width bytes per frame and stream.  Every stream starts fresh."""
+    N, F, Cc = int(num_streams), int(max_frames), int(num_classes)
+    dev = torch.device(device)
+    if N < 1 or F < 1:
+        raise ValueError("a beam stream needs num_streams >= 1 and max_frames >= 1, got %d and %d" % (N, F))
+    if dev.type != "cuda":
+        raise ValueError("a beam stream lives on a HIP device, not on %s" % dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if lm is None:
+        B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
+    else:
+        B, top_n = _beam_lm_checks_for(Cc, dev, beam_width, cutoff_top_n, blank, lm["space"], lm["word_table"], lm["ngram_table"],
+                                       lm["order"], lm["bos"])
+        lm = dict(lm, space=int(lm["space"]), order=int(lm["order"]), bos=int(lm["bos"]), alpha=float(lm["alpha"]),
+                  beta=float(lm["beta"]), lexicon=bool(lm.get("lexicon", True)))
+    if (F + 1) * B > 2 ** 31 - 1:
+        raise ValueError("max_frames=%d with beam_width=%d passes the node pool's 2^31 - 1 slots per stream" % (F, B))
+    state = torch.empty(query("ds2_beam_stream_bytes", N, B, F, int(lm is not None)), dtype=torch.uint8, device=dev)
+    # state_stride: bytes between two streams' states at the front of the buffer; the node pool follows them
+    h = BeamStreamHandle(state=state, N=N, B=B, max_frames=F, C=Cc, blank=int(blank), top_n=top_n, cutoff_prob=float(cutoff_prob),
+                         lm=lm, device=dev, state_stride=query("ds2_beam_stream_state_stride", B, int(lm is not None)))
+    beam_stream_reset(h)
+    return h
+
+
+def _beam_checks(Cc, beam_width, cutoff_top_n, blank):
+    """The argument checks that every beam search shares (beam_decode, _beam_lm_checks, beam_stream_open); returns (B, top_n)."""
+    B, top_n = int(beam_width), int(cutoff_top_n)
+    if not 1 <= B <= BEAM_MAX_WIDTH:
+        raise ValueError("beam_width must be in [1, %d], got %d" % (BEAM_MAX_WIDTH, B))
+    if top_n < 1 or min(top_n, Cc) > BEAM_MAX_TOP_N:
+        raise ValueError("min(cutoff_top_n, number of classes) must be in [1, %d], got cutoff_top_n=%d with %d classes"
+                         % (BEAM_MAX_TOP_N, top_n, Cc))
+    if not 1 <= Cc <= BEAM_MAX_CLASSES:
+        raise ValueError("the beam decoder supports up to %d classes, got %d" % (BEAM_MAX_CLASSES, Cc))
+    if not 0 <= blank < Cc:
+        raise ValueError("blank index %d out of range for %d classes" % (blank, Cc))
+    return B, top_n
+
+
+def beam_stream_reset(h, streams=None):
+    """Streams `streams` (indices; None = all) start again from the empty beam; the others are untouched."""
+    mask = None
+    if streams is not None:
+        m = torch.zeros(h.N, dtype=torch.int32)
+        for n in streams:
+            if not 0 <= int(n) < h.N:
+                raise ValueError("stream index %d out of range for %d streams" % (int(n), h.N))
+            m[int(n)] = 1
+        mask = m.to(h.device)
+    call("ds2_beam_stream_reset", P(h.state), h.N, h.B, h.max_frames, int(h.lm is not None), P(mask), S())
+
+
+def _beam_stream_call(h, probs, Tc, sz, row_stride, top_only=False):
+    """one ds2_beam_stream_feed(_lm) call: a chunk (or none, Tc == 0), with the output stage when row_stride is given; the device
+    writes, and the call allocates and copies, R = 1 rank with top_only and all B otherwise"""
+    dev, N, B = h.device, h.N, h.B
+    R = 1 if top_only else B
+    buf = lens = scores = None
+    if row_stride is not None:
+        row_stride = max(int(row_stride), 1)
+        buf = torch.empty((2, N, R, row_stride), dtype=torch.int32, device=dev)
+        lens = torch.empty((N, R), dtype=torch.int32, device=dev)
+        scores = torch.empty((2, N, R), dtype=torch.float32, device=dev)
+    ws = torch.empty(query("ds2_beam_stream_ws_bytes", N, Tc), dtype=torch.uint8, device=dev) if Tc > 0 else None
+    x = (P(probs), probs.stride(0), probs.stride(1)) if Tc > 0 else (P(None), 0, 0)
+    out = (P(buf[0]), P(buf[1]), row_stride, R, P(lens), P(scores[0])) if buf is not None else \
+        (P(None), P(None), 0, 0, P(None), P(None))
+    if h.lm is None:
+        call("ds2_beam_stream_feed", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, P(h.state), h.max_frames, *out,
+             P(ws), S())
+    else:
+        L = h.lm
+        call("ds2_beam_stream_feed_lm", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, L["space"], P(L["word_table"]),
+             L["word_table"].shape[0], P(L["ngram_table"]), L["ngram_table"].shape[0], L["order"], L["bos"], L["alpha"], L["beta"],
+             int(L["lexicon"]), P(h.state), h.max_frames, *out, P(scores[1]) if buf is not None else P(None), P(ws), S())
+    if buf is None:
+        return None
+    ln = lens.cpu().numpy()
+    width = min(max(int(ln.max()), 1), row_stride)
+    host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
+    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(R)] for n in range(N)]
+    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(R)] for n in range(N)]
+    sc = scores.cpu()
+    return (toks, offs, sc[0]) if h.lm is None else (toks, offs, sc[0], sc[1])
+
+
+def _sizes_to_device(sizes, dev):
+    """a feed's sizes as an int32 tensor on dev (None stays None); host values go through pinned memory, so the copy is queued on
+    the stream and the host does not wait for it"""
+    if sizes is None:
+        return None
+    sz = torch.as_tensor(sizes)
+    if sz.is_cuda:
+        return sz.to(dev, torch.int32)
+    return sz.to(torch.int32).pin_memory().to(dev, non_blocking=True)
+
+
+def beam_stream_feed(h, probs, sizes=None, row_stride=None):
+    """Feeds one chunk to the streams of h.  probs: (N, Tc, C) CUDA tensor of probabilities (any strides with a contiguous class
+    dimension); sizes: [N] ints (tensor or sequence; None = Tc), the frames of the chunk that each stream takes, 0 leaving it as it
+    is.  The call does not wait for the device: host sizes travel through pinned memory in a copy queued on the stream,
+    and sizes that are already an int32 tensor on the stream's device are used as they are.  A stream that would pass max_frames takes nothing and has its overflow flag set
+    (beam_stream_header).  With row_stride (>= the largest consumed count) the same launch runs the output stage and the call
+    returns beam_stream_result's value; otherwise None."""
+    if not (torch.is_tensor(probs) and probs.dim() == 3 and probs.shape[0] == h.N and probs.shape[2] == h.C):
+        raise ValueError("a chunk for this stream has shape (%d, Tc, %d), got %s"
+                         % (h.N, h.C, tuple(probs.shape) if torch.is_tensor(probs) else type(probs).__name__))
+    Tc = probs.shape[1]
+    if Tc == 0:
+        return None if row_stride is None else beam_stream_result(h, row_stride)
+    if probs.dtype != torch.float32:
+        probs = probs.float()
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    sz = _sizes_to_device(sizes, h.device)
+    if sz is not None and sz.shape != (h.N,):
+        raise ValueError("sizes must have one entry per stream (%d), got shape %s" % (h.N, tuple(sz.shape)))
+    return _beam_stream_call(h, probs, Tc, sz, row_stride)
+
+
+def beam_stream_result(h, row_stride=None, top_only=False):
+    """The beams of every stream on the frames consumed so far: beam_decode's three values (with an LM beam_decode_lm's four, the
+    end-of-utterance bonus and re-rank included), equal bit for bit to the one-shot call on those frames.  The state is left
+    unchanged, so feeding goes on.  row_stride: an upper bound of the consumed counts (default max_frames), which sizes the device
+    rows; only the surviving labels travel.  With top_only the device writes rank 0 alone (rows of row_stride ints per stream,
+    not per beam) and every returned list has one entry per stream."""
+    return _beam_stream_call(h, None, 0, None, h.max_frames if row_stride is None else row_stride, top_only)
+
+
+def beam_stream_header(h):
+    """Host (N, 3) int32 tensor: per stream the frames consumed, the live beams and the overflow flag (waits for the device)."""
+    hdr = h.state[:h.state_stride * h.N].view(h.N, h.state_stride)[:, :16].contiguous().view(torch.int32)
+    return hdr[:, :3].cpu()
+
+
+def greedy_stream_feed(scores, sizes, blank, carry):
+    """greedy_decode on one chunk of N streams (ds2_greedy_stream_feed).  scores: (N, Tc, C) f32 CUDA tensor; sizes: [N] ints or
+    None (= Tc); carry: the (N, 2) int32 CUDA tensor that holds the streams' state between the calls, zeros for fresh streams
+    (updated in place).  Returns host lists: the labels that this chunk adds per stream and their frames counted from the start
+    of the stream; over all feeds they concatenate to greedy_decode's output on the concatenated input."""
+    N, T, Cc = scores.shape
+    if not (torch.is_tensor(carry) and carry.is_cuda and carry.dtype == torch.int32 and carry.shape == (N, 2)
+            and carry.is_contiguous()):
+        raise ValueError("carry must be a contiguous (%d, 2) int32 tensor on the device" % N)
+    if N == 0 or T == 0:
+        return [[] for _ in range(N)], [torch.zeros(0, dtype=torch.int32) for _ in range(N)]
+    if scores.dtype != torch.float32:
+        scores = scores.float()
+    if scores.stride(2) != 1:
+        scores = scores.contiguous()
+    dev = scores.device
+    sz = _sizes_to_device(sizes, dev)
+    buf = torch.empty((2, N, T), dtype=torch.int32, device=dev)
+    counts = torch.empty(N, dtype=torch.int32, device=dev)
+    call("ds2_greedy_stream_feed", P(scores), scores.stride(0), scores.stride(1), N, T, Cc, P(sz), blank, P(carry), P(buf[0]),
+         P(buf[1]), P(counts), S())
+    cnt = counts.cpu()
+    width = int(cnt.max().item())
+    host = buf[:, :, :max(width, 1)].cpu()           # only the surviving labels + offsets travel
+    toks = [host[0, i, :int(cnt[i])].tolist() for i in range(N)]
+    offs = [host[1, i, :int(cnt[i])] for i in range(N)]
+    return toks, offs
 
 
 ERROR_COUNTS_MAX_LEN = 4096      # ds2_error_counts: labels of one hypothesis or reference

@@ -381,6 +381,16 @@ int ds2_wave_mix(const float* wav, long ldw, const int* nsamples, int N, const f
 int ds2_greedy_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank,
                       int* tokens, int* offsets, int* counts, ds2_stream_t stream);
 
+/* ds2_greedy_decode on one chunk (N, Tc, C) of N streams.  carry: [N][2] int32 on the device, per stream (arg-max of its last
+ * frame, frames consumed); all zero for a fresh stream, updated by the call.  sizes[n] == 0 leaves stream n as it is.
+ * tokens / offsets [N][Tc]: the counts[n] labels that this chunk adds to stream n and their frames counted from the start of the
+ * stream.  Greedy output is append-only: the chunks' outputs, concatenated, are ds2_greedy_decode's on the concatenated input.
+ * Tc >= 1: there is no output stage to run on its own, so unlike ds2_beam_stream_feed an empty chunk is DS2_ERR_ARG (the
+ * wrappers return before the call).  The consumed-frame counter is an int32 that nothing bounds: a stream must be reset before
+ * it has taken 2^31 - 1 frames. */
+int ds2_greedy_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank,
+                           int* carry, int* tokens, int* offsets, int* counts, ds2_stream_t stream);
+
 /* ---- CTC prefix beam search on the device (BeamCTCDecoder, reference decoder.py:56-117) ---------------
  * x[n*stride_n + t*stride_t + c] f32 probabilities, C <= 8192; sizes [N] int32 on the device (null = T); 1 <= B <= 256,
  * cutoff_top_n >= 1 with min(cutoff_top_n, C) <= 64; cutoff_prob < 1 also cuts each frame at that cumulative probability.
@@ -419,6 +429,43 @@ int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N,
                             const void* ngram_table, long ngram_slots, int order, int bos, int lexicon, int G, const float* alphas,
                             const float* betas, int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws,
                             ds2_stream_t stream);
+
+/* ---- resumable CTC prefix beam search: N streams fed chunk by chunk (DESIGN.md "ds2_beam_stream") --------------------------
+ * After feeds that delivered frames [0, t_n) of stream n, the output stage gives what ds2_beam_decode / ds2_beam_decode_lm give on
+ * those t_n frames, bit for bit (labels, frames, lengths, scores, acoustic scores).
+ * state: one device buffer per session of ds2_beam_stream_bytes(N, B, max_frames, lm) bytes, 256-byte aligned (host-only size
+ *   query; 0 for N, B or max_frames <= 0; lm != 0 adds the language-model fields).  It holds per stream a header of four int32
+ *   (frames consumed, live beams, overflow flag, unused) and the beams' fields as arrays of B entries, at a 256-byte aligned
+ *   stride of 16 + 32 * B (+ 36 * B with an LM) bytes, which ds2_beam_stream_state_stride(B, lm) returns (host-only; 0 for
+ *   B <= 0), then the node pool [N][max_frames + 1][B] x (parent, label, frame) int32:
+ *   12 * B bytes per frame and stream.  N, B, max_frames, lm, blank, the cutoffs and the LM arguments are the session's: the same
+ *   in every call on one buffer.
+ * ds2_beam_stream_reset: the streams with mask[n] != 0 (mask [N] int32 on the device, null = all) start again from the empty
+ *   beam; the others are untouched.  A new buffer is reset as a whole before its first feed.
+ * ds2_beam_stream_feed: x is the chunk (N, Tc, C) with ds2_beam_decode's strides and limits; sizes [N] int32 on the device
+ *   (null = Tc) says how many of its frames each stream takes, 0 leaving the stream as it is.  A stream whose consumed count would
+ *   pass max_frames takes nothing and has its overflow flag set (until it is reset); the pool is never written beyond.
+ *   tokens / offsets / lens / scores are all null (no output stage) or all given: then the best out_ranks beams of every stream
+ *   are written, 1 <= out_ranks <= B: rows (n, b), b < out_ranks, of tokens / offsets lie row_stride ints apart, row_stride >=
+ *   the largest consumed count (labels past a shorter row are not written); lens / scores [N][out_ranks].  The output stage
+ *   reads the state and leaves it unchanged.  Tc == 0 runs the output stage alone (x, sizes, ws unused).
+ *   ws: ds2_beam_stream_ws_bytes(N, Tc) bytes (the chunk's kept lists), 256-byte aligned; needed during the call only.
+ * ds2_beam_stream_feed_lm: the same with the language model of ds2_beam_decode_lm; the output stage includes the end-of-utterance
+ *   bonus and re-rank, which always look at all the live beams; acoustic [N][out_ranks] may be null.
+ *   The consumed count never passes max_frames, so it needs no bound of its own.
+ * DS2_ERR_ARG: as ds2_beam_decode(_lm); outputs given in part, or out_ranks outside [1, B] with them; Tc == 0 without outputs; (max_frames + 1) * B > 2^31 - 1. */
+long ds2_beam_stream_bytes(int N, int B, int max_frames, int lm);
+long ds2_beam_stream_ws_bytes(int N, int Tc);
+long ds2_beam_stream_state_stride(int B, int lm);
+int ds2_beam_stream_reset(void* state, int N, int B, int max_frames, int lm, const int* mask, ds2_stream_t stream);
+int ds2_beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                         int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets,
+                         long row_stride, int out_ranks, int* lens, float* scores, void* ws, ds2_stream_t stream);
+int ds2_beam_stream_feed_lm(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                            int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                            const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
+                            void* state, int max_frames, int* tokens, int* offsets, long row_stride, int out_ranks, int* lens,
+                            float* scores, float* acoustic, void* ws, ds2_stream_t stream);
 
 /* ---- character / word error counts on the device (the edit distances of validation.py:66-132, decoder.CharErrorRate /
  * WordErrorRate) ----

@@ -14,6 +14,14 @@ label's logit is raised (--space-boost) in both the plain and the LM run.
 With --grid the weight search is timed at G points: one ops.beam_decode_lm_grid call plus ops.error_counts ("grid"), against G
 sequential ops.beam_decode_lm calls, each followed by the host metrics on the best transcripts ("loop", the path without the grid
 entry).  Both are reported as the whole call and as its device kernels alone (the raw entries on a preallocated workspace).
+
+    python tools/bench_beam.py --stream 100 [--lm tests/golden/lm/toy3.arpa] [--widths 10,128]
+
+With --stream the resumable search (ops.beam_stream_*) is timed per width on the same input cut into chunks of that many frames:
+the one-shot call, the sum of the chunked feeds with one result fetch at the end, a single feed without and with the result fetch,
+and the first feed of a stream against the feed of its last CHUNK_FRAMES frames: the same chunk length, so the two differ only
+in the frames already consumed (the state is put back before every repetition, outside the timed interval).  The last of the
+chunked feeds is shorter where CHUNK_FRAMES does not divide T'; it is not the "last feed" that is timed on its own.
 """
 import argparse
 import json
@@ -30,12 +38,17 @@ import torch  # noqa: E402
 from deepspeech.pytorch_amd import ops  # noqa: E402
 
 
-def timed(fn, runs, warmup=3):
+def timed(fn, runs, warmup=3, prep=None):
+    """median, min and max of fn's time over runs calls after warm-up; prep() runs before every call, outside the timed interval"""
     for _ in range(warmup):
+        if prep:
+            prep()
         fn()
     torch.cuda.synchronize()
     ms = []
     for _ in range(runs):
+        if prep:
+            prep()
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
         fn()
@@ -43,6 +56,43 @@ def timed(fn, runs, warmup=3):
         b.synchronize()
         ms.append(a.elapsed_time(b))
     return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
+
+
+def stream_rows(a, probs, lm, oneshot):
+    """the resumable search against the one-shot call oneshot(B), per width; lm: None or ops.beam_stream_open's dict"""
+    N, T, C = probs.shape
+    Tc = a.stream
+    assert 1 <= Tc <= T
+    chunks = [probs[:, i:i + Tc] for i in range(0, T, Tc)]
+    rows = []
+    for B in [int(w) for w in a.widths.split(",")]:
+        h = ops.beam_stream_open(N, T, C, 0, B, a.top_n, 1.0, "cuda", lm)
+        states = h.state[:h.N * h.state_stride]          # what a feed reads and writes besides the pool slots of its own frames
+
+        def chunked():
+            ops.beam_stream_reset(h)
+            for c in chunks:
+                ops.beam_stream_feed(h, c)
+            return ops.beam_stream_result(h, T)
+
+        ops.beam_stream_reset(h)
+        for i in range(0, T - Tc, Tc):                   # everything but the last Tc frames (the last of these feeds may overlap
+            c = probs[:, i:min(i + Tc, T - Tc)]          # nothing: it is cut at T - Tc)
+            ops.beam_stream_feed(h, c)
+        late = states.clone()
+        fresh = lambda: ops.beam_stream_reset(h)
+        resume = lambda: states.copy_(late)
+        row = dict(decoder="stream+lm" if lm else "stream", B=B, chunk=Tc, feeds=len(chunks))
+        row["oneshot_ms"], row["oneshot_min"], row["oneshot_max"] = timed(lambda: oneshot(B), a.runs)
+        row["chunked_ms"], row["chunked_min"], row["chunked_max"] = timed(chunked, a.runs)
+        row["feed_ms"], row["feed_min"], row["feed_max"] = timed(lambda: ops.beam_stream_feed(h, chunks[0]), a.runs, prep=fresh)
+        row["feed_result_ms"], row["feed_result_min"], row["feed_result_max"] = \
+            timed(lambda: ops.beam_stream_feed(h, chunks[0], row_stride=Tc), a.runs, prep=fresh)
+        row["first_ms"], row["first_min"], row["first_max"] = row["feed_ms"], row["feed_min"], row["feed_max"]
+        row["last_ms"], row["last_min"], row["last_max"] = \
+            timed(lambda: ops.beam_stream_feed(h, probs[:, T - Tc:]), a.runs, prep=resume)
+        rows.append(row)
+    return rows
 
 
 def grid_rows(a, probs, sizes, wt, gt, model, C):
@@ -124,6 +174,7 @@ def main():
     ap.add_argument("--open", action="store_true", help="open mode (lexicon=False)")
     ap.add_argument("--space-boost", type=float, default=0.0)
     ap.add_argument("--grid", default=None, help="with --lm: numbers of (alpha, beta) points, e.g. 1,8,64")
+    ap.add_argument("--stream", type=int, default=None, metavar="CHUNK_FRAMES", help="also time the resumable search in chunks")
     a = ap.parse_args()
     assert a.runs >= 10
     assert torch.cuda.is_available(), "bench_beam needs a HIP device"
@@ -163,9 +214,24 @@ def main():
             rows.append(dict(decoder="beam+lm", B=B, ms_per_batch=med, min_ms=lo, max_ms=hi, us_per_step=1e3 * med / T))
     if a.lm and a.grid:
         rows += grid_rows(a, probs, sizes, wt, gt, model, C)
+    if a.stream:
+        rows += stream_rows(a, probs, None, lambda B: ops.beam_decode(probs, sizes, 0, B, a.top_n, 1.0))
+        if a.lm:
+            lm_args = dict(space=C - 1, word_table=wt, ngram_table=gt, order=model.order, bos=model.bos, alpha=a.alpha, beta=a.beta,
+                           lexicon=not a.open)
+            rows += stream_rows(a, probs, lm_args,
+                                lambda B: ops.beam_decode_lm(probs, sizes, 0, B, a.top_n, 1.0, C - 1, wt, gt, model.order, model.bos,
+                                                             a.alpha, a.beta, not a.open))
     lines = notes + ["# tools/bench_beam.py: N=%d T'=%d C=%d cutoff_top_n=%d softmax(normal * %.1f), median of %d calls after warm-up, %s"
              % (N, T, C, a.top_n, a.scale, a.runs, torch.cuda.get_device_name(0))]
     for r in rows:
+        if r["decoder"].startswith("stream"):
+            lines.append("%-9s B=%-4d chunk=%-4d one-shot %8.3f ms (min %.3f, max %.3f) | %d feeds + result %8.3f ms (min %.3f, max %.3f) | "
+                         "feed of frames 0..chunk %.3f ms, the same + result %.3f ms | feed of the first chunk frames %.3f ms (min %.3f, "
+                         "max %.3f), of the last chunk frames (T'-chunk..T') %.3f ms (min %.3f, max %.3f)" % (r["decoder"], r["B"], r["chunk"], r["oneshot_ms"], r["oneshot_min"], r["oneshot_max"], r["feeds"],
+                                        r["chunked_ms"], r["chunked_min"], r["chunked_max"], r["feed_ms"], r["feed_result_ms"],
+                                        r["first_ms"], r["first_min"], r["first_max"], r["last_ms"], r["last_min"], r["last_max"]))
+            continue
         if r["decoder"] in ("grid", "loop"):
             lines.append("%-7s B=%-4d G=%-3d %10.3f ms/call (min %.3f, max %.3f)  kernels %10.3f ms  %8.3f ms/point" %
                          (r["decoder"], r["B"], r["G"], r["ms_per_call"], r["min_ms"], r["max_ms"], r["kernel_ms"], r["ms_per_point"]))
