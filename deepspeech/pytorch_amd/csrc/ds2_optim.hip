@@ -356,6 +356,102 @@ __global__ void __launch_bounds__(256) k_opt_matrix_perm(float* __restrict__ p, 
   o[1] = make_uint4(w[4], w[5], w[6], w[7]);
 }
 
+// Row-block form of the permuted update: a workgroup owns PR_ROWS rows x cw of the perm_c channels, i.e. the source columns
+// [c0 * perm_f, (c0 + cw) * perm_f) -- one contiguous fp32 stream per row (16-byte accesses, a thread holds 4 rows x 4 columns of p, g,
+// m, v as above) -- and the output columns f * perm_c + c0 .. + cw of every f.  The bf16 side leaves in full runs too: every updated
+// value is dropped into an LDS image of the workgroup's OUTPUT columns ([PR_ROWS][perm_f][cw] bf16, 2-byte LDS writes), which is then
+// written to dst in 16-byte pieces (runs of cw elements per row and f) and to dstT as one 32-byte run of PR_ROWS rows per output
+// column.  k_opt_matrix_perm above scatters the bf16 copy with 2-byte global stores 64 bytes apart -- that, not the 28 B/element of
+// fp32 traffic, held it at half the rate of k_opt_matrix4_multi.  The arithmetic per element is the same, so are the bits.
+// cw % 8 == 0, (cw * perm_f) % 8 == 0, R % PR_ROWS == 0, PR_ROWS * cw * perm_f * 2 bytes of dynamic LDS.
+constexpr int PR_ROWS = 16;
+__global__ void __launch_bounds__(256) k_opt_matrix_perm_rows(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                              float* __restrict__ v, int C, int perm_c, int perm_f, int cw, int Cout,
+                                                              uint16_t* __restrict__ dst, long ldd, uint16_t* __restrict__ dstT,
+                                                              long lddT, Hyper h) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char pr_smem[];
+  uint16_t* img = reinterpret_cast<uint16_t*>(pr_smem);
+  const int tid = threadIdx.x, r0 = blockIdx.x * PR_ROWS, c0 = blockIdx.y * cw;
+  const int WL = cw * perm_f, nq = WL / 4;       // the workgroup's columns, their float4 quads
+  const float cs = h.clip ? h.clip[1] : 1.f;
+  for (int idx = tid; idx < (PR_ROWS / 4) * nq; idx += 256) {
+    const int rg = idx / nq, s0 = (idx - rg * nq) * 4;              // s0: source column relative to c0 * perm_f
+    float4 pv[4], gv[4], mv[4], vv[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const long o = (long)(r0 + rg * 4 + i) * C + c0 * perm_f + s0;
+      pv[i] = *reinterpret_cast<const float4*>(p + o);
+      gv[i] = *reinterpret_cast<const float4*>(g + o);
+      mv[i] = *reinterpret_cast<const float4*>(m + o);
+      vv[i] = h.mode == 0 ? *reinterpret_cast<const float4*>(v + o) : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    int jl[4];                                    // image column of source column c * perm_f + f: f * cw + (c - c0)
+    {
+      int c = s0 / perm_f, f = s0 - c * perm_f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        jl[e] = f * cw + c;
+        if (++f == perm_f) {
+          f = 0;
+          ++c;
+        }
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      float* pe = reinterpret_cast<float*>(&pv[i]);
+      float* ge = reinterpret_cast<float*>(&gv[i]);
+      float* me = reinterpret_cast<float*>(&mv[i]);
+      float* ve = reinterpret_cast<float*>(&vv[i]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        update(h, cs, pe[e], ge[e], me[e], ve[e]);
+        img[(rg * 4 + i) * WL + jl[e]] = (uint16_t)cvt_pk_bf16(pe[e], 0.f);
+      }
+      const long o = (long)(r0 + rg * 4 + i) * C + c0 * perm_f + s0;
+      *reinterpret_cast<float4*>(p + o) = pv[i];
+      *reinterpret_cast<float4*>(m + o) = mv[i];
+      if (h.mode == 0) *reinterpret_cast<float4*>(v + o) = vv[i];
+    }
+  }
+  // zero pad columns [C, Cout) of this row block (done by the first channel block)
+  if (blockIdx.y == 0 && Cout > C) {
+    const int npad = Cout - C;
+    for (int e = tid; e < PR_ROWS * npad; e += 256) {
+      const int r = r0 + e / npad, j = C + e % npad;
+      if (dst != nullptr) dst[(long)r * ldd + j] = 0;
+      if (dstT != nullptr) dstT[(long)j * lddT + r] = 0;
+    }
+  }
+  __syncthreads();
+  if (dst != nullptr) {
+    const int np = WL / 8, hp = cw / 8;           // 16-byte pieces per image row, per run
+    for (int idx = tid; idx < PR_ROWS * np; idx += 256) {
+      const int row = idx / np, k = idx - row * np, f = k / hp, part = k - f * hp;
+      *reinterpret_cast<uint4*>(dst + (long)(r0 + row) * ldd + f * perm_c + c0 + part * 8) =
+          *reinterpret_cast<const uint4*>(img + row * WL + k * 8);
+    }
+  }
+  if (dstT != nullptr) {
+    for (int j = tid; j < WL; j += 256) {
+      const int f = j / cw, jo = f * perm_c + c0 + (j - f * cw);
+      uint32_t w[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) w[k] = (uint32_t)img[(2 * k) * WL + j] | ((uint32_t)img[(2 * k + 1) * WL + j] << 16);
+      uint4* o = reinterpret_cast<uint4*>(dstT + (long)jo * lddT + r0);
+      o[0] = make_uint4(w[0], w[1], w[2], w[3]);
+      o[1] = make_uint4(w[4], w[5], w[6], w[7]);
+    }
+  }
+}
+// channels per workgroup of k_opt_matrix_perm_rows: half of them when that keeps every access whole, else all; 0: the shape is not taken
+inline int perm_rows_cw(int C, int perm_c, int perm_f) {
+  if (perm_c <= 0 || perm_c % 8 != 0 || C % 8 != 0) return 0;
+  const int half = perm_c / 2;
+  return (half % 8 == 0 && (half * perm_f) % 8 == 0) ? half : perm_c;
+}
+constexpr int PR_MAX_LDS = 64 * 1024;
+
 Hyper make_hyper(int mode, const float* hp, int first, const float* clip) {
   Hyper h{};
   h.mode = mode;
@@ -492,6 +588,13 @@ int ds2_opt_matrix(int mode, float* p, const float* g, float* m, float* v, int R
   if (vec)
     hipLaunchKernelGGL(k_opt_matrix4, dim3(ds2_cdiv(C, 64), ds2_cdiv(R, 64)), dim3(256), 0, st, p, g, m, v, R, C, (uint16_t*)dst, ldd,
                        (uint16_t*)dstT, lddT, h);
+  else if (perm_rows_cw(C, perm_c, perm_f) > 0 && PR_ROWS * perm_rows_cw(C, perm_c, perm_f) * perm_f * 2 <= PR_MAX_LDS &&
+           (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)(mode == 0 ? v : p)) & 15) == 0 &&
+           (dst == nullptr || (ldd % 8 == 0 && (((uintptr_t)dst) & 15) == 0))) {
+    const int cw = perm_rows_cw(C, perm_c, perm_f);
+    hipLaunchKernelGGL(k_opt_matrix_perm_rows, dim3(R / PR_ROWS, perm_c / cw), dim3(256), PR_ROWS * cw * perm_f * 2, st, p, g, m, v, C,
+                       perm_c, perm_f, cw, Cout, (uint16_t*)dst, ldd, (uint16_t*)dstT, lddT, h);
+  }
   else if (perm_c > 0 && C % 4 == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)(mode == 0 ? v : p)) & 15) == 0)
     hipLaunchKernelGGL(k_opt_matrix_perm, dim3(ds2_cdiv(C, 64), ds2_cdiv(R, 64)), dim3(256), 0, st, p, g, m, v, R, C, perm_c, perm_f,
                        Cout, (uint16_t*)dst, ldd, (uint16_t*)dstT, lddT, h);

@@ -576,8 +576,18 @@ __global__ void __launch_bounds__(256) k_rnn_bias_grads(const float* __restrict_
   if (i >= D * per_d) return;
   const int d = (int)(i / per_d), c = (int)(i % per_d), plane = c / H, u = c % H;
   const float* p = bacc + (long)d * N * per_d + c;
+  // the N loads are cold and a strided walk apart: eight are issued together, then added in sample order (n = 0 .. N-1, the order
+  // of the plain loop, so the sums keep their bits)
   float s = 0.f;
-  for (int n = 0; n < N; ++n) s += p[(long)n * per_d];
+  int n = 0;
+  for (; n + 8 <= N; n += 8) {
+    float x[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) x[k] = p[(long)(n + k) * per_d];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) s += x[k];
+  }
+  for (; n < N; ++n) s += p[(long)n * per_d];
   const long gh = (long)G * H;
   if (plane < G) dbih[d * gh + (long)plane * H + u] = s;
   if (NB == G)

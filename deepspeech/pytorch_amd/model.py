@@ -950,6 +950,13 @@ class _LookaheadFn(torch.autograd.Function):
         return dx, dw[:Ht].reshape(Ht, 1, ctxlen).contiguous(), None, None
 
 
+def _head_weight(c, wfc, Cp, H, dtype):
+    """The head weight zero-padded to [Cp][H] in the operand type (cached until the parameter changes)."""
+    Cc, Ht = wfc.shape
+    return c.get(("wfc", dtype), [wfc], lambda: _pad_cols(torch.cat(
+        [wfc.detach(), torch.zeros(Cp - Cc, Ht, device=wfc.device)], 0), H).to(dtype).contiguous())
+
+
 class _HeadFn(torch.autograd.Function):
     """fc = SequenceWise(BatchNorm1d(H) -> Linear(H, C, bias=False)) (model.py:195-201).  Output: fp32 logits [T'*N][32]
     (C = 29 valid columns, the rest zero) -- the padded leading dimension is what the CTC kernel and the GEMMs want."""
@@ -963,9 +970,10 @@ class _HeadFn(torch.autograd.Function):
         c = mod._cache
         Xh = torch.empty_like(X)
         sv = _bn_seq_fwd(bn, bn_w, bn_b, X, Xh, R, Ht, H, training)
-        Wp = c.get(("wfc", dtype), [wfc], lambda: _pad_cols(torch.cat(
-            [wfc.detach(), torch.zeros(Cp - Cc, Ht, device=wfc.device)], 0), H).to(dtype).contiguous())      # [Cp][H]
-        logits = ops.gemm_nt(Xh, Wp, out_dtype=torch.float32)                                                # [R][Cp]
+        Wp = _head_weight(c, wfc, Cp, H, dtype)                                                              # [Cp][H]
+        # at most 64 padded classes in bf16: the output-layer kernels (one pass over Xh each way); else the generic products
+        ctx.fc = ops.fc_ok(dtype, H, Cp) and Xh.dtype == torch.bfloat16
+        logits = ops.fc_fwd(Xh, Wp, R, H) if ctx.fc else ops.gemm_nt(Xh, Wp, out_dtype=torch.float32)         # [R][Cp]
         ctx.mod, ctx.dims, ctx.sv = mod, (N, Tp, dtype, H, Cc, Ht, Cp), sv
         ctx.save_for_backward(X, Xh, wfc)
         return logits
@@ -976,12 +984,17 @@ class _HeadFn(torch.autograd.Function):
         N, Tp, dtype, H, Cc, Ht, Cp = ctx.dims
         R = Tp * N
         c = ctx.mod._cache
+        if ctx.fc:
+            dXh, dW = ops.fc_bwd(dlogits.contiguous(), Xh, _head_weight(c, wfc, Cp, H, dtype), R, H)
+            dX = torch.empty_like(dXh)
+            dg, db = _bn_seq_bwd(dXh, X, dX, ctx.sv, R, Ht, H)
+            return dX, dg, db, dW[:Cc, :Ht].contiguous(), None, None, None, None, None
         dl = dlogits.contiguous().to(dtype)                                                                  # [R][Cp]
         WpT = c.get(("wfcT", dtype), [wfc], lambda: _pad_cols(torch.cat(
             [wfc.detach(), torch.zeros(Cp - Cc, Ht, device=wfc.device)], 0), H).t().to(dtype).contiguous())  # [H][Cp]
         dXh = ops.gemm_nt(dl, WpT)                                                                           # [R][H]
         dl_T, Xh_T = ops.transpose(dl), ops.transpose(Xh)
-        dW = ops.gemm_nt_kslices(dl_T, Xh_T, max(1, min(32, R // 2048)))         # [Cp][H], the same in every run (no atomics)
+        dW = ops.gemm_nt_kslices(dl_T, Xh_T, ops.head_kslices(R))         # [Cp][H], the same in every run (no atomics)
         dX = torch.empty_like(dXh)
         dg, db = _bn_seq_bwd(dXh, X, dX, ctx.sv, R, Ht, H)
         return dX, dg, db, dW[:Cc, :Ht].contiguous(), None, None, None, None, None

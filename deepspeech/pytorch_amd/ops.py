@@ -166,6 +166,23 @@ def gemm_nt(A, B, bias=None, out_dtype=None, M=None, N=None, K=None, lda=None, l
     return out
 
 
+def kslice_plan(K, slices):
+    """(slices, Ks): how a contraction of length K is cut for gemm_nt_kslices -- the wanted slice count or the next smaller one (down
+    to half) that divides the 64-element tiles, slices of Ks = whole tiles each (+ a rest of K - slices * Ks).  The one place that
+    decides it: fc_bwd cuts its rows the same way, which is what keeps its dW bit for bit the K-sliced product's."""
+    nkt = K // 64
+    for s_ in range(slices, max(1, slices // 2), -1):   # a slice count that divides the 64-element tiles leaves no rest
+        if nkt % s_ == 0 and K % 64 == 0:
+            slices = s_
+            break
+    return slices, (K // max(slices, 1)) // 64 * 64
+
+
+def head_kslices(R):
+    """K-slices of the output layer's weight gradient over R rows (model._HeadFn, both of its paths)."""
+    return max(1, min(32, R // 2048))
+
+
 def gemm_nt_kslices(A, B, slices):
     """C[M][N] f32 = A[M][K] * B[N][K]^T (2-D row-major A, B) with the contraction cut into `slices` K-slices of equal length (whole
     64-element tiles) that run as the kernel's BATCH into a [slices (+1 for the rest of K)][M][N] scratch and are added in index order
@@ -173,12 +190,7 @@ def gemm_nt_kslices(A, B, slices):
     M, K = A.shape[-2], A.shape[-1]
     N = B.shape[-2]
     lda, ldb = A.stride(-2), B.stride(-2)
-    nkt = K // 64
-    for s_ in range(slices, max(1, slices // 2), -1):   # a slice count that divides the 64-element tiles leaves no rest
-        if nkt % s_ == 0 and K % 64 == 0:
-            slices = s_
-            break
-    Ks = (K // max(slices, 1)) // 64 * 64
+    slices, Ks = kslice_plan(K, slices)
     if slices <= 1 or Ks == 0 or (M * N) % 4 != 0:
         return gemm_nt(A, B, out_dtype=torch.float32)
     rest = K - slices * Ks
@@ -190,6 +202,45 @@ def gemm_nt_kslices(A, B, slices):
     out = torch.empty((M, N), dtype=torch.float32, device=A.device)
     call("ds2_sum_slices", P(ws), P(out), M * N, ws.shape[0], S())
     return out
+
+
+FC_CALLS = {"fwd": 0, "bwd": 0}     # launches of the output-layer kernels (tests assert that the model routes through them)
+
+
+def fc_ok(dtype, H, Cp):
+    """Shapes the output-layer kernels take: bf16 activations, 32 or 64 padded classes, H % 8 == 0 and a weight that fits their LDS."""
+    return dtype == torch.bfloat16 and bool(query("ds2_fc_supported", int(H), int(Cp)))
+
+
+def fc_fwd(Xh, Wp, R=None, H=None):
+    """logits [R][Cp] f32 = Xh[R][H] * Wp[Cp][H]^T (bf16 operands; Xh may carry a padded row stride) -- one pass over Xh."""
+    R = Xh.shape[0] if R is None else R
+    H = Wp.shape[1] if H is None else H
+    Cp = Wp.shape[0]
+    logits = torch.empty((R, Cp), dtype=torch.float32, device=Xh.device)
+    call("ds2_fc_fwd", P(Xh), Xh.stride(0), P(Wp), Wp.stride(0), P(logits), Cp, R, H, Cp, S())
+    FC_CALLS["fwd"] += 1
+    return logits
+
+
+def fc_bwd(dlogits, Xh, Wp, R=None, H=None):
+    """(dXh [R][H] bf16 = bf16(dlogits) * Wp, dW [Cp][H] f32 = bf16(dlogits)^T * Xh) from dlogits and Xh as stored: no cast pass, no
+    transposes.  dW's row blocks are the K-slices gemm_nt_kslices would cut (kslice_plan) and are added in index order (no atomics);
+    both results have the bits of gemm_nt(bf16(dlogits), Wp^T) and gemm_nt_kslices(dlogits^T, Xh^T, head_kslices(R))."""
+    R = Xh.shape[0] if R is None else R
+    H = Wp.shape[1] if H is None else H
+    Cp = Wp.shape[0]
+    dev = Xh.device
+    K = rup(R, 64)                       # the transposed operands' contraction length (ops.transpose pads the rows to whole tiles)
+    slices, Ks = kslice_plan(K, head_kslices(R))
+    block_rows = K if slices <= 1 or Ks == 0 else Ks
+    dXh = torch.empty((R, H), dtype=torch.bfloat16, device=dev)
+    dW = torch.empty((Cp, H), dtype=torch.float32, device=dev)
+    ws = torch.empty((query("ds2_fc_bwd_partials", R, block_rows), Cp, H), dtype=torch.float32, device=dev)
+    call("ds2_fc_bwd", PF(dlogits), dlogits.stride(0), P(Xh), Xh.stride(0), P(Wp), Wp.stride(0), P(dXh), H, P(dW), P(ws), R, H, Cp,
+         block_rows, S())
+    FC_CALLS["bwd"] += 1
+    return dXh, dW
 
 
 FP32_KSPLIT = __import__("os").environ.get("DS2_FP32_KSPLIT", "1") != "0"    # 0: every exact-fp32 product in one pass (round 5)

@@ -269,6 +269,23 @@ int ds2_lookahead_bwd(int dtype, const void* x, const float* w, const void* pre,
  * per-sample sums dBacc [D][N][NB*H] that ds2_rnn_persist_bwd accumulates (cell: 0 GRU, 1 LSTM, 2 tanh RNN). */
 int ds2_rnn_bias_grads(int cell, int D, int N, int H, const float* dBacc, float* dbih, float* dbhh, ds2_stream_t stream);
 
+/* ---- output layer for at most 64 padded classes (model.py:195-201, Linear(H, C, bias=False)) --------------------------------------
+ * Xh [R][ldx] bf16 (H columns used), Wp [Cp][ldw] bf16 = the head weight zero-padded to Cp = 32 or 64 classes, H % 8 == 0.  Both
+ * passes are bound by the activation matrix and move it once, in 16-byte pieces; products on the bf16 matrix pipe, fp32 accumulation
+ * in a fixed order (the same bits in every run).  ds2_fc_supported: 1 for the (H, Cp) these entries take (Wp must fit the forward's
+ * LDS image: Cp * H <= 64 Ki elements), else the caller keeps ds2_gemm_nt.
+ * fwd: logits [R][ldl] f32 = Xh * Wp^T.
+ * bwd: dXh [R][lddx] bf16 = bf16(dlogits) * Wp and dW [Cp][H] f32 = bf16(dlogits)^T * Xh from dlogits [R][ldg] f32 and Xh as stored
+ * (no cast pass, no transposes; Xh is read once): the fp32 partials of dW over row blocks of block_rows rows (a multiple of 32;
+ * ds2_fc_bwd_partials(R, block_rows) of them) go to ws (that many * Cp * H floats) and a last launch adds them in index order: no
+ * atomics.  The three products keep the 16-wide k-steps, their order and the operand slots of ds2_gemm_nt: with block_rows = the
+ * slice length of a K-sliced ds2_gemm_nt (+ ds2_sum_slices) over the same rows, the results have that path's bits. */
+int ds2_fc_supported(int H, int Cp);
+int ds2_fc_fwd(const void* Xh, long ldx, const void* Wp, long ldw, float* logits, long ldl, long R, int H, int Cp, ds2_stream_t stream);
+long ds2_fc_bwd_partials(long R, long block_rows);
+int ds2_fc_bwd(const float* dlogits, long ldg, const void* Xh, long ldx, const void* Wp, long ldw, void* dXh, long lddx, float* dW,
+               float* ws, long R, int H, int Cp, long block_rows, ds2_stream_t stream);
+
 /* probs = softmax(logits) row-wise (InferenceBatchSoftmax, model.py:72-77), f32 [rows][C] */
 int ds2_softmax_rows(const float* logits, float* probs, long rows, int C, long ld_in, long ld_out, ds2_stream_t stream);
 
