@@ -1365,6 +1365,76 @@ class DeepSpeech(_Base):
             out = ops.softmax_rows(logits, Cc).view(Tp, N, Cc).transpose(0, 1)   # model.py:238, 72-77
         return out, output_lengths, new_hs
 
+    # ---- exact chunked inference (streaming.StreamingTranscriber(carry_context=True)): eval mode, no autograd -------------------
+    def _stream_begin(self):
+        """What an eval-mode _logits does before its first kernel: weight layouts of a model that was trained since are stale."""
+        if self._weights_dirty:
+            self._cache.epoch += 1
+            self._weights_dirty = False
+        return self.compute_dtype()
+
+    def stream_front_weights(self, dtype):
+        """The conv front-end's operands for ops.stream_conv1 / stream_conv2: (w1k, b1, scale1, shift1, w2t, b2, scale2, shift2).
+        Eval BatchNorm2d folded to fp32 [32] vectors: scale = gamma * rsqrt(running_var + eps), shift = beta - running_mean * scale."""
+        sm, c = self.conv.seq_module, self._cache
+        self._prep_small_weights(dtype)
+        w1k = c.get("w1k", [sm[0].weight], lambda: sm[0].weight.detach().reshape(32, 451).t().contiguous())
+        w2t = c.get(("w2t", dtype), [sm[3].weight], lambda: sm[3].weight.detach().permute(2, 3, 0, 1).contiguous().to(dtype))
+
+        def fold(bn):
+            scale = bn.weight.detach().float() * torch.rsqrt(bn.running_var.float() + bn.eps)
+            return scale.contiguous(), (bn.bias.detach().float() - bn.running_mean.float() * scale).contiguous()
+        s1, h1 = c.get(("bnfold", 1), [sm[1].weight, sm[1].bias, sm[1].running_mean, sm[1].running_var], lambda: fold(sm[1]))
+        s2, h2 = c.get(("bnfold", 4), [sm[4].weight, sm[4].bias, sm[4].running_mean, sm[4].running_var], lambda: fold(sm[4]))
+        return w1k, sm[0].bias.detach(), s1, h1, w2t, sm[3].bias.detach(), s2, h2
+
+    def stream_lookahead_weight(self):
+        """[Hp][ctx] fp32: the lookahead taps at the internal width (zero rows for the padded units), as _LookaheadFn builds them"""
+        w = self.lookahead[0].conv.weight
+        return self._cache.get("la_w", [w], lambda: torch.cat(
+            [w.detach().reshape(w.shape[0], w.shape[2]), w.new_zeros((self._Hp - w.shape[0], w.shape[2]))], 0).contiguous())
+
+    @torch.no_grad()
+    def stream_rnn(self, X0, lens_dev, N, Tp, hs=None):
+        """The recurrent stack alone, eval mode: X0 [(t*N + n)][rnn_ld] rows in the sequence layout (what the conv stack hands on),
+        lens_dev [N] int32 on the device (valid frames of every stream, descending), hs as ``forward`` takes it.  Returns (the last
+        layer's rows [Tp*N][Hp] in the compute dtype, new_hs)."""
+        dtype = X0.dtype
+        with torch.autocast("cuda", enabled=False):
+            if self._Hp == self.rnns[0].hidden_size:
+                for li in range(len(self.rnns)):
+                    self._bias_views(li)
+            self._prep_rnn_weights(dtype, False)
+            self._frame_rows = None                      # every row is a frame of the chunk: no row list
+            X, hn_l, cn_l = X0, [], []
+            for i, layer in enumerate(self.rnns):
+                h0 = c0 = None
+                if hs is not None and hs[i] is not None:
+                    if self._kind == "lstm":
+                        h0, c0 = hs[i][0].float().contiguous(), hs[i][1].float().contiguous()
+                    else:
+                        h0 = hs[i].float().contiguous()
+                params = []
+                if layer.batch_norm is not None:
+                    params += [layer.batch_norm.module.weight, layer.batch_norm.module.bias]
+                p = layer.rnn
+                params += [p.weight_ih_l0, p.weight_hh_l0, p.bias_ih_l0, p.bias_hh_l0]
+                outs = _RnnLayerFn.apply(X, self, lens_dev, N, Tp, dtype, False, i, h0, c0, *params)
+                X = outs[0]
+                hn_l.append(outs[1])
+                if len(outs) > 2:
+                    cn_l.append(outs[2])
+        return X, ([(hn_l[i], cn_l[i]) for i in range(len(hn_l))] if self._kind == "lstm" else hn_l)
+
+    @torch.no_grad()
+    def stream_head(self, X, N, Tp):
+        """fc + softmax, eval mode, from post-lookahead rows [Tp*N][Hp]: probabilities (N, Tp, C) (a view, as ``forward`` returns)"""
+        fcm = self.fc[0].module
+        with torch.autocast("cuda", enabled=False):
+            logits = _HeadFn.apply(X, fcm[0].weight, fcm[0].bias, fcm[1].weight, self, N, Tp, X.dtype, False)
+        Cc = len(self.labels)
+        return ops.softmax_rows(logits, Cc).view(Tp, N, Cc).transpose(0, 1)
+
     def training_step(self, batch, batch_idx):
         inputs, targets, input_percentages, target_sizes = batch
         if inputs.is_cuda:

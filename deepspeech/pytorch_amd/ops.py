@@ -1512,3 +1512,59 @@ def wave_mix(wav, nsamples, gain=None, level=None, bank=None, noise_off=None, no
     call("ds2_wave_mix", P(wav), wav.stride(0), P(ns), N, P(g), P(lv), P(bank), blen, P(off), P(start),
          P(partial if lv is not None else None), P(out), out.shape[1], S())
     return out
+
+
+# ---- exact chunked inference (csrc/ds2_stream.hip, streaming.StreamingTranscriber(carry_context=True)) ----------------------
+STREAM_CONV_CARRY = 10     # positions both convolutions carry: their kernel width in time minus one
+
+
+def stream_state_views(dtype, N, F0, H, ctx, device):
+    """The double-buffered carries of one session in ONE zeroed buffer of ds2_stream_state_bytes: ([2][N][F0][10] f32 input frames,
+    [2][N][F1][10][32] conv1 activations, [2][ctx-1][N][H] RNN rows (None for ctx = 1)) as lists of the two views, and the buffer."""
+    nbytes = query("ds2_stream_state_bytes", dt(dtype), N, F0, H, ctx)
+    if nbytes <= 0:
+        raise ValueError("ds2_stream_state_bytes refuses dtype %s, N %d, F0 %d, H %d, ctx %d" % (dtype, N, F0, H, ctx))
+    buf = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+    F1 = conv_rows(F0)[0]
+    views, pos = [], 0
+    for shape, d in (((N, F0, STREAM_CONV_CARRY), torch.float32), ((N, F1, STREAM_CONV_CARRY, 32), dtype), ((ctx - 1, N, H), dtype)):
+        n = int(np.prod(shape)) * (4 if d == torch.float32 else 2)
+        pair = []
+        for _ in range(2):
+            pair.append(buf[pos:pos + n].view(d).view(shape) if n else None)
+            pos += rup(n, 256)
+        views.append(pair)
+    assert pos == nbytes, (pos, nbytes)
+    return views[0], views[1], views[2], buf
+
+
+def stream_conv1(x, carry, nxt, w1k, b1, scale, shift, off, J, dtype, lens=None, live=None):
+    """conv1 + eval BatchNorm + Hardtanh over the window [carry | x]: x (N, 1, F0, Tc) f32 (Tc may be 0), carry / nxt [N][F0][10] f32.
+    Returns the J new activation frames [N][F1][J][32] in `dtype`; nxt receives the next carry."""
+    N, _, F0, Tc = x.shape
+    y = torch.empty((N, conv_rows(F0)[0], J, 32), dtype=dtype, device=x.device)
+    call("ds2_stream_conv1", dt(dtype), PF(x) if Tc else C.c_void_p(0), PF(carry), PF(nxt), PF(w1k), PF(b1), PF(scale), PF(shift),
+         P(lens), P(live), P(y) if J else C.c_void_p(0), N, F0, Tc, off, J, S())
+    return y
+
+
+def stream_conv2(a1, carry, nxt, w2t, b2, scale, shift, off, J, rld, F0=161, lens=None, live=None, out=None):
+    """conv2 + eval BatchNorm + Hardtanh over the window [carry | a1]: a1 [N][F1][Jin][32], carry / nxt [N][F1][10][32].  Returns the
+    J new rows of the sequence layout, X0 [(j*N + n)][rld] (written into `out` when given); nxt receives the next carry."""
+    N, F1, Jin, _ = a1.shape
+    assert F1 == conv_rows(F0)[0] and carry.dtype == a1.dtype == nxt.dtype == w2t.dtype
+    x0 = torch.empty((J * N, rld), dtype=a1.dtype, device=a1.device) if out is None else out
+    assert tuple(x0.shape) == (J * N, rld) and x0.is_contiguous() and x0.dtype == a1.dtype
+    call("ds2_stream_conv2", dt(a1), P(a1) if Jin else C.c_void_p(0), P(carry), P(nxt), P(w2t), PF(b2), PF(scale), PF(shift),
+         P(lens), P(live), P(x0) if J else C.c_void_p(0), N, F0, Jin, off, J, rld, S())
+    return x0
+
+
+def stream_lookahead(x, carry, nxt, w, N, H, off, J, lens=None):
+    """hardtanh(lookahead) over the window of rows [carry ctx-1 | x Jin][N][H]; w [H][ctx] f32.  Returns the J new output rows
+    [J*N][H]; nxt receives the next carry (carry / nxt None for ctx = 1)."""
+    ctx, Jin = w.shape[1], x.shape[0] // N
+    y = torch.empty((J * N, H), dtype=x.dtype, device=x.device)
+    call("ds2_stream_lookahead", dt(x), P(x) if Jin else C.c_void_p(0), P(carry), P(nxt), PF(w), P(lens), P(y) if J else C.c_void_p(0),
+         N, H, ctx, Jin, off, J, S())
+    return y

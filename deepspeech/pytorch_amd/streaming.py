@@ -12,20 +12,63 @@ A session feed waits for the device once per chunk, where it fetches the text: `
 the labels of rank 0), the new labels in a greedy feed.  The decoder feed itself does not wait: ``forward`` returns the output
 lengths as a host tensor, so reading them costs no synchronisation, and they reach the device through pinned memory.
 
-The acoustic side is the reference's: the convolutions and the lookahead see each chunk on its own, and ``feed_wave`` normalises
-every chunk's spectrogram on its own (the reference's ChunkSpectrogramParser).  Carrying their context is outside this class."""
+By default the acoustic side is the reference's: the convolutions and the lookahead see each chunk on its own (every chunk
+boundary is an utterance boundary to them), and ``feed_wave`` normalises every chunk's spectrogram on its own (the reference's
+ChunkSpectrogramParser).
+
+``carry_context=True`` makes the acoustic side exact as well, for uni-directional models: the conv front-end and the lookahead
+carry their time context from feed to feed on the device (csrc/ds2_stream.hip), so the probabilities emitted over all feeds,
+concatenated per stream, are the one-shot eval ``forward`` of the whole utterance up to floating-point summation details.  A
+frame is emitted once nothing that a later feed brings can change it (``plan_feed``): with lookahead context C the first output
+arrives after 2 * C + 14 input frames (``latency_frames``; 54 frames = 0.54 s at C = 20) -- the model's latency, not the
+implementation's.  Streams start and end together; the last feed (``final=True``, or ``end()``) may be ragged."""
+import collections
+
 import torch
 
 from .decoder import BeamCTCDecoder
 
+CONV_CARRY = 10          # frames both convolutions carry: their kernel width in time minus one
+
+StreamPlan = collections.namedtuple("StreamPlan", "j1_old j1_new j2_old j2_new j3_old j3_new off1 off2 off3 k_in k_act k_la")
+
+
+def _range_ends(G, ctx, final):
+    """How many conv1 / conv2 (= RNN) / output frames are final after G input frames of a stream"""
+    if final:
+        Tp = (G - 1) // 2 + 1 if G > 0 else 0
+        return Tp, Tp, Tp
+    J1 = 0 if G < 6 else (G - 6) // 2 + 1          # conv1 frame j reads inputs 2j-5 .. 2j+5
+    J2 = max(J1 - 5, 0)                             # conv2 frame j reads conv1 activations j-5 .. j+5
+    return J1, J2, max(J2 - (ctx - 1), 0)           # output t reads RNN rows t .. t+ctx-1
+
+
+def plan_feed(frames, chunk, ctx, final=False):
+    """ds2_stream_plan: after `frames` input frames, a feed of `chunk` more computes conv1 frames [j1_old, j1_new), conv2 and RNN
+    frames [j2_old, j2_new) and outputs [j3_old, j3_new) (global indices, any range may be empty); off1..3 are the positions of
+    the first frame each kernel reads in its window [carry | chunk], k_* the carried positions."""
+    frames, chunk, ctx = int(frames), int(chunk), int(ctx)
+    if frames < 0 or chunk < 0 or ctx < 1:
+        raise ValueError("plan_feed: frames and chunk must be >= 0 and ctx >= 1")
+    o, e = _range_ends(frames, ctx, False), _range_ends(frames + chunk, ctx, bool(final))
+    return StreamPlan(o[0], e[0], o[1], e[1], o[2], e[2], 2 * o[0] + 5 - frames, o[1] + 5 - o[0], o[2] + (ctx - 1) - o[1],
+                      CONV_CARRY, CONV_CARRY, ctx - 1)
+
 
 class StreamingTranscriber:
-    def __init__(self, model, decoder, front_end=None, max_frames=6000):
+    def __init__(self, model, decoder, front_end=None, max_frames=6000, carry_context=False):
         """model: a DeepSpeech on a HIP device; decoder: a BeamCTCDecoder or GreedyDecoder over the model's labels; front_end: a
         SpectrogramFrontEnd for feed_wave (None = one with the model's spect_cfg, made on first use).  max_frames bounds the output
-        frames per stream of a beam decoder (its node pool is allocated at the first feed)."""
+        frames per stream of a beam decoder (its node pool is allocated at the first feed).  carry_context: exact chunked
+        inference (module docstring); uni-directional models only -- a reverse direction cannot be streamed exactly."""
         self.model, self.decoder, self.front_end, self.max_frames = model, decoder, front_end, int(max_frames)
         self.hs, self.stream = None, None
+        self.carry_context = bool(carry_context)
+        if self.carry_context and model.bidirectional:
+            raise ValueError("carry_context=True needs a uni-directional model: a reverse direction cannot be streamed exactly")
+        self._state = None                 # the carries (allocated at the first feed)
+        self._fed, self._ended, self._text = 0, False, None
+        self.last_output = None            # exact mode: (probabilities (N, J, C), valid frames per stream) of the last feed, or None
 
     def _open(self, N, device):
         if isinstance(self.decoder, BeamCTCDecoder):
@@ -35,13 +78,27 @@ class StreamingTranscriber:
 
     @property
     def frames(self):
-        """output frames consumed per stream (host ints)"""
+        """output frames consumed per stream (host ints); with carry_context: the output frames emitted so far"""
         return list(self.stream.frames) if self.stream is not None else []
 
-    def feed(self, spect, lengths):
+    @property
+    def latency_frames(self):
+        """input frames that must be fed before the first output frame: 0 without carry_context (every feed emits), else the
+        smallest G with an output frame final, 2 * lookahead_context + 14"""
+        if not self.carry_context:
+            return 0
+        return 2 * int(self.model.lookahead[0].context) + 14
+
+    def feed(self, spect, lengths, final=False):
         """spect: (N, 1, 161, Tc) spectrogram chunk on the model's device; lengths: [N] ints, the valid input frames of every
-        stream's chunk (what ``forward`` takes).  Returns the best transcript so far per stream (a list of N str)."""
+        stream's chunk (what ``forward`` takes).  Returns the best transcript so far per stream (a list of N str).
+        carry_context: every stream's length is Tc unless final=True, the last feed of the utterance, whose lengths may be ragged
+        (descending, as ``forward`` takes them)."""
         m = self.model
+        if self.carry_context:
+            return self._feed_exact(spect, lengths, bool(final))
+        if final:
+            raise ValueError("final=True is a carry_context=True feed; without it every feed stands on its own")
         if self.stream is None:
             self._open(spect.shape[0], spect.device)
         elif spect.shape[0] != self.stream.num_streams:
@@ -59,6 +116,9 @@ class StreamingTranscriber:
     def feed_wave(self, wav, nsamples):
         """wav: [N][Lmax] waveform chunk on the device, nsamples: [N] ints.  The chunk's spectrogram is computed and normalised on
         its own by the front end, then fed."""
+        if self.carry_context:
+            raise ValueError("feed_wave is not available with carry_context=True: normalising the whole utterance's spectrogram is "
+                             "not causal and normalising each chunk is not what the one-shot forward sees; feed spectrogram chunks")
         if self.front_end is None:
             from .spectrogram import SpectrogramFrontEnd
             self.front_end = SpectrogramFrontEnd(getattr(self.model, "spect_cfg", None))
@@ -84,7 +144,93 @@ class StreamingTranscriber:
         return [[t] for t in self.stream.text], [[o] for o in self.stream.offsets]
 
     def reset(self):
-        """Every stream starts a new utterance: the hidden state and the decoder state are dropped."""
+        """Every stream starts a new utterance: the hidden state and the decoder state are dropped; with carry_context the carries
+        are zeroed on the device."""
         self.hs = None
         if self.stream is not None:
             self.stream.reset()
+        if self._state is not None:
+            self._state["buf"].zero_()
+            self._state["cur"] = [0, 0, 0]
+        self._fed, self._ended, self.last_output = 0, False, None
+        if self._text is not None:
+            self._text = [''] * len(self._text)
+
+    # ---- exact mode -----------------------------------------------------------------------------------------------------------
+    def end(self):
+        """carry_context: the end of the utterance as a final feed of nothing -- every frame still held back is emitted.  Returns
+        the transcripts."""
+        if not self.carry_context:
+            raise ValueError("end() belongs to carry_context=True; without it there is nothing held back")
+        if self._state is None:
+            raise ValueError("StreamingTranscriber.end: nothing has been fed")
+        N, F0 = self._state["N"], self.model._F0
+        return self._feed_exact(torch.empty((N, 1, F0, 0), dtype=torch.float32, device=self._state["buf"].device), [0] * N, True)
+
+    def _feed_exact(self, spect, lengths, final):
+        from . import ops
+        m = self.model
+        if self._ended:
+            raise ValueError("the utterance has ended (a final feed or end()); reset() starts the next one")
+        if spect.dim() != 4 or spect.shape[1] != 1 or spect.shape[2] != m._F0:
+            raise ValueError("expected a (N, 1, %d, Tc) spectrogram chunk, got %s" % (m._F0, tuple(spect.shape)))
+        N, Tc = spect.shape[0], spect.shape[3]
+        lens = [int(v) for v in lengths]
+        if len(lens) != N:
+            raise ValueError("%d lengths for %d streams" % (len(lens), N))
+        if not final and (Tc < 1 or any(v != Tc for v in lens)):
+            raise ValueError("a feed that is not final needs every stream's length to be the chunk's %d frames (>= 1), got %s" % (Tc, lens))
+        if final and (any(v < 0 or v > Tc for v in lens) or any(a < b for a, b in zip(lens, lens[1:]))):
+            raise ValueError("the final feed's lengths must lie in [0, %d] and descend, got %s" % (Tc, lens))
+        if self.stream is None:
+            self._open(N, spect.device)
+            self._text = [''] * N
+        elif N != self.stream.num_streams:
+            raise ValueError("this session has %d streams, the chunk has %d" % (self.stream.num_streams, N))
+        ctx, H, dev = int(m.lookahead[0].context), m._Hp, spect.device
+        dtype = m._stream_begin()
+        st = self._state
+        if st is None or st["dtype"] != dtype:
+            cin, cact, cla, buf = ops.stream_state_views(dtype, N, m._F0, H, ctx, dev)
+            st = self._state = dict(cin=cin, cact=cact, cla=cla, buf=buf, cur=[0, 0, 0], N=N, dtype=dtype)
+        chunk = max(lens) if lens else 0
+        p = plan_feed(self._fed, chunk, ctx, final)
+        J1, J2, J3 = p.j1_new - p.j1_old, p.j2_new - p.j2_old, p.j3_new - p.j3_old
+        len_dev = live1 = live2 = None
+        sizes = [J3] * N
+        if final:
+            # the streams' own ends: inputs, activations and RNN rows beyond them read as zero, masked frames are written as zero
+            tot = [(self._fed + v - 1) // 2 + 1 if self._fed + v > 0 else 0 for v in lens]
+            sizes = [min(max(t - p.j3_old, 0), J3) for t in tot]
+            host = torch.tensor([lens, [min(max(t - p.j1_old, 0), J1) for t in tot], [min(max(t - p.j2_old, 0), J2) for t in tot]],
+                                dtype=torch.int32)
+            len_dev, live1, live2 = host.to(dev, non_blocking=True)
+        x = spect.contiguous().float()
+        self.last_output = None
+        with torch.no_grad():
+            w1k, b1, s1, h1, w2t, b2, s2, h2 = m.stream_front_weights(dtype)
+            cur = st["cur"]
+            a1 = None
+            if chunk > 0 or J1 > 0:
+                a1 = ops.stream_conv1(x, st["cin"][cur[0]], st["cin"][1 - cur[0]], w1k, b1, s1, h1, p.off1, J1, dtype, lens=len_dev, live=live1)
+                cur[0] ^= 1
+            if J1 > 0 or J2 > 0:
+                if a1 is None:
+                    a1 = torch.empty((N, m._F1, 0, 32), dtype=dtype, device=dev)
+                x0 = ops.stream_conv2(a1, st["cact"][cur[1]], st["cact"][1 - cur[1]], w2t, b2, s2, h2, p.off2, J2, m._rnn_ld, F0=m._F0,
+                                      live=live2)
+                cur[1] ^= 1
+            if J2 > 0:
+                rnn_lens = live2 if final else torch.full((N,), J2, dtype=torch.int32, device=dev)
+                rows, self.hs = m.stream_rnn(x0, rnn_lens, N, J2, self.hs)
+                y = ops.stream_lookahead(rows, st["cla"][cur[2]], st["cla"][1 - cur[2]], m.stream_lookahead_weight(), N, H, p.off3, J3)
+                if ctx > 1:
+                    cur[2] ^= 1
+                if J3 > 0:
+                    probs = m.stream_head(y, N, J3)
+                    self.last_output = (probs, sizes)
+                    self.stream.feed(probs, torch.tensor(sizes, dtype=torch.int))
+                    self._text = self.best()
+        self._fed += chunk
+        self._ended = final
+        return list(self._text)

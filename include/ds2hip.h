@@ -484,6 +484,46 @@ int ds2_beam_stream_feed_lm(const float* x, long stride_n, long stride_t, int N,
                             void* state, int max_frames, int* tokens, int* offsets, long row_stride, int out_ranks, int* lens,
                             float* scores, float* acoustic, void* ws, ds2_stream_t stream);
 
+/* ---- exact chunked inference: conv front-end and lookahead with carried time context -------------
+ * For a uni-directional model in eval mode: fed chunk by chunk, the three kernels below give the frames of the one-shot forward.
+ * Each reads, per stream n, a VIRTUAL WINDOW over time: position i < K comes from `carry` (the K positions in front of the
+ * chunk), K <= i < K + len[n] from the chunk, everything else is 0; len [N] int32 on the device, null = the whole chunk; a
+ * value outside [0, chunk] is clamped.  Output frame j of the call, 0 <= j < J, reads the window from position off + stride * j
+ * on; frames j >= live[n] are written as zeros (live [N] int32 on the device, null = J).  Each also writes the NEXT carry
+ * next[i] = V[len[n] + i], i < K, into a second buffer (next != carry: the old one is read during the call); a session
+ * ping-pongs two.  A zero carry at the start of a stream is the one-shot's left zero padding.  J = 0 writes the carry alone.
+ * ds2_stream_plan (host only): after `frames` input frames, a feed of `chunk` more (final != 0: the last of the utterance)
+ *   computes conv1 frames [out[0], out[1]), conv2 / RNN frames [out[2], out[3]) and output frames [out[4], out[5]) -- global
+ *   indices per stream, any range may be empty; out[6..8] are the `off` of conv1, conv2 and the lookahead; out[9..11] the
+ *   carried positions K: 10 input frames, 10 conv1 activation frames, ctx - 1 RNN rows.  Not final, with G = frames + chunk:
+ *   J1 = 0 if G < 6 else (G - 6) / 2 + 1, J2 = max(J1 - 5, 0), J3 = max(J2 - (ctx - 1), 0); final: all three (G - 1) / 2 + 1
+ *   (0 for G = 0).  At the end of an utterance the per-stream totals go in through len / live.
+ * ds2_stream_state_bytes (host only): the double-buffered carries of one session, each 256-byte aligned: 2 x ([N][F0][10] f32 +
+ *   [N][F1][10][32] + [ctx - 1][N][H] in the storage type); 0 for an argument out of range.
+ * ds2_stream_conv1: Conv2d(1, 32, (41, 11), stride (2, 2)) + eval BatchNorm2d + Hardtanh(0, 20) over [carry | x]; x [N][F0][Tc]
+ *   f32, carry / next [N][F0][10] f32, K = 10, stride 2.  w1k [451][32], b1 [32] as for ds2_conv1_fwd; scale = gamma *
+ *   rsqrt(running_var + eps) and shift = beta - running_mean * scale, [32] f32: y = clamp(fma(acc + bias, scale, shift), 0, 20),
+ *   y [N][F1][J][32] in the storage type (what ds2_stream_conv2 reads).  Any F0 ds2_conv_rows accepts.
+ * ds2_stream_conv2: Conv2d(32, 32, (21, 11), stride (2, 1)) + eval BatchNorm2d + Hardtanh(0, 20) on the matrix pipes over
+ *   [carry | a1]; a1 [N][F1][Jin][32], carry / next [N][F1][10][32], w2t [21*11][32][32] in the storage type (as ds2_conv2_fwd),
+ *   K = 10, stride 1.  Writes the sequence layout the recurrent stack reads: x0[(j * N + n) * rld + f * 32 + c], columns
+ *   [32 * F2, rld) zero; rld >= 32 * F2, a multiple of 16; J * N * rld < 2^31.
+ * ds2_stream_lookahead: y[t][n][h] = hardtanh(sum_k w[h][k] * V[off + t + k]) over rows [carry ctx - 1 | x Jin][N][H], taps
+ *   ascending with fmaf (ds2_lookahead_fwd's order); w [H][ctx] f32; K = ctx - 1, stride 1; ctx = 1: no carry (null).  H a
+ *   multiple of the 16-byte vector (4 f32 / 8 bf16).  No live: rows beyond a stream's end are zero already.
+ * DS2_ERR_ARG: N < 1, a negative count or offset, a null buffer that the counts say is read or written, next == carry, and the
+ *   limits above; DS2_ERR_DTYPE: a storage type other than f32 / bf16. */
+int ds2_stream_plan(long frames, int chunk, int ctx, int final, int* out);
+long ds2_stream_state_bytes(int dtype, int N, int F0, int H, int ctx);
+int ds2_stream_conv1(int dtype, const float* x, const float* carry, float* next, const float* w1k, const float* b1,
+                     const float* scale, const float* shift, const int* len, const int* live, void* y, int N, int F0, int Tc,
+                     int off, int J, ds2_stream_t stream);
+int ds2_stream_conv2(int dtype, const void* a1, const void* carry, void* next, const void* w2t, const float* b2, const float* scale,
+                     const float* shift, const int* len, const int* live, void* x0, int N, int F0, int Jin, int off, int J,
+                     int rld, ds2_stream_t stream);
+int ds2_stream_lookahead(int dtype, const void* x, const void* carry, void* next, const float* w, const int* len, void* y, int N,
+                         int H, int ctx, int Jin, int off, int J, ds2_stream_t stream);
+
 /* ---- character / word error counts on the device (the edit distances of validation.py:66-132, decoder.CharErrorRate /
  * WordErrorRate) ----
  * hyp: P rows of int32 labels, row p at hyp + p * hyp_stride with hyp_lens[p] labels; ref: the references' labels back to back,

@@ -6,9 +6,15 @@ forward sweep takes h0/c0 and returns hn/cn).  Prints one JSON line per model: p
 
     python tools/bench_stream.py [--seconds 30 --chunk 2.0 --stock]
     python tools/bench_stream.py --decode beam [--beam-width 100]
+    python tools/bench_stream.py --carry [--decode greedy --chunk 0.2 --streams 1]
 
 With --decode greedy|beam the drop-in class runs inside a streaming.StreamingTranscriber: every chunk's output goes to the decoder
 stream on the device and the best transcript so far comes back per chunk (no output leaves the device, nothing is decoded twice).
+
+--carry times a session feed of the uni-directional model in both modes at the same chunk size: the default one (every chunk on its
+own, as in the reference) and carry_context=True (exact chunked inference: conv and lookahead context carried on the device, DESIGN.md
+section 3.6.2); the exact mode ends the utterance with end().  It also prints, for a small uni-directional GRU in bf16, the error of
+the streamed probabilities and of the one-shot forward against the fp64 oracle (e_stream, e_oneshot).
 """
 import argparse
 import json
@@ -57,6 +63,61 @@ def run_decoding(st, chunks, reps):
     return np.array(lat), total, text, st.frames
 
 
+def run_carry(st, chunks, reps, N):
+    """run_decoding() for either mode of a session over N streams; the exact mode ends the utterance (end()) outside the timed feeds"""
+    lat, emitted = [], 0
+    for r in range(reps + 1):
+        st.reset()
+        torch.cuda.synchronize()
+        t_all = time.perf_counter()
+        for c in chunks:
+            t0 = time.perf_counter()
+            text = st.feed(c, [c.shape[3]] * N)
+            if r > 0:
+                lat.append(time.perf_counter() - t0)
+        emitted = st.frames[0]
+        if st.carry_context:
+            text = st.end()
+        torch.cuda.synchronize()
+        total = time.perf_counter() - t_all
+    return np.array(lat), total, text, emitted, st.frames[0]
+
+
+def carry_error():
+    """bf16 on a small uni-directional GRU (32 units, 2 layers, lookahead 20), 2 streams of 160 / 155 frames fed as (54, 1, 2, 37, 66):
+    max |p - p_oracle| over the valid frames of the streamed session and of the one-shot forward"""
+    from deepspeech.pytorch_amd import configs, decoder as D, synth
+    from deepspeech.pytorch_amd.model import DeepSpeech
+    from deepspeech.pytorch_amd.streaming import StreamingTranscriber
+    from oracle import ds2_oracle as O, ds2_torch_port as TP
+    cfg = dict(rnn_type="gru", hidden_size=32, hidden_layers=2, bidirectional=False, lookahead_context=20)
+    state = TP.random_state(cfg, 0)
+    mc = configs.UniDirectionalConfig(rnn_type=configs.RNNType.gru, hidden_size=32, hidden_layers=2, lookahead_context=20)
+    m = DeepSpeech(configs.LABELS, mc, "bf16", configs.AdamConfig(), configs.SpectConfig())
+    m.load_state_dict({k: v.clone() for k, v in state.items()}, strict=True)
+    m = m.to("cuda").eval()
+    lengths = np.array([160, 155])
+    inputs = synth.synth_batch(lengths, seed=11)[0]
+    P = {k: v.double().numpy() if v.dtype.is_floating_point else v.numpy() for k, v in state.items()}
+    ref, out_lens = O.model_forward(P, cfg, inputs.astype(np.float64), lengths, train=False, keep_cache=False)[:2]
+    x = torch.from_numpy(inputs).to("cuda")
+    with torch.no_grad():
+        one = m(x, torch.from_numpy(lengths).int())[0].double().cpu().numpy()
+    st = StreamingTranscriber(m, D.GreedyDecoder(configs.LABELS), carry_context=True)
+    got, pos, chunks = [[], []], 0, (54, 1, 2, 37, 66)
+    for i, c in enumerate(chunks):
+        last = i == len(chunks) - 1
+        st.feed(x[:, :, :, pos:pos + c].contiguous(), [int(g) - pos for g in lengths] if last else [c, c], final=last)
+        if st.last_output is not None:
+            for n in range(2):
+                got[n].append(st.last_output[0][n, :st.last_output[1][n]].double().cpu().numpy())
+        pos += c
+    err = lambda rows: float(max(np.abs(rows[n] - ref[n, :out_lens[n]]).max() for n in range(2)))
+    print(json.dumps({"metric": "bf16 probabilities against the fp64 oracle, max abs over valid frames", "model": "uni-GRU-32x2+lookahead20",
+                      "frames": lengths.tolist(), "chunks": list(chunks), "e_stream": err([np.concatenate(g) for g in got]),
+                      "e_oneshot": err([one[n, :out_lens[n]] for n in range(2)])}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=30.0)
@@ -65,6 +126,8 @@ def main():
     ap.add_argument("--stock", action="store_true")
     ap.add_argument("--decode", choices=("greedy", "beam"), default=None, help="decode inside the chunk loop (StreamingTranscriber)")
     ap.add_argument("--beam-width", type=int, default=100)
+    ap.add_argument("--carry", action="store_true", help="time a session feed with and without carry_context (uni-directional model)")
+    ap.add_argument("--streams", type=int, default=1, help="--carry: streams fed in lock step")
     a = ap.parse_args()
     from deepspeech.pytorch_amd import configs
     from deepspeech.pytorch_amd.model import DeepSpeech
@@ -97,6 +160,25 @@ def main():
                     with torch.no_grad(), torch.autocast("cuda", dtype=torch.bfloat16):
                         out, _, hs2 = port.forward(c, torch.tensor([c.shape[3]], dtype=torch.int), train=False, hs=hs, return_hs=True)
                     return out.float(), hs2
+            if impl == "ds2hip" and a.carry:
+                if bi:
+                    continue                  # a reverse direction cannot be streamed exactly
+                from deepspeech.pytorch_amd import decoder as D
+                from deepspeech.pytorch_amd.streaming import StreamingTranscriber
+                Ns = a.streams
+                dec = D.BeamCTCDecoder(configs.LABELS, beam_width=a.beam_width) if a.decode == "beam" else D.GreedyDecoder(configs.LABELS)
+                even = [c.expand(Ns, -1, -1, -1).contiguous() for c in chunks if c.shape[3] == tc]      # equal chunks only
+                for carry in (False, True):
+                    st = StreamingTranscriber(m, dec, max_frames=T // 2 + len(chunks), carry_context=carry)
+                    lat, total, text, emitted, frames = run_carry(st, even, a.reps, Ns)
+                    print(json.dumps({"metric": "session feed, chunked inference (StreamingTranscriber)", "model": name,
+                                      "carry_context": carry, "decode": a.decode or "greedy", "streams": Ns, "audio_seconds": a.seconds,
+                                      "chunk_seconds": a.chunk, "chunks": len(even), "latency_frames": st.latency_frames,
+                                      "ms_per_feed_median": round(float(np.median(lat)) * 1e3, 3),
+                                      "ms_per_feed_p95": round(float(np.percentile(lat, 95)) * 1e3, 3),
+                                      "real_time_factor": round(a.seconds / total, 1), "out_frames_before_end": int(emitted),
+                                      "out_frames": int(frames), "dtype": "bf16"}))
+                continue
             if impl == "ds2hip" and a.decode:
                 from deepspeech.pytorch_amd import decoder as D
                 from deepspeech.pytorch_amd.streaming import StreamingTranscriber
@@ -124,3 +206,5 @@ def main():
 
 if __name__ == "__main__":
     main()
+    if "--carry" in sys.argv:
+        carry_error()
