@@ -626,9 +626,6 @@ constexpr int CWR_SPLITS = 85;           // position splits: 6 row groups x 85 =
 // out of HBM / the Infinity Cache once per XCD and out of that XCD's L2 the other five times.
 // ------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void* cw_lds_ptr_t;
-#ifndef CWD_ABL
-#define CWD_ABL 0   // timing-only ablations: 1 no DMA after the first tile, 2 no LDS reads after k-step 0
-#endif
 #ifndef CWD_KSN
 #define CWD_KSN 7
 #endif
@@ -650,8 +647,7 @@ __device__ __forceinline__ uint4 cwd_frag(const CwdFrag& f) { return make_uint4(
 #define CWD_READ(FA, FB, KS, IDX)                                                                             \
   do {                                                                                                        \
     constexpr int idx_ = (IDX);                                                                               \
-    if constexpr ((CWD_ABL & 2) != 0 && (KS) > 0) {                                                           \
-    } else if constexpr (idx_ < 8) {                                                                          \
+    if constexpr (idx_ < 8) {                                                                                 \
       if constexpr (idx_ % 2 == 0) CWD_RDTR(FA[idx_ / 2].lo, aA, (idx_ / 2) * DYB + (KS) * 1024);             \
       else CWD_RDTR(FA[idx_ / 2].hi, aA, (idx_ / 2) * DYB + (KS) * 1024 + 256);                               \
     } else if constexpr (idx_ < 14) {                                                                         \
@@ -698,10 +694,8 @@ __device__ __forceinline__ void cwd_kstep(ds2_f32x16 (&acc)[4][3], CwdFrag (&fa)
     CWD_READ(fa[n], fb[n], KS + 1, 2 * (M));                                                 \
     CWD_READ(fa[n], fb[n], KS + 1, 2 * (M) + 1);                                             \
   }                                                                                          \
-  if constexpr (!(CWD_ABL & 1)) {                                                            \
-    if constexpr ((M) == 8) cwd_dma_dy<KSN, KS>(nx);                                         \
-    if constexpr ((M) == 10 && KS < 3) cwd_dma_x<KSN, KS>(nx);                               \
-  }                                                                                          \
+  if constexpr ((M) == 8) cwd_dma_dy<KSN, KS>(nx);                                           \
+  if constexpr ((M) == 10 && KS < 3) cwd_dma_x<KSN, KS>(nx);                                 \
   __builtin_amdgcn_sched_barrier(0);
   CWD_SLOT(0) CWD_SLOT(1) CWD_SLOT(2) CWD_SLOT(3) CWD_SLOT(4) CWD_SLOT(5)
   CWD_SLOT(6) CWD_SLOT(7) CWD_SLOT(8) CWD_SLOT(9) CWD_SLOT(10) CWD_SLOT(11)
@@ -854,7 +848,7 @@ __global__ void __launch_bounds__(256, cwd_wgs_per_cu(KSN)) k_conv2_wgrad_bf16d(
 // The waves' partial sums over their items meet in LDS once per tile (fixed order), wave w finishing output row w; the next
 // tile's input patch travels global -> LDS by DMA during the MFMAs (two patch buffers; round 5 -- until then it went through 40
 // registers per lane and a commit phase behind the MFMAs).  Where a tile's time goes (config 3, forward = two launches, timing-only
-// ablations RT_ABL): 0.51 ms as shipped, 0.46 without the DMA pieces, 0.40 without the partial-sum exchange and the output, 0.37
+// ablations): 0.51 ms as shipped, 0.46 without the DMA pieces, 0.40 without the partial-sum exchange and the output, 0.37
 // without both; 0.28 would be the matrix pipe alone.
 // ============================================================================================================
 struct RTapArgs {
@@ -912,9 +906,6 @@ __device__ __forceinline__ void rt_dma_all(const RtNext& nx) {
   rt_dma_piece<PR, I>(nx);
   if constexpr (I + 1 < 12) rt_dma_all<PR, I + 1>(nx);
 }
-#ifndef RT_ABL
-#define RT_ABL 0   // timing-only ablations: 1 no DMA pieces in the loop, 2 no partial-sum exchange and no output, 4 no fragment reads
-#endif
 constexpr int RT_AH = 4;          // steps a fragment is read ahead of its MFMAs (two: a step of one or two MFMAs is shorter than the LDS)
 template <int ST>
 __device__ __forceinline__ void rt_prefetch(uint4 (&bq)[RT_AH + 1], const uint32_t (&aj)[6]) {
@@ -941,7 +932,7 @@ __device__ __forceinline__ void rt_step(ds2_f32x16 (&acc)[RT_FB], const uint4 (&
     const int m = rho - fl;
     if (m >= 0 && m < KF) Mma<bf16_t>::mma32(acc[fl], A[m][j], bq[ST % (RT_AH + 1)]);
   }
-  if constexpr (ST % 6 == 3 && ST >= 9 && (ST - 9) / 6 < 12 && !(RT_ABL & 1)) rt_dma_piece<PR, (ST - 9) / 6>(nx);   // behind an MFMA group of the middle rows
+  if constexpr (ST % 6 == 3 && ST >= 9 && (ST - 9) / 6 < 12) rt_dma_piece<PR, (ST - 9) / 6>(nx);   // behind an MFMA group of the middle rows
   __builtin_amdgcn_sched_barrier(0);
   if constexpr (ST + 1 < NS) rt_step<KF, ST + 1>(acc, A, bq, aj, nx);
 }
@@ -1042,12 +1033,6 @@ __global__ void __launch_bounds__(256, 1) k_conv_rtap(RTapArgs a) {
       rt_step<KF, 0>(acc, A, bq, aj, nx);
     }
     // ---- the four waves' partial sums meet: red[wave][row][g][lane] x 16 bytes
-    if (RT_ABL & 2) {
-      if (acc[0][0] == 123.f && acc[1][1] == 3.f && acc[2][2] == 1.f && acc[3][3] == 7.f) red[0] = 1.f;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      continue;
-    }
 #pragma unroll
     for (int fl = 0; fl < RT_FB; ++fl)
 #pragma unroll

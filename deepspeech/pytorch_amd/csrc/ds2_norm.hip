@@ -324,35 +324,10 @@ __global__ void k_bn_bwd_finalize(const float* __restrict__ psum_g, const float*
   c2[c] = (float)(q / count);
 }
 
-template <typename T, bool CONV, bool SEQ_IN>
-__global__ void __launch_bounds__(256)
-    k_bn_bwd_apply(const T* __restrict__ G, const T* __restrict__ X, T* __restrict__ DX, long R, int C, long ldg, long ldx,
-                   long lddx, const float* __restrict__ scale, const float* __restrict__ shift,
-                   const float* __restrict__ mean, const float* __restrict__ rstd, const float* __restrict__ c1,
-                   const float* __restrict__ c2, RowMap rm, const int* __restrict__ lens, int N) {
-  constexpr int V = Vec16<T>::N;
-  const int chunks = C / V;
-  const long total = R * chunks;
-  for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-    long r = e / chunks;
-    int c0 = (int)(e % chunks) * V;
-    float g[V], xh[V], o[V];
-    if (load_gated<T, CONV, SEQ_IN>(G, X, r, c0, C, ldg, ldx, scale, shift, mean, rstd, rm, lens, N, g, xh)) {
-#pragma unroll
-      for (int i = 0; i < V; ++i) o[i] = bn_dx(g[i], xh[i], scale[c0 + i], c1[c0 + i], c2[c0 + i]);
-    } else {
-      // masked position: the mask that follows the conv (model.py:61-68) zeroes this gradient
-#pragma unroll
-      for (int i = 0; i < V; ++i) o[i] = 0.f;
-    }
-    Vec16<T>::store(DX + r * lddx + c0, o);
-  }
-}
-
-// Round 6: the same pass on the reductions' thread map -- a thread owns ONE 16-byte column chunk for the whole launch, so the six
-// per-channel vectors of its chunk (scale, shift, mean, rstd, c1, c2: 48 values in bf16 storage) are loaded once instead of once per
-// row (the grid-stride form above re-read them for every 16 bytes of payload: 3.1-3.9 TB/s on the conv tensors and at H = 1280), and
-// two rows are in flight per thread.  Same arithmetic per element: bit-identical output.
+// The apply pass of the backward, on the reductions' thread map -- a thread owns ONE 16-byte column chunk for the whole launch, so the
+// six per-channel vectors of its chunk (scale, shift, mean, rstd, c1, c2: 48 values in bf16 storage) are loaded once instead of once
+// per row (the grid-stride form of rounds 1-5 re-read them for every 16 bytes of payload: 3.1-3.9 TB/s on the conv tensors and at
+// H = 1280), and two rows are in flight per thread.
 template <typename T, bool CONV, bool SEQ_IN>
 __global__ void __launch_bounds__(NORM_RY* NORM_CX)
     k_bn_bwd_apply_cols(const T* __restrict__ G, const T* __restrict__ X, T* __restrict__ DX, long R, int C, long ldg, long ldx,
@@ -559,16 +534,9 @@ int ds2_bn_bwd(int dtype, int mode, const void* G, const void* X, void* DX, long
   if (agy > 2048 / acb) agy = 2048 / acb;
   if (agy < 1) agy = 1;
   const dim3 agrd(acb, (unsigned)agy);
-#ifdef DS2_BN_APPLY_GRIDSTRIDE   /* A/B (tools/ab_variants.py): the grid-stride form of rounds 1-5 */
-#define LAUNCH_APP(TT, CV, SI)                                                                                          \
-  hipLaunchKernelGGL((k_bn_bwd_apply<TT, CV, SI>), dim3(apply_grid(R*(C / V))), dim3(256), 0, st, (const TT*)G,           \
-                     (const TT*)X, (TT*)DX, R, C, ldg, ldx, lddx, save_scale, save_shift, save_mean, save_rstd, c1, c2, \
-                     rm, lens, N)
-#else
 #define LAUNCH_APP(TT, CV, SI)                                                                                          \
   hipLaunchKernelGGL((k_bn_bwd_apply_cols<TT, CV, SI>), agrd, blk, 0, st, (const TT*)G, (const TT*)X, (TT*)DX, R, C, ldg, \
                      ldx, lddx, save_scale, save_shift, save_mean, save_rstd, c1, c2, rm, lens, N)
-#endif
 #define BOTH(WHICH)                                        \
   if (dtype == DS2_F32) {                                  \
     if (mode == 0) WHICH(float, false, false);             \

@@ -14,9 +14,9 @@
 #include "ds2_rnn_persist_widths.h"
 
 namespace ds2p {
-int launch_gru(bool bwd, int H, const PArgs& a, hipStream_t st, bool dense);
-int launch_lstm(bool bwd, int H, const PArgs& a, hipStream_t st, bool dense);
-int launch_rnn(bool bwd, int H, const PArgs& a, hipStream_t st, bool dense);
+int launch_gru(bool bwd, int H, const PArgs& a, hipStream_t st);
+int launch_lstm(bool bwd, int H, const PArgs& a, hipStream_t st);
+int launch_rnn(bool bwd, int H, const PArgs& a, hipStream_t st);
 }  // namespace ds2p
 namespace ds2r {
 #define DS2_ROW(HH)                                                                         \
@@ -51,11 +51,11 @@ unsigned variant_of(const ds2_persist_opts* o) { return o ? o->variant : 0u; }
 
 int gates(int cell) { return cell == CELL_GRU ? 3 : cell == CELL_LSTM ? 4 : 1; }
 
-int launch1_any(bool bwd, int cell, int H, const PArgs& a, hipStream_t st, bool dense) {
+int launch1_any(bool bwd, int cell, int H, const PArgs& a, hipStream_t st) {
   switch (cell) {
-    case CELL_GRU: return launch_gru(bwd, H, a, st, dense);
-    case CELL_LSTM: return launch_lstm(bwd, H, a, st, dense);
-    case CELL_RNN: return launch_rnn(bwd, H, a, st, dense);
+    case CELL_GRU: return launch_gru(bwd, H, a, st);
+    case CELL_LSTM: return launch_lstm(bwd, H, a, st);
+    case CELL_RNN: return launch_rnn(bwd, H, a, st);
   }
   return DS2_ERR_ARG;
 }
@@ -97,17 +97,18 @@ struct Plan {
   long ws_bytes() const { return family ? reset_bytes(true) + probe_bytes : 0; }   // BPTT exchanges G * H values per sample, forward H
 };
 
-// Routing A/B bits (ds2_persist_opts.variant / the `variant` argument of the queries; 0 = the shipping routing): bit 0 = do not use
-// the round-4 general kernels; 1 = two-set groups execute every half-step; 2 = unused; 3 = the general kernels take H = 1024 too;
-// 4 = the tuned kernels keep 9-16 clips per group; 5 = the 8-clip tuned kernels use dense products (round 4's form) instead of the
-// structured-sparse ones; 6 = the general kernels keep dense 16-row tiles for groups of <= 8 clips too (round 5's form); 7 = groups
-// of 9-16 clips run as two structured-sparse sets (measured and rejected, kept for A/B).  They travel with every call (and so does
-// the spin budget), so the entries are re-entrant and a test that dies cannot re-route the launches after it.
+// Routing bits (ds2_persist_opts.variant / the `variant` argument of the queries; 0 = the shipping routing), by which the tests and the
+// probe tools reach a family on shapes that the default routing sends elsewhere: bit 0 (1) = do not use the round-4 general kernels;
+// bit 3 (8) = the general kernels take H = 1024 too; bit 4 (16) = the tuned kernels keep 9-16 clips per group.  Any other bit is a
+// caller's mistake: no family, and the sweeps answer DS2_ERR_ARG.  The bits travel with every call (and so does the spin budget), so
+// the entries are re-entrant and a test that dies cannot re-route the launches after it.
 //
 // cus = compute units to plan for: the device's, or 256 for "would a full device take this shape".  Arithmetic and the instantiation
 // tables only -- no HIP call.  Every family wants one workgroup per CU and all of them co-resident, hence >= 256 CUs.
+constexpr unsigned VARIANT_LIVE = 1u | 8u | 16u;
 bool plan(int dtype, int cell, int D, int N, int H, int cus, unsigned variant, Plan& pl) {
   pl = Plan{};
+  if (variant & ~VARIANT_LIVE) return false;
   if ((cell != CELL_GRU && cell != CELL_LSTM && cell != CELL_RNN) || (D != 1 && D != 2) || N < 1 || cus < 256) return false;
   const bool bf16 = dtype == DS2_BF16;
   const long kf = H, kb = (long)gates(cell) * H;   // K of the recurrent product: forward, BPTT
@@ -137,14 +138,13 @@ bool plan(int dtype, int cell, int D, int N, int H, int cus, unsigned variant, P
     pl.gpd = (pl.xmap ? 8 * pl.gx : 256 / pl.P) / D;
     if (pl.gpd > N) pl.gpd = N;
     const int ns = pl.gpd ? ceil_div(N, pl.gpd) : 0;
-    // groups of <= 8 clips: ONE set on the structured-sparse products where the width has them (H % 256 == 0; variant bit 6: never).
-    // 9-16 clips as two sparse sets of <= 8 (variant bit 7, A/B only) LOSE to one dense 16-row set: a half-step is a latency chain
-    // whatever its matrix work -- config 5b's groups of 11: 4.07 / 4.54 us per time step against 2.71 / 3.38 (profiles/r06c_time_sweeps.txt)
-    const int sparse_max = (variant & 128u) ? 16 : 8;
-    // measured (profiles/r06e_sparse_single_set.txt): LSTM-1280, 8 clips per group 2.62 / 2.88 against 2.70 / 3.01 us per time step
-    // dense; GRU-768 equal; LSTM-512 forward 1.93 against 1.69 (two k-blocks per wave leave nothing to overlap) -> from H = 1024 on
-    pl.sparse = !(variant & 64u) && ns <= sparse_max && (H >= 1024 || (variant & 128u)) && inst3(cell, H, 1);
-    pl.nset = pl.sparse ? (ns <= 8 ? 1 : 2) : (ns <= 16 ? 1 : ns <= 32 ? 2 : 0);
+    // groups of <= 8 clips: ONE set on the structured-sparse products where the width has them (H % 256 == 0).  9-16 clips stay one
+    // dense 16-row set: as two sparse sets of <= 8 they lose, a half-step is a latency chain whatever its matrix work -- config 5b's
+    // groups of 11: 4.07 / 4.54 us per time step against 2.71 / 3.38 (profiles/r06c_time_sweeps.txt).  From H = 1024 on
+    // (profiles/r06e_sparse_single_set.txt): LSTM-1280, 8 clips per group 2.62 / 2.88 against 2.70 / 3.01 us per time step dense;
+    // GRU-768 equal; LSTM-512 forward 1.93 against 1.69 (two k-blocks per wave leave nothing to overlap)
+    pl.sparse = ns <= 8 && H >= 1024 && inst3(cell, H, 1);
+    pl.nset = ns <= 16 ? 1 : ns <= 32 ? 2 : 0;
     if (pl.gpd >= 1 && pl.nset && inst3(cell, H, 0)) {
       pl.family = 3;
       pl.NG = pl.gpd * D;
@@ -239,7 +239,7 @@ RArgs rargs(const Sweep& s, const Plan& pl) {
   ra.q = qargs(s, pl);
   ra.xcc = (u64*)((char*)s.ws + AUX_BYTES + pl.xbuf(s.bwd));
   ra.P = pl.P, ra.xmap = pl.xmap, ra.gx = pl.gx, ra.nset = pl.nset, ra.sparse = pl.sparse;
-  ra.skip = (pl.nset == 2 && !(variant_of(s.opts) & 2u)) ? 1 : 0;
+  ra.skip = pl.nset == 2;
   probe_hooks(ra, s, pl);
   return ra;
 }
@@ -309,7 +309,7 @@ int ds2_rnn_persist_fwd(int dtype, int cell, int D, int N, int H, int Tp, const 
   if (pl.family <= 2) {
     PArgs a = pargs(s, pl);
     inputs(a);
-    return launch1_any(false, cell, H, a, s.st, (variant_of(opts) & 32u) != 0);   // bit 5: the 8-clip kernels on dense products
+    return launch1_any(false, cell, H, a, s.st);
   }
   if (pl.family == 4) {
     QArgs a = qargs(s, pl);
@@ -341,7 +341,7 @@ int ds2_rnn_persist_bwd(int dtype, int cell, int D, int N, int H, int Tp, const 
   if (pl.family <= 2) {
     PArgs a = pargs(s, pl);
     gradients(a);
-    return launch1_any(true, cell, H, a, s.st, (variant_of(opts) & 32u) != 0);
+    return launch1_any(true, cell, H, a, s.st);
   }
   if (pl.family == 4) {
     QArgs a = qargs(s, pl);

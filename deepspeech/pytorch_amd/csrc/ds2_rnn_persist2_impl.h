@@ -354,9 +354,6 @@ __device__ __forceinline__ float2 load_partials_q4b(const float* part, int row, 
   }
   return s;
 }
-#ifndef DS2Q_Q4
-#define DS2Q_Q4 1        // 0: the 16x16x4 form everywhere (round 5), for A/B runs
-#endif
 
 // ---- payload-only exchange (MT >= 2, bf16): the large-batch regime is bound by the gathered BYTES (a workgroup reads N_s x K
 // values per step through one CU's vector-memory path), so the granule tags are dropped: payload = plain bf16 in A-fragment order
@@ -515,7 +512,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist2_fwd(QArgs a) {
   constexpr int PAR_BYTES = KT * MT * (FLAGS ? 1024 : 2048);   // one slot (payload-only) / one parity (tagged granules)
   static_assert(H % KSZ == 0 && H % 16 == 0, "unsupported hidden size");
   // fp32, <= 4 samples per group, GRU / LSTM: the 4x4x1 broadcast form (gather_mma2_q4); tanh cells would use 16 of its 64 unit slots
-  constexpr bool Q4 = DS2Q_Q4 && std::is_same<T, float>::value && MT == 1 && SP == 4 && G >= 3;
+  constexpr bool Q4 = std::is_same<T, float>::value && MT == 1 && SP == 4 && G >= 3;
   extern __shared__ __attribute__((aligned(16))) float part[];       // [2][4][MT][RT][256]
   constexpr int PART_FLOATS = 4 * MT * RT * 256;
   __builtin_amdgcn_s_setprio(3);
@@ -765,7 +762,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist2_bwd(QArgs a) {
   static_assert(H % KSZ == 0 && H % 16 == 0, "unsupported hidden size");
   extern __shared__ __attribute__((aligned(16))) float part[];       // [2][4][MT][1][256]
   constexpr int PART_FLOATS = 4 * MT * RT * 256;
-  constexpr bool Q4 = DS2Q_Q4 && std::is_same<T, float>::value && MT == 1 && SP == 4 && G >= 3;   // see gather_mma2_q4
+  constexpr bool Q4 = std::is_same<T, float>::value && MT == 1 && SP == 4 && G >= 3;   // see gather_mma2_q4
   __builtin_amdgcn_s_setprio(3);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // scalar: wave-uniform predicates
   const int grp = blockIdx.x % a.NG, p = blockIdx.x / a.NG;

@@ -38,7 +38,7 @@ struct RArgs {
   int nset;      // sample sets per group (the kernel's NSET)
   int skip;      // 1: a set executes only the time steps at which one of its clips is inside its sequence (the caller zeroes the
                  // padding rows of the outputs: they are no longer written for the steps left out)
-  int sparse;    // 1: sets of <= 8 clips on the structured-sparse products (Gather3S); 0: dense 16-row tiles
+  int sparse;    // 1: one set of <= 8 clips on the structured-sparse products (Gather3S); 0: dense 16-row tiles
 #ifdef DS2_PROBE   // tools/probe_persist3.py builds its own library with -DDS2_PROBE; the shipping kernels carry none of it
   unsigned long long* dbg;  // [NG][8] cycle counters of workgroup 0 of each group (thread 0 and thread 255)
   int dbgmask;              // 1 skip GI / dOut / S prefetch loads, 2 skip output stores, 8 skip the gather + products (no exchange),
@@ -51,14 +51,6 @@ struct RArgs {
 // tiles per k-step): the tiles t >= TR of EVERY k-step, so that each k-step's few LDS reads hide under the register tiles' MFMAs.
 // BPTT kernels (RT = 2): whole k-steps, spread evenly: k-step k is LDS-resident iff bit (k % 10) of kmask is set.  PB = partial-sum
 // buffers (2: one barrier per half-step; 1: a second barrier in front of the stores, when LDS is short).
-// Compile-time ablations for tools/ab_variants.py (-DDS2R_VAR=<bits>, timing only -- results are wrong): the DS2_PERSIST_DBG bits of
-// the probe build (1 no prefetch loads of the gate operands, 2 no output stores, 8 no gather and no products, 32 no products with the
-// LDS-resident fragments, 128 gather but no products) plus 256 no gate math (every frame treated as inactive) and 512 no gather loads
-// (products on zeros) -- without the probe build's counters and run-time branches, i.e. in the shipping kernels' own schedule.
-#ifndef DS2R_VAR
-#define DS2R_VAR 0
-#endif
-
 struct Plan3 {
   int TR;
   unsigned kmask;
@@ -159,85 +151,9 @@ __device__ __forceinline__ void pub32(char* p, uint32_t v, bool local) {
   else
     __hip_atomic_store((uint32_t*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-// A/B VARIANT (-DDS2R_QUAD_STORES), measured and not kept: the four lanes of a quad (tid & 3 = dw) hold four CONSECUTIVE dwords of a
-// sample row -- in the exchange slot and in every stored plane.  quad_gather() collects them on every lane (meaningful on the quad's
-// lane 0), so that lane 0 issues ONE 16-byte store where four lanes issued four 4-byte ones.  Fewer active lanes per store, but three
-// DPP moves per stored dword in front of the publish: config 5a 108.1 vs 106.2 ms with plain dword stores, 5b 58.0 vs 57.7
-// (profiles/r04g_ab_dword_stores_*.txt); the same idea loses 3 % in the tuned H = 1024 kernels (r04f_ab_quad_stores_cfg3.txt).
-// Without the flag quad_gather() is the identity on element 0 and every lane stores its own dword.
-__device__ __forceinline__ u32x4_t quad_gather(uint32_t v) {
-  u32x4_t r;
-  r[0] = v;
-#ifndef DS2R_QUAD_STORES
-  r[1] = r[2] = r[3] = 0u;
-  return r;
-#endif
-  r[1] = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x55 /* quad_perm [1,1,1,1] */, 0xf, 0xf, true);
-  r[2] = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xAA /* quad_perm [2,2,2,2] */, 0xf, 0xf, true);
-  r[3] = (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0xFF /* quad_perm [3,3,3,3] */, 0xf, 0xf, true);
-  return r;
-}
-// 16-byte publish into the group's exchange buffer (byte offset `off` inside the resource): plain policy inside one XCD, write-through
-// (sc1) across XCDs.  Dwords are what the protocol looks at (sentinel or data), so a 16-byte store need not be atomic as a whole.
-__device__ __forceinline__ void pub128(__amdgpu_buffer_rsrc_t rsrc, int off, u32x4_t v, bool local) {
-  if (local)
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 0);
-  else
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 16 /* sc1 */);
-}
-__device__ __forceinline__ void st128(bf16_t* p, u32x4_t v) { *reinterpret_cast<u32x4_t*>(p) = v; }
-
 __device__ __forceinline__ uint32_t pay_word(float a, float b) {
   const uint32_t pk = cvt_pk_bf16(a, b);
   return pk == XSENT2 ? 0x7fc07fc0u : pk;
-}
-
-// EXPERIMENT, OFF BY DEFAULT (-DDS2R_ASM_MFMA; measured and rejected in round 4: cfg5a 111 -> 104 ms, cfg5b 58.6 -> 57.0, but WRONG
-// RESULTS on every shape whose MFMAs are not separated by LDS reads -- 15 of 32 kernel tests -- although the instruction itself is
-// fine: tools/_build/mfma_asm_test.hip reproduces the builtin bit for bit with B in AGPRs.  The compiler cannot see that an asm
-// statement is an MFMA, so it re-uses source registers inside the few cycles in which the matrix pipe still reads them; keeping the
-// fragments live across a pad was not enough).  What it is:
-// MFMA with the B fragment read STRAIGHT from an accumulation register (AGPR).  These kernels hold 400-490 registers per lane, so the
-// compiler parks the resident W fragments in AGPRs -- and, through the builtin, copies every one of them into VGPRs in front of its
-// MFMA (4 x v_accvgpr_read_b32: 240 extra VALU-slot instructions per forward half-step at LSTM-1280, as many issue cycles as the
-// MFMAs' own pipe time).  gfx950's MFMA takes srcB from the AGPR file directly; the builtin never asks for it, inline asm does.
-// The compiler does not see an MFMA in the asm, so it pads no hazards: accumulators are reused at a distance of >= 4 MFMAs (> the 18
-// wait states any XDL result needs), and mfma_results_ready() -- an asm statement every accumulator passes through -- holds the 18
-// wait states between the last MFMA and the first reader of its result.
-__device__ __forceinline__ void mfma_breg(ds2_f32x4& acc, const uint4& a, const uint4& b) {       // b: register-resident fragment
-#ifndef DS2R_ASM_MFMA
-  Mma<bf16_t>::mma16(acc, a, b);
-  return;
-#endif
-  const u32x4_t av = __builtin_bit_cast(u32x4_t, a), bv = __builtin_bit_cast(u32x4_t, b);
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(av), "a"(bv));
-}
-__device__ __forceinline__ void mfma_bvgpr(ds2_f32x4& acc, const uint4& a, const uint4& b) {      // b: staged from LDS
-#ifndef DS2R_ASM_MFMA
-  Mma<bf16_t>::mma16(acc, a, b);
-  return;
-#endif
-  const u32x4_t av = __builtin_bit_cast(u32x4_t, a), bv = __builtin_bit_cast(u32x4_t, b);
-  asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(acc) : "v"(av), "v"(bv));
-}
-#ifndef DS2R_READY_PAD
-#define DS2R_READY_PAD "s_nop 15\n\ts_nop 3"
-#endif
-template <int NA>
-__device__ __forceinline__ void mfma_results_ready(ds2_f32x4 (&acc)[NA]) {
-  static_assert(NA == 2 || NA == 4 || NA == 6 || NA == 8, "accumulator count");
-#ifndef DS2R_ASM_MFMA
-  return;
-#endif
-  if constexpr (NA == 2)
-    asm volatile(DS2R_READY_PAD : "+v"(acc[0]), "+v"(acc[1]));
-  else if constexpr (NA == 4)
-    asm volatile(DS2R_READY_PAD : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]));
-  else if constexpr (NA == 6)
-    asm volatile(DS2R_READY_PAD : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]));
-  else
-    asm volatile(DS2R_READY_PAD : "+v"(acc[0]), "+v"(acc[1]), "+v"(acc[2]), "+v"(acc[3]), "+v"(acc[4]), "+v"(acc[5]), "+v"(acc[6]),
-                 "+v"(acc[7]));
 }
 
 // Resident weight fragments beyond what the vector registers hold: these kernels keep 56-60 B fragments (224-240 registers) per lane
@@ -325,14 +241,7 @@ struct Gather3 {
       int voff = k_ok ? lane_off : XOOB;
       if (SP == 2 && k0 + 1 >= KSW) voff = part ? XOOB : voff;         // odd K-quarter: the second lane part has no k-step here
       if (SP == 2 && RAGGED) voff = (part && k0 + 1 >= cnt) ? XOOB : voff;
-      if (DS2R_VAR & 512)
-        v[b][i] = u32x4_t{0u, 0u, 0u, 0u};
-      else
-#ifdef DS2R_NO_SOFF
-        v[b][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff == XOOB ? XOOB : voff + soff, 0, 16 /* sc1 */);
-#else
-        v[b][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 16 /* sc1 */);
-#endif
+      v[b][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 16 /* sc1 */);
     }
   }
   __device__ __forceinline__ bool bad(int b) const {
@@ -354,9 +263,8 @@ struct Gather3 {
       if (kk < CH) lds_kstep(kk % (LA + 1), c * CH + kk, wl_lane);
   }
   static constexpr int NACC = BWD ? 2 * RT : RT;     // BPTT (two tiles): even and odd k-steps accumulate apart, so that an accumulator is
-                                                     // reused every 4th MFMA at the earliest (see mfma_breg)
+                                                     // reused every 4th MFMA at the earliest
   __device__ __forceinline__ void mma(int b, int c, ds2_f32x4 (&acc)[NACC], const WArr& w, const uint4* wl_lane, int dbgmask) {
-    u32x4_t rot[SP == 2 ? PER : 1];     // SP == 2: the rotated fragments of the odd k-steps
 #pragma unroll
     for (int kk = 0; kk < CH; ++kk) {
       const int k_ = c * CH + kk;                    // compile-time after unrolling
@@ -364,41 +272,23 @@ struct Gather3 {
       if (k_ < KSW && !(dbgmask & 128)) {
         const int i = kk / SP;
         uint4 a_ = make_uint4(v[b][i][0], v[b][i][1], v[b][i][2], v[b][i][3]);
-        if (SP == 2 && (kk & 1)) {
-          a_ = row_from_plus4(a_, 8);
-          rot[i] = u32x4_t{a_.x, a_.y, a_.z, a_.w};
-          a_ = make_uint4(rot[i][0], rot[i][1], rot[i][2], rot[i][3]);
-        }
+        if (SP == 2 && (kk & 1)) a_ = row_from_plus4(a_, 8);     // the fragment of an odd k-step, rotated into place
 #pragma unroll
         for (int t = 0; t < RT; ++t) {
           ds2_f32x4& ac = acc[BWD ? t + RT * (k_ & 1) : t];
           if (in_lds3(TR, KM, t, k_)) {
             const uint4 wv = st[kk % (LA + 1)][lds_tile3(TR, KM, t, k_)];
-            if (!(dbgmask & 32)) mfma_bvgpr(ac, a_, wv);
+            if (!(dbgmask & 32)) Mma<bf16_t>::mma16(ac, a_, wv);
           } else {
-            mfma_breg(ac, a_, w[t][k_]);
+            Mma<bf16_t>::mma16(ac, a_, w[t][k_]);
           }
         }
       }
     }
-#ifdef DS2R_ASM_MFMA
-    // The compiler does not know that the asm statements above are MFMAs whose source registers are still being read for a few
-    // cycles after issue: left alone it re-uses an A-fragment register for the next VALU result right behind the last MFMA (the
-    // sentinel check's v_max landed in the fragment of the last k-step: wrong sums on every shape without LDS reads in between).
-    // So the chunk's fragments stay live across a pad behind the block.
-    asm volatile("s_nop 15\n\ts_nop 3");
-#pragma unroll
-    for (int i = 0; i < PER; ++i) asm volatile("" : : "v"(v[b][i]));
-    if (SP == 2) {
-#pragma unroll
-      for (int i = 0; i < PER; ++i)
-        if ((c * CH + SP * i + 1) < KSW && !(dbgmask & 128)) asm volatile("" : : "v"(rot[i]));
-    }
-#endif
   }
 };
 
-// ---- Structured-sparse form (round 6): sets of <= 8 clips on all 16 tile rows ---------------------------------------------------
+// ---- Structured-sparse form (round 6): one set of <= 8 clips on all 16 tile rows ---------------------------------------------------
 // What ds2_rnn_persist_impl.h does for config 3 (see smma16 there), in the general kernels: tile rows s and s + 8 both belong to clip
 // s -- row s carries its k = 0, 1 (mod 4) elements, row s + 8 its k = 2, 3 (mod 4) ones, so every row is 2:4-sparse by construction --
 // and v_smfmac_f32_16x16x64_bf16 multiplies a k-BLOCK of 64 at the cost of a dense k-step of 32: half the matrix instructions for a
@@ -443,10 +333,7 @@ struct Gather3S {
       const bool ok = u < KB;
       const int soff = __builtin_amdgcn_readfirstlane(ok ? (ks0 / 2 + u) * 1024 : 0);
       const int voff = ok ? lane_off : XOOB;
-      if (DS2R_VAR & 512)
-        v[b][i] = u32x4_t{0u, 0u, 0u, 0u};
-      else
-        v[b][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 16 /* sc1 */);
+      v[b][i] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 16 /* sc1 */);
     }
   }
   __device__ __forceinline__ bool bad(int b) const {
@@ -591,10 +478,10 @@ __device__ __forceinline__ float2 load_partials3(const float* part, int t, int r
 // same for 6 rows as for 16: it is a latency chain).  sched3: the step range [lo, hi) of the sweep's step counter s in which set q has a clip inside its
 // sequence, for a sweep that visits t = s (ascending = true) or t = T' - 1 - s (false): outside it the set's half-steps are not
 // executed at all -- no gather, no products, no publish (the carried state of every clip is its initial one there).
-template <int NSET, int CAP = 16>
+template <int NSET>
 __device__ __forceinline__ void sched3(const int* lens, int slice, int gpd, int Ns, int Tp, bool ascending, bool skip, int (&lo)[NSET],
                                        int (&hi)[NSET], int& RPS) {
-  RPS = NSET == 1 ? Ns : min(CAP, Ns);
+  RPS = NSET == 1 ? Ns : min(16, Ns);
 #pragma unroll
   for (int q = 0; q < NSET; ++q) {
     int mx = 0;
@@ -636,7 +523,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_fwd(RArgs ra) {
   constexpr int SLOT = KT * 1024, SETB = 4 * SLOT;       // bytes of one slot / of one set's four slots (SS uses the first half of a slot)
   static_assert(H % 32 == 0 && PL.ok, "unsupported hidden size");
   static_assert(SP == 1 || NSET == 1, "lane sharing is instantiated for single-set groups only");
-  static_assert(!SS || (SP == 1 && KT % 8 == 0), "structured-sparse sets: whole k-blocks per wave, no lane sharing");
+  static_assert(!SS || (NSET == 1 && SP == 1 && KT % 8 == 0), "one structured-sparse set: whole k-blocks per wave, no lane sharing");
   typedef typename std::conditional<SS, Gather3S<RT, KSW, false>, Gather3<RT, KSW, SP, RAGGED, false>>::type GX;
   extern __shared__ __attribute__((aligned(16))) uint4 smem3[];
   uint4* wl = smem3;                                                   // [LDS-resident fragment][4 waves][64 lanes]
@@ -682,7 +569,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_fwd(RArgs ra) {
   const int gbase = lq * 256 + srow * 16;
   int lo[NSET], hi[NSET], RPS;
   const bool asc = d == 0;                              // the sweep's step s visits t = s (else t = T' - 1 - s)
-  sched3<NSET, SS ? 8 : 16>(a.lens, slice, a.gpd, Ns, Tp, asc, (ra.skip & 1) != 0, lo, hi, RPS);
+  sched3<NSET>(a.lens, slice, a.gpd, Ns, Tp, asc, (ra.skip & 1) != 0, lo, hi, RPS);
   int glen[NSET];
 #pragma unroll
   for (int q = 0; q < NSET; ++q)
@@ -766,7 +653,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_fwd(RArgs ra) {
   unsigned rounds = 0;
   DS2_PROBE_ONLY(unsigned long long c_gather = 0, c_bar = 0, c_gate = 0; const int dbgmask = ra.dbgmask;)
 #ifndef DS2_PROBE
-  constexpr int dbgmask = DS2R_VAR;
+  constexpr int dbgmask = 0;
 #endif
   const bool plain = local || (dbgmask & 64);
   GX gx;
@@ -791,7 +678,6 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_fwd(RArgs ra) {
 #pragma unroll
       for (int tt = 0; tt < RT; ++tt) acc[tt] = ds2_f32x4{0.f, 0.f, 0.f, 0.f};
       DS2R_GATHER_PHASE(a.h0 != nullptr)
-      mfma_results_ready<RT>(acc);
       {   // this set's input projection DEP steps ahead
 #pragma unroll
         for (int i = 0; i + 1 < DEP; ++i)
@@ -813,7 +699,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_fwd(RArgs ra) {
 #pragma unroll
       for (int m = 0; m < M; ++m) pl[m][0] = pl[m][1] = 0.f;
       if (on[q]) {
-        const bool act = t < len[q] && !(dbgmask & 256);
+        const bool act = t < len[q];
         float2 gh[G];
 #pragma unroll
         for (int g = 0; g < G; ++g) gh[g] = load_partials3<RT, SS>(pp, 2 * g + (jl >> 4), grow, jl & 15);
@@ -866,34 +752,22 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_fwd(RArgs ra) {
         if (dead) hn0 = hn1 = hprev[q][0] = hprev[q][1] = QNAN;   // fail loudly downstream
       }
       {
-        // the quad's four dwords meet on its lane 0 (all lanes active: rows are uniform within a quad), which publishes the carried
-        // state first (inactive samples republish their unchanged state), then re-arms and stores the bookkeeping planes
-        const u32x4_t pubv = quad_gather(pay_word(hprev[q][0], hprev[q][1]));
-        const u32x4_t hsv = quad_gather(cvt_pk_bf16(hn0, hn1));
-        u32x4_t plv[M];
+        // every lane publishes the carried state of its own pair first (inactive samples republish their unchanged state), then
+        // re-arms and stores the bookkeeping planes.  Dword stores: merging a quad's four into one 16-byte store costs three DPP moves
+        // per dword in front of the publish -- config 5a 108.1 vs 106.2 ms, 5b 58.0 vs 57.7 (profiles/r04g_ab_dword_stores_*.txt)
+        const uint32_t pubw = pay_word(hprev[q][0], hprev[q][1]), hsw = cvt_pk_bf16(hn0, hn1);
+        uint32_t plw[M];
 #pragma unroll
-        for (int m = 0; m < M; ++m) plv[m] = quad_gather(cvt_pk_bf16(pl[m][0], pl[m][1]));
-#ifndef DS2R_QUAD_STORES       // A/B variant: every lane stores its own dword (the form before the quad gathers)
+        for (int m = 0; m < M; ++m) plw[m] = cvt_pk_bf16(pl[m][0], pl[m][1]);
         if (on[q]) {
-          pub32(xg + q * SETB + (s & 3) * SLOT + xoff, pubv[0], plain);
-          pub32(xg + q * SETB + ((s + 2) & 3) * SLOT + xoff, XSENT2, plain);
+          pub32(xg + q * SETB + (s & 3) * SLOT + xoff, pubw, plain);
+          pub32(xg + q * SETB + ((s + 2) & 3) * SLOT + xoff, XSENT2, plain);     // re-arm step s + 2's slot
           if (!(dbgmask & 2)) {
-            *reinterpret_cast<uint32_t*>(hs_ptr[q]) = hsv[0];
+            *reinterpret_cast<uint32_t*>(hs_ptr[q]) = hsw;
 #pragma unroll
-            for (int m = 0; m < NS; ++m) *reinterpret_cast<uint32_t*>(sv_ptr[q] + (long)m * H) = plv[m][0];
+            for (int m = 0; m < NS; ++m) *reinterpret_cast<uint32_t*>(sv_ptr[q] + (long)m * H) = plw[m];
           }
         }
-#else
-        if (on[q] && dw == 0) {
-          pub128(rsrc, q * SETB + (s & 3) * SLOT + xoff, pubv, plain);
-          pub128(rsrc, q * SETB + ((s + 2) & 3) * SLOT + xoff, u32x4_t{XSENT2, XSENT2, XSENT2, XSENT2}, plain);   // re-arm step s + 2's slot
-          if (!(dbgmask & 2)) {
-            st128(hs_ptr[q], hsv);
-#pragma unroll
-            for (int m = 0; m < NS; ++m) st128(sv_ptr[q] + (long)m * H, plv[m]);
-          }
-        }
-#endif
       }
       if (NS) sv_ptr[q] += sv_stride;
       hs_ptr[q] += hs_stride;
@@ -946,7 +820,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_bwd(RArgs ra) {
   constexpr int SLOT = KT * 1024, SETB = 4 * SLOT, GATEB = SS ? KTH * 512 : KTH * 1024;   // gate g's k = g * H + j
   static_assert(H % 32 == 0 && PL.ok, "unsupported hidden size");
   static_assert(SP == 1 || NSET == 1, "lane sharing is instantiated for single-set groups only");
-  static_assert(!SS || (SP == 1 && KT % 8 == 0 && H % 64 == 0), "structured-sparse sets: whole k-blocks per wave and gate");
+  static_assert(!SS || (NSET == 1 && SP == 1 && KT % 8 == 0 && H % 64 == 0), "one structured-sparse set: whole k-blocks per wave and gate");
   typedef typename std::conditional<SS, Gather3S<RT, KSW, true>, Gather3<RT, KSW, SP, RAGGED, true>>::type GX;
   extern __shared__ __attribute__((aligned(16))) uint4 smem3[];
   uint4* wl = smem3;
@@ -991,7 +865,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_bwd(RArgs ra) {
   const int gbase = lq * 256 + srow * 16;
   int lo[NSET], hi[NSET], RPS;
   const bool asc = d != 0;                              // BPTT visits t = T' - 1 - s for direction 0
-  sched3<NSET, SS ? 8 : 16>(a.lens, slice, a.gpd, Ns, Tp, asc, (ra.skip & 1) != 0, lo, hi, RPS);
+  sched3<NSET>(a.lens, slice, a.gpd, Ns, Tp, asc, (ra.skip & 1) != 0, lo, hi, RPS);
   int glen[NSET];
 #pragma unroll
   for (int q = 0; q < NSET; ++q)
@@ -1042,7 +916,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_bwd(RArgs ra) {
 
   DS2_PROBE_ONLY(const int dbgmask = ra.dbgmask;)
 #ifndef DS2_PROBE
-  constexpr int dbgmask = DS2R_VAR;
+  constexpr int dbgmask = 0;
 #endif
   // gate-phase operands of a half-step, loaded one half-step ahead (raw pairs)
   struct Pre {
@@ -1103,7 +977,6 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_bwd(RArgs ra) {
         ds2_f32x4 (&acc)[2 * RT] = acc2;
         DS2R_GATHER_PHASE(false)
       }
-      mfma_results_ready<2 * RT>(acc2);
       ds2_f32x4 acc[RT];
 #pragma unroll
       for (int tt = 0; tt < RT; ++tt) acc[tt] = acc2[tt] + acc2[tt + RT];
@@ -1120,7 +993,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_bwd(RArgs ra) {
 #pragma unroll
       for (int g = 0; g < G; ++g) gx[g][0] = gx[g][1] = 0.f;
       if (on[q]) {
-        const bool act = t < len[q] && !(dbgmask & 256);
+        const bool act = t < len[q];
         const float2 mp = load_partials3<RT, SS>(pp, jl >> 4, grow, jl & 15);
         const float din0 = car[q][0] + mp.x, din1 = car[q][1] + mp.y;
         car[q][0] = din0;
@@ -1171,64 +1044,38 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist3_bwd(RArgs ra) {
         if (dead) gx[0][0] = gx[0][1] = QNAN;
       }
       {
-        // packed planes; the quad's four dwords meet on its lane 0 (all lanes active), which publishes, re-arms and stores 16 bytes at
-        // a time; every lane keeps the bias sums of its own pair from the ROUNDED values (= the column sums of the stored planes)
-        uint32_t pk[G];
-#pragma unroll
-        for (int g = 0; g < G; ++g) pk[g] = cvt_pk_bf16(gx[g][0], gx[g][1]);
-        const uint32_t pkn = cvt_pk_bf16(gn[0], gn[1]);
-        u32x4_t pubv[G], stv[G];
+        // packed planes: every lane publishes, re-arms and stores the dwords of its own pair, and keeps the bias sums of that pair
+        // from the ROUNDED values (= the column sums of the stored planes)
+        uint32_t pk[G], pubw[G];     // pubw travels: a pair that would read as the sentinel goes out as two canonical NaNs
 #pragma unroll
         for (int g = 0; g < G; ++g) {
-          stv[g] = quad_gather(pk[g]);
-          pubv[g] = quad_gather(pk[g] == XSENT2 ? 0x7fc07fc0u : pk[g]);
+          pk[g] = cvt_pk_bf16(gx[g][0], gx[g][1]);
+          pubw[g] = pk[g] == XSENT2 ? 0x7fc07fc0u : pk[g];
         }
-        const u32x4_t nv = quad_gather(pkn);
+        const uint32_t pkn = cvt_pk_bf16(gn[0], gn[1]);
+        // Dead on purpose: what is left of the 16-byte merged stores (measured and rejected in round 4, removed).  Without this tuple the
+        // compiler issues 4-6 independent instructions of the 25 single-set GRU kernels in another order -- same instructions, same
+        // registers -- and on one box that form was 0.3-0.6 % off the parent's BPTT time at H = 1280 / 1536, at the edge of the noise
+        // (profiles/prune_device_code.md).  Kept until somebody re-times the kernels without it.
+        const u32x4_t nv = u32x4_t{pkn, 0u, 0u, 0u};
+        (void)nv;
         if (on[q]) {
-#ifndef DS2R_QUAD_STORES
-          {
-            char* xo = xg + q * SETB + (s & 3) * SLOT + xoff;
-            char* xr = xg + q * SETB + ((s + 2) & 3) * SLOT + xoff;
+          char* xo = xg + q * SETB + (s & 3) * SLOT + xoff;
+          char* xr = xg + q * SETB + ((s + 2) & 3) * SLOT + xoff;     // re-armed for step s + 2
 #pragma unroll
-            for (int g = 0; g < G; ++g) pub32(xo + g * GATEB, pubv[g][0], plain);
+          for (int g = 0; g < G; ++g) pub32(xo + g * GATEB, pubw[g], plain);
 #pragma unroll
-            for (int g = 0; g < G; ++g) pub32(xr + g * GATEB, XSENT2, plain);
-            if (!(dbgmask & 2)) {
-              bf16_t* dgi = dgi_ptr[q];
-              if (CELL == CELL_GRU) {
-                *reinterpret_cast<uint32_t*>(dgi) = pk[0];
-                *reinterpret_cast<uint32_t*>(dgi + H) = pk[1 % G];
-                *reinterpret_cast<uint32_t*>(dgi + 2 * H) = pkn;
-                *reinterpret_cast<uint32_t*>(dgh_ptr[q]) = pk[2 % G];
-              } else {
+          for (int g = 0; g < G; ++g) pub32(xr + g * GATEB, XSENT2, plain);
+          if (!(dbgmask & 2)) {
+            bf16_t* dgi = dgi_ptr[q];
+            if (CELL == CELL_GRU) {
+              *reinterpret_cast<uint32_t*>(dgi) = pk[0];
+              *reinterpret_cast<uint32_t*>(dgi + H) = pk[1 % G];
+              *reinterpret_cast<uint32_t*>(dgi + 2 * H) = pkn;
+              *reinterpret_cast<uint32_t*>(dgh_ptr[q]) = pk[2 % G];
+            } else {
 #pragma unroll
-                for (int g = 0; g < G; ++g) *reinterpret_cast<uint32_t*>(dgi + (long)g * H) = pk[g];
-              }
-            }
-          }
-          if (false) {
-            const int xo = 0, xr = 0;
-#pragma unroll
-            for (int g = 0; g < G; ++g) pub128(rsrc, xo + g * GATEB, pubv[g], plain);
-#else
-          if (dw == 0) {
-            const int xo = q * SETB + (s & 3) * SLOT + xoff, xr = q * SETB + ((s + 2) & 3) * SLOT + xoff;   // xr: re-armed for step s + 2
-#pragma unroll
-            for (int g = 0; g < G; ++g) pub128(rsrc, xo + g * GATEB, pubv[g], plain);
-#endif
-#pragma unroll
-            for (int g = 0; g < G; ++g) pub128(rsrc, xr + g * GATEB, u32x4_t{XSENT2, XSENT2, XSENT2, XSENT2}, plain);
-            if (!(dbgmask & 2)) {
-              bf16_t* dgi = dgi_ptr[q];
-              if (CELL == CELL_GRU) {     // dGI = [dr, dz, dn], dQ apart
-                st128(dgi, stv[0]);
-                st128(dgi + H, stv[1 % G]);
-                st128(dgi + 2 * H, nv);
-                st128(dgh_ptr[q], stv[2 % G]);
-              } else {
-#pragma unroll
-                for (int g = 0; g < G; ++g) st128(dgi + (long)g * H, stv[g]);
-              }
+              for (int g = 0; g < G; ++g) *reinterpret_cast<uint32_t*>(dgi + (long)g * H) = pk[g];
             }
           }
           if (CELL == CELL_GRU) {
@@ -1279,11 +1126,12 @@ constexpr bool covered3() {
   return H % 32 == 0 && plan3(2 * G, (H / 32 + 3) / 4).ok && plan3(2, (G * H / 32 + 3) / 4).ok;
 }
 
-// Structured-sparse sets (Gather3S): every wave's K-quarter is a whole number of k-blocks of 64, forward (K = H) and BPTT (K = G * H)
+// The structured-sparse set (Gather3S): every wave's K-quarter is a whole number of k-blocks of 64, forward (K = H) and BPTT
+// (K = G * H); from H = 1024 on, below that the dense tiles are as fast or faster (see plan() in ds2_rnn_persist.hip)
 template <int CELL, int H>
 constexpr bool sparse3() {
   constexpr int G = CellInfo<CELL>::G;
-  return H % 256 == 0 && covered3<CELL, H>() && plan3(2 * G, H / 128, 1).ok && plan3(2, G * H / 128, 1).ok;
+  return H >= 1024 && H % 256 == 0 && covered3<CELL, H>() && plan3(2 * G, H / 128, 1).ok && plan3(2, G * H / 128, 1).ok;
 }
 
 template <int CELL, int H, int NSET, int SP, bool SS = false>
@@ -1306,18 +1154,15 @@ int launch3_one(bool bwd, const RArgs& ra, hipStream_t st) {
   }
 }
 
-// nset = sample sets (1 or 2).  ra.sparse (the host's choice for groups of <= 16 clips at the widths sparse3 covers): sets of <= 8 clips
-// on the structured-sparse products; otherwise single-set groups of <= 8 samples share the gather loads between lane pairs (SP = 2).
+// nset = sample sets (1 or 2).  ra.sparse (the host's choice for groups of <= 8 clips at the widths sparse3 covers): ONE set on the
+// structured-sparse products; otherwise single-set groups of <= 8 samples share the gather loads between lane pairs (SP = 2).
 // probe: is the combination instantiated?
 template <int CELL, int H>
 int launch3(bool probe, bool bwd, const RArgs& ra, hipStream_t st) {
   if (!covered3<CELL, H>()) return DS2_ERR_ARG;
   if (probe) return (!ra.sparse || sparse3<CELL, H>()) ? 0 : DS2_ERR_ARG;
   const int ns = (ra.q.N + ra.q.gpd - 1) / ra.q.gpd;
-  if (ra.sparse) {
-    if (ra.nset == 2) return launch3_one<CELL, H, 2, 1, true>(bwd, ra, st);
-    return launch3_one<CELL, H, 1, 1, true>(bwd, ra, st);
-  }
+  if (ra.sparse) return launch3_one<CELL, H, 1, 1, true>(bwd, ra, st);
   if (ra.nset == 2) return launch3_one<CELL, H, 2, 1>(bwd, ra, st);
   if (ns <= 8) return launch3_one<CELL, H, 1, 2>(bwd, ra, st);
   return launch3_one<CELL, H, 1, 1>(bwd, ra, st);

@@ -223,12 +223,9 @@ __device__ __forceinline__ uint32_t ror8(uint32_t v) {   // lane i <- lane i^8 w
 constexpr int L2_AHEAD = DS2_L2_AHEAD;
 // A/B knobs of the 8-clip sweeps (tools/ab_sweeps.py, profiles/r05h_ab_sweep_timing.txt).  Forward: the input-projection loads of
 // step s + 1 are issued at the END of step s (behind the publish, raw 16-bit values converted after the next gather) and a short pause
-// stands in front of the gather where their wait used to pace it: GRU 1.345 -> 1.315-1.32 us per time step with a pause of 2-3 (no
-// pause: 1.37-1.39, re-polls; 6: 1.38), LSTM unchanged.  BPTT: a pause in front of the gather costs its own length (1 / 2 / 4:
+// (DS2_FWD_SLEEP) stands in front of the gather where their wait used to pace it: GRU 1.345 -> 1.315-1.32 us per time step with a pause
+// of 2-3 (no pause: 1.37-1.39, re-polls; 6: 1.38), LSTM unchanged.  BPTT: a pause in front of the gather costs its own length (1 / 2 / 4:
 // +0.00 / +0.03 / +0.07 us per step).
-#ifndef DS2_FWD_GI_AHEAD
-#define DS2_FWD_GI_AHEAD 1
-#endif
 #ifndef DS2_FWD_SLEEP
 #define DS2_FWD_SLEEP 2
 #endif
@@ -369,9 +366,8 @@ __device__ __forceinline__ void gather_mma(ds2_f32x4 (&acc)[TILES], const uint4 
 // ------------------------------------------------------------------------------------------------------------------
 // Tag-free exchange (groups of <= 8 samples: k_rnn_persist_fwd4 / bwd4).  The tagged granules spend half of every gathered byte
 // -- and half of the load instructions, which is what a step is priced in -- on tags.  Here the payload alone travels:
-//   * the buffer is FOUR slots (step e publishes into slot e & 3), each in MFMA A-fragment order
-//     [k-step][lq (4)][sample row (8)] x 16 bytes = the 8 bf16 k-values 32*kstep + 8*lq .. +7 of one row: ONE 16-byte load is
-//     one A fragment;
+//   * the buffer is FOUR slots (step e publishes into slot e & 3), each in the order of the (structured-sparse, see below) MFMA
+//     A fragments: ONE 16-byte load is one A fragment;
 //   * "not there yet" is the dword 0xFFFFFFFF (two bf16 NaNs with all mantissa bits set, which no published pair is: a pair
 //     that would be is published as two canonical NaNs).  The host fills the buffer with 0xFF bytes; a dword is written by
 //     exactly one thread with one 4-byte store, so it is either the sentinel or complete data;
@@ -392,12 +388,6 @@ constexpr int chunk_ksteps_tf(int KS) {
   // round 3 (nothing co-resident any more, L2-warm operands): 24 in one chunk again -- 2.19 us per BPTT step against 1.81-1.95 with 12
   return KS <= 8 ? KS : (KS % 12 == 0 ? 12 : 8);
 #endif
-}
-__device__ __forceinline__ int xtf_unit_bytes(int kstep, int lq, int row) { return ((kstep * 4 + lq) * 8 + row) * 16; }
-// byte offset of the dword that carries elements (k, k+1), k even, of sample row `row`
-__device__ __forceinline__ int xtf_pair_bytes(int k, int row) {
-  const int kk = k & 31;
-  return xtf_unit_bytes(k >> 5, kk >> 3, row) + ((kk & 7) >> 1) * 4;
 }
 __device__ __forceinline__ uint32_t xtf_word(uint32_t pk) { return pk == XSENT ? 0x7fc07fc0u : pk; }
 __device__ __forceinline__ void publish32(void* p, uint32_t v, bool local) {
@@ -434,22 +424,6 @@ __device__ __forceinline__ ds2_f32x4 zero_in_vgprs() {
   asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\tv_mov_b32 %3, 0" : "=v"(z[0]), "=v"(z[1]), "=v"(z[2]), "=v"(z[3]));
   return z;
 }
-// A/B VARIANT (-DDS2_PREADD, round 6; measured and not kept, profiles/r06g_ab_preadd.txt): the two tile rows of a clip (lanes l and
-// l + 32 of an accumulator register) are added BEFORE the partial sums go to LDS -- one v_permlane32_swap + one add per register, 24
-// of each per wave and forward step -- so that a gate thread reads 4 instead of 8 partial sums per gate.
-#ifndef DS2_PREADD
-#define DS2_PREADD 0
-#endif
-template <int TILES>
-__device__ __forceinline__ void preadd_rows(ds2_f32x4 (&acc)[TILES]) {
-#pragma unroll
-  for (int t = 0; t < TILES; ++t)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(acc[t][r]), __float_as_uint(acc[t][r]), false, false);
-      acc[t][r] = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
-    }
-}
 __device__ __forceinline__ void smma16(ds2_f32x4& acc, const uint4& a, const uint4& b0, const uint4& b1, int idx) {
   struct {
     uint4 lo, hi;
@@ -457,39 +431,14 @@ __device__ __forceinline__ void smma16(ds2_f32x4& acc, const uint4& a, const uin
   acc = __builtin_amdgcn_smfmac_f32_16x16x64_bf16(__builtin_bit_cast(ds2_bf16x8, a), __builtin_bit_cast(ds2_bf16x16, bb), acc, idx, 0, 0);
 }
 
-// ---- 16-byte merged stores of the 8-samples-per-group kernels (-DDS2_QUAD_STORES: an A/B variant) ---------------------------------
-// The even lanes 8m, 8m+2, 8m+4, 8m+6 of a wave hold four CONSECUTIVE dwords of one sample row -- in the exchange slot and in every
-// stored plane (thread bits: e, pair within the 16-byte unit (2), sample row (3), lq (2)).  row4() collects them on lane 8m, which then
-// issues ONE 16-byte store where four lanes issued four 4-byte ones (8 instead of 32 active lanes per store instruction).
-typedef __attribute__((ext_vector_type(4))) unsigned int u32x4q;
-template <int N>
-__device__ __forceinline__ uint32_t row_plus(uint32_t v) {      // lane i of every 16-lane row <- lane (i + N) mod 16
-  return (uint32_t)__builtin_amdgcn_mov_dpp((int)v, 0x120 + (16 - N), 0xf, 0xf, true);
-}
-__device__ __forceinline__ u32x4q row4(uint32_t v) {
-  u32x4q r;
-  r[0] = v;
-  r[1] = row_plus<2>(v);
-  r[2] = row_plus<4>(v);
-  r[3] = row_plus<6>(v);
-  return r;
-}
-__device__ __forceinline__ void publish128(__amdgpu_buffer_rsrc_t rsrc, int off, u32x4q v, bool local) {
-  if (local)
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 2 /* nt: plain policy, the line stays in this XCD's L2 */);
-  else
-    __builtin_amdgcn_raw_buffer_store_b128(v, rsrc, off, 0, 16 /* sc1: write-through */);
-}
-
-// SP: the structured-sparse form (see smma16): srow = the lane's tile row (0..15), `half` is unused, w[t][2*kb], w[t][2*kb + 1] (the
-// dense fragments of k-steps 2*kb, 2*kb + 1) are the B operand of k-block kb, `spidx` the lane's index word.
-template <int TILES, int KS, bool SP = false, typename F = NoTouch>
+// The tag-free gather on the structured-sparse products (see smma16): srow = the lane's tile row (0..15), w[t][2*kb], w[t][2*kb + 1]
+// (the dense fragments of k-steps 2*kb, 2*kb + 1) are the B operand of k-block kb, `spidx` the lane's index word.
+template <int TILES, int KS, typename F = NoTouch>
 __device__ __forceinline__ void gather_mma_tf(ds2_f32x4 (&acc)[TILES], const uint4 (&w)[TILES][KS], __amdgpu_buffer_rsrc_t rsrc,
-                                              int slot_off, int kstep0, int lq, int srow, int half, bool need, int* err, int* lerr,
-                                              bool& dead, unsigned& rounds, F after_issue = F(), int spidx = 0) {
+                                              int slot_off, int kstep0, int lq, int srow, bool need, int* err, int* lerr,
+                                              bool& dead, unsigned& rounds, F after_issue, int spidx) {
   constexpr int CH = chunk_ksteps_tf(KS);
-  constexpr int PER = CH / 2;       // loads of a lane per chunk: half of the chunk's k-steps (the other half arrives by the DPP row
-                                    // rotate), or (SP) its fragment of each of the chunk's CH / 2 k-blocks
+  constexpr int PER = CH / 2;       // loads of a lane per chunk: its fragment of each of the chunk's CH / 2 k-blocks
   static_assert(KS % CH == 0 && CH % 2 == 0, "k-steps per wave must tile into poll chunks");
   typedef __attribute__((ext_vector_type(4))) unsigned int u32x4;
 #pragma unroll
@@ -503,27 +452,17 @@ __device__ __forceinline__ void gather_mma_tf(ds2_f32x4 (&acc)[TILES], const uin
     // fewer VALU instructions per BPTT step, and 1.34 / 1.65 instead of 1.29 / 1.56 us per time step, profiles/r05h_ab_sweep_timing.txt)
 #define DS2_TF_LOAD(FIRST)                                                                                             \
     _Pragma("unroll") for (int i = 0; i < PER; ++i) v[i] = __builtin_amdgcn_raw_buffer_load_b128(                      \
-        rsrc, need ? slot_off + (SP ? xsp_unit_bytes((kstep0 + c * CH) / 2 + i, lq, srow)                              \
-                                    : xtf_unit_bytes(kstep0 + c * CH + half * PER + i, lq, srow)) : 0x7ffffff0, 0, 16 /* sc1 */); \
+        rsrc, need ? slot_off + xsp_unit_bytes((kstep0 + c * CH) / 2 + i, lq, srow) : 0x7ffffff0, 0, 16 /* sc1 */);    \
     if (FIRST && c == 0 && !std::is_same<F, NoTouch>::value) {                                                         \
       after_issue();                     /* scalar work that hides under the first round trip (l2_touch) */            \
       __builtin_amdgcn_sched_barrier(0); /* nothing that waits for the loads may be scheduled above it   */            \
     }
 #define DS2_TF_MMA()                                                                                                   \
-    _Pragma("unroll") for (int t = 0; t < TILES; ++t) part[t] = (SP && KS != CH) ? zero_in_vgprs() : ds2_f32x4{0.f, 0.f, 0.f, 0.f}; \
-    if (SP) {                                                                                                          \
-      _Pragma("unroll") for (int i = 0; i < PER; ++i) {                                                                \
-        const uint4 a = make_uint4(v[i][0], v[i][1], v[i][2], v[i][3]);                                                \
-        _Pragma("unroll") for (int t = 0; t < TILES; ++t)                                                              \
-            smma16(part[t], a, w[t][c * CH + 2 * i], w[t][c * CH + 2 * i + 1], spidx);                                 \
-      }                                                                                                                \
-    } else {                                                                                                           \
-      _Pragma("unroll") for (int k = 0; k < CH; ++k) {                                                                 \
-        const int i = k % PER;                                                                                         \
-        uint4 a = make_uint4(v[i][0], v[i][1], v[i][2], v[i][3]);                                                      \
-        if (k >= PER) a = make_uint4(ror8(a.x), ror8(a.y), ror8(a.z), ror8(a.w));                                      \
-        _Pragma("unroll") for (int t = 0; t < TILES; ++t) Mma<bf16_t>::mma16(part[t], a, w[t][c * CH + k]);            \
-      }                                                                                                                \
+    _Pragma("unroll") for (int t = 0; t < TILES; ++t) part[t] = KS != CH ? zero_in_vgprs() : ds2_f32x4{0.f, 0.f, 0.f, 0.f}; \
+    _Pragma("unroll") for (int i = 0; i < PER; ++i) {                                                                  \
+      const uint4 a = make_uint4(v[i][0], v[i][1], v[i][2], v[i][3]);                                                  \
+      _Pragma("unroll") for (int t = 0; t < TILES; ++t)                                                                \
+          smma16(part[t], a, w[t][c * CH + 2 * i], w[t][c * CH + 2 * i + 1], spidx);                                   \
     }
 #define DS2_TF_CHECK(bad)                                                                                              \
     bool bad = false;                                                                                                  \
@@ -837,7 +776,7 @@ __device__ __forceinline__ float dpp_xor1(float v) {      // value of the neighb
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1 /* quad_perm [1,0,3,2] */, 0xf, 0xf, true));
 }
 
-template <int CELL, int H, int P, bool SP>
+template <int CELL, int H, int P>
 __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
   constexpr int G = CellInfo<CELL>::G, NS = CellInfo<CELL>::NS;
   constexpr int U = H / P;
@@ -845,7 +784,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
   constexpr int KS = H / 128;
   constexpr int X2 = H / 2;
   static_assert(U == 32 && H % 128 == 0, "the one-unit-per-thread gate map assumes 32 hidden units per workgroup");
-  static_assert(!SP || H % 256 == 0, "a wave's K-quarter is whole k-blocks of 64");
+  static_assert(H % 256 == 0, "a wave's K-quarter is whole k-blocks of 64");
   __shared__ __attribute__((aligned(16))) float part[2][4 * TILES * PT_TILE];
   DS2_PROBE_ONLY(__shared__ unsigned long long tl_[TL_N][TL_K];)
   __builtin_amdgcn_s_setprio(3);
@@ -866,24 +805,23 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
       const int r = 16 * t + li;
       const bf16_t* row = Wd + ((long)(r / U) * H + p * U + (r % U)) * H + wave * (H / 4) + lq * 8;
 #pragma unroll
-      for (int k = 0; k < KS; ++k) w[t][k] = *reinterpret_cast<const uint4*>(row + 32 * k);   // SP: the same fragments (see smma16)
+      for (int k = 0; k < KS; ++k) w[t][k] = *reinterpret_cast<const uint4*>(row + 32 * k);   // dense fragments; pairs of them feed smma16
     }
   }
   // tag-free exchange: 4 slots of [H/32 k-steps][4][8 rows] x 16 bytes inside this group's share of the scratch
   constexpr int SLOT_BYTES = (H / 32) * 512;
   static_assert(4 * SLOT_BYTES <= 2 * MAXS * X2 * 8, "four payload slots fit where the two tagged parities lived");
   char* xg = (char*)(a.xbuf + (long)grp * 2 * MAXS * X2);
-  const int srow = SP ? li : (li & 7), half = li >> 3;
   const bool need = (li & 7) < Ns;
-  const int spidx = (li & 8) ? 0xEEEE : 0x4444;      // SP: rows 8..15 carry the k = 2, 3 (mod 4) elements
+  const int spidx = (li & 8) ? 0xEEEE : 0x4444;      // rows 8..15 carry the k = 2, 3 (mod 4) elements
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xg, 0, 4 * SLOT_BYTES, 0x00020000);
 
-  // ---- gate identity: thread bits = (e: unit of the pair, pair within the 16-byte unit (2), sample row (3), lq (2)) -- the pair
-  // index (tid >> 1) has the bit order of the exchange layout, so the even lanes of a wave publish one contiguous 128-byte run
-  // (SP: (e, pair within the unit (2), tile-row half (1), sample row (3), 16-k block of the workgroup's 32 units (1)): two 64-byte runs)
+  // ---- gate identity: thread bits = (e: unit of the pair, pair within the 16-byte unit (2), tile-row half (1), sample row (3), 16-k
+  // block of the workgroup's 32 units (1)) -- the pair index (tid >> 1) has the bit order of the exchange layout, so the even lanes of
+  // a wave publish two contiguous 64-byte runs
   const int e = tid & 1, pid = tid >> 1;
-  const int gi_i = SP ? (pid >> 3) & 7 : (pid >> 2) & 7;
-  const int up = SP ? (pid >> 6) * 8 + (pid & 3) * 2 + ((pid >> 2) & 1) : ((pid >> 5) & 3) * 4 + (pid & 3);
+  const int gi_i = (pid >> 3) & 7;
+  const int up = (pid >> 6) * 8 + (pid & 3) * 2 + ((pid >> 2) & 1);
   const bool gate_thread = gi_i < Ns;
   const int n = slice + a.gpd * gi_i;
   const int j = p * U + 2 * up;              // first unit of the pair
@@ -918,7 +856,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
     *reinterpret_cast<uint32_t*>(hb - (long)N * H) = 0u;
     *reinterpret_cast<uint32_t*>(hb + (long)Tp * N * H) = 0u;
   }
-  const int xoff = SP ? xsp_pair_bytes(j, gi_i) : xtf_pair_bytes(j, gi_i);     // this pair's dword inside a slot
+  const int xoff = xsp_pair_bytes(j, gi_i);     // this pair's dword inside a slot
   if (a.h0) {                    // initial state as "step -1": slot 3
     const float other = dpp_xor1(hprev);
     if (gate_thread && e == 0) publish32(xg + 3 * SLOT_BYTES + xoff, xtf_word(pack_bf16x2(hprev, other)), local);
@@ -949,7 +887,6 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
     pf_p[i] = uniform64(a.GI + ((long)(d == 0 ? pf_s0 : Tp - 1 - pf_s0) * N + nr) * ldgi + (long)d * GH + p * U);
   }
   const uint64_t pf_step = uniform64((uint64_t)(dstep * N * ldgi * 2));
-#if DS2_FWD_GI_AHEAD
   uint32_t gi_raw[G];
 #pragma unroll
   for (int g = 0; g < G; ++g) gi_raw[g] = 0u;
@@ -957,7 +894,6 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
 #pragma unroll
     for (int g = 0; g < G; ++g) gi_raw[g] = gi_ptr[(long)g * H];
   }
-#endif
   for (int s = 0; s < Tp; ++s) {
     DS2_PROBE_ONLY(const unsigned long long t0 = __builtin_readcyclecounter();)
     DS2_TL(0);
@@ -975,15 +911,6 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
         pf_p[1] += pf_step;
       }
     };
-    float gi[G];
-#pragma unroll
-    for (int g = 0; g < G; ++g) gi[g] = 0.f;
-#if !DS2_FWD_GI_AHEAD
-    if (gate_thread && !DS2_DBG(a, 1)) {
-#pragma unroll
-      for (int g = 0; g < G; ++g) gi[g] = __uint_as_float((uint32_t)gi_ptr[(long)g * H] << 16);
-    }
-#endif
 #if DS2_FWD_SLEEP
     if (s > 0) __builtin_amdgcn_s_sleep(DS2_FWD_SLEEP);
 #endif
@@ -991,22 +918,18 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
 #pragma unroll
     for (int tt = 0; tt < TILES; ++tt) acc[tt] = ds2_f32x4{0.f, 0.f, 0.f, 0.f};
     if (s > 0 || a.h0)
-      gather_mma_tf<TILES, KS, SP>(acc, w, rsrc, ((s + 3) & 3) * SLOT_BYTES, wave * KS, lq, srow, half, need, a.err, a.lerr, dead, rounds, touch, spidx);
+      gather_mma_tf<TILES, KS>(acc, w, rsrc, ((s + 3) & 3) * SLOT_BYTES, wave * KS, lq, li, need, a.err, a.lerr, dead, rounds, touch, spidx);
     else
       touch();
-#if DS2_FWD_GI_AHEAD
-    {   // loaded at the end of the step before (the gather's waits have drained them: vmcnt retires in order)
-      if (s == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    float gi[G];   // loaded at the end of the step before (the gather's waits have drained them: vmcnt retires in order)
+    if (s == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-      for (int g = 0; g < G; ++g) {
-        gi[g] = __uint_as_float(gi_raw[g] << 16);
-        asm volatile("" : "+v"(gi[g]));
-      }
+    for (int g = 0; g < G; ++g) {
+      gi[g] = __uint_as_float(gi_raw[g] << 16);
+      asm volatile("" : "+v"(gi[g]));
     }
-#endif
     DS2_PROBE_ONLY(const unsigned long long t1 = __builtin_readcyclecounter();)
     DS2_TL(2);
-    if (SP && DS2_PREADD) preadd_rows<TILES>(acc);
     store_partials_t<TILES>(part[par], acc, wave, lane);
     __syncthreads();
     DS2_PROBE_ONLY(const unsigned long long t2 = __builtin_readcyclecounter();)
@@ -1022,8 +945,8 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
       for (int g = 0; g < G; ++g) {
         const float* pp = part[par] + pidx[g];
         gh[g] = (pp[0] + pp[TILES * PT_TILE]) + (pp[2 * TILES * PT_TILE] + pp[3 * TILES * PT_TILE]);
-        if (SP && !DS2_PREADD)      // the clip's second tile row (k = 2, 3 mod 4), 8 floats on in the [col][row] tile
-          gh[g] += (pp[8] + pp[TILES * PT_TILE + 8]) + (pp[2 * TILES * PT_TILE + 8] + pp[3 * TILES * PT_TILE + 8]);
+        // the clip's second tile row (k = 2, 3 mod 4), 8 floats on in the [col][row] tile
+        gh[g] += (pp[8] + pp[TILES * PT_TILE + 8]) + (pp[2 * TILES * PT_TILE + 8] + pp[3 * TILES * PT_TILE + 8]);
       }
       if (act) {
         if (CELL == CELL_GRU) {
@@ -1057,19 +980,6 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
       float pl_o[NS ? NS : 1];
 #pragma unroll
       for (int q = 0; q < (NS ? NS : 1); ++q) pl_o[q] = dpp_xor1(pl[q]);
-#ifdef DS2_QUAD_STORES
-      const u32x4q pubv = row4(xtf_word(pack_bf16x2(hprev, hp_o))), hsv = row4(pack_bf16x2(hn, hn_o));
-      u32x4q plv[NS ? NS : 1];
-#pragma unroll
-      for (int q = 0; q < (NS ? NS : 1); ++q) plv[q] = row4(pack_bf16x2(pl[q], pl_o[q]));
-      if (gate_thread && (tid & 7) == 0) {
-        publish128(rsrc, (s & 3) * SLOT_BYTES + xoff, pubv, local);
-        publish128(rsrc, ((s + 2) & 3) * SLOT_BYTES + xoff, u32x4q{XSENT, XSENT, XSENT, XSENT}, local);   // re-arm the slot of step s + 2
-        *reinterpret_cast<u32x4q*>(hs_ptr) = hsv;
-#pragma unroll
-        for (int q = 0; q < NS; ++q) *reinterpret_cast<u32x4q*>(sv_ptr + (long)q * H) = plv[q];
-      }
-#else
       if (gate_thread && e == 0) {
         publish32(xg + (s & 3) * SLOT_BYTES + xoff, xtf_word(pack_bf16x2(hprev, hp_o)), local);
         publish32(xg + ((s + 2) & 3) * SLOT_BYTES + xoff, XSENT, local);        // re-arm the slot of step s + 2
@@ -1078,15 +988,12 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_fwd4(PArgs a) {
 #pragma unroll
         for (int q = 0; q < NS; ++q) *reinterpret_cast<uint32_t*>(sv_ptr + (long)q * H) = pack_bf16x2(pl[q], pl_o[q]);
       }
-#endif
     }
     gi_ptr += gi_stride;
-#if DS2_FWD_GI_AHEAD
     if (gate_thread && s + 1 < Tp) {
 #pragma unroll
       for (int g = 0; g < G; ++g) gi_raw[g] = gi_ptr[(long)g * H];
     }
-#endif
     if (NS) sv_ptr += sv_stride;
     hs_ptr += hs_stride;
     l2_touch_retire();
@@ -1347,7 +1254,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd(PArgs a) {
 // ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float ld_bf16(const bf16_t* p) { return __uint_as_float((uint32_t)p->v << 16); }
 
-template <int CELL, int H, int P, bool SP>
+template <int CELL, int H, int P>
 __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
   constexpr int G = CellInfo<CELL>::G, NS = CellInfo<CELL>::NS;
   constexpr int U = H / P;
@@ -1355,7 +1262,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
   constexpr int KS = G * H / 128;
   constexpr int X2 = G * H / 2;
   static_assert(U == 32 && (G * H) % 128 == 0, "the one-unit-per-thread gate map assumes 32 hidden units per workgroup");
-  static_assert(!SP || ((G * H) % 256 == 0 && H % 64 == 0), "a wave's K-quarter is whole k-blocks of 64; a gate starts on a k-block");
+  static_assert((G * H) % 256 == 0 && H % 64 == 0, "a wave's K-quarter is whole k-blocks of 64; a gate starts on a k-block");
   __shared__ __attribute__((aligned(16))) float part[2][4 * TILES * PT_TILE];
   DS2_PROBE_ONLY(__shared__ unsigned long long tl_[TL_N][TL_K];)
   __builtin_amdgcn_s_setprio(3);
@@ -1375,21 +1282,20 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
     for (int t = 0; t < TILES; ++t) {
       const bf16_t* row = WT + (long)(p * U + 16 * t + li) * GH + wave * (GH / 4) + lq * 8;
 #pragma unroll
-      for (int k = 0; k < KS; ++k) w[t][k] = *reinterpret_cast<const uint4*>(row + 32 * k);   // SP: the same fragments (see smma16)
+      for (int k = 0; k < KS; ++k) w[t][k] = *reinterpret_cast<const uint4*>(row + 32 * k);   // dense fragments; pairs of them feed smma16
     }
   }
-  // tag-free exchange (see gather_mma_tf): 4 slots of [G*H/32 k-steps][4][8 rows] x 16 bytes
+  // tag-free exchange (see gather_mma_tf): 4 slots of [G*H/64 k-blocks][4][16 tile rows] x 16 bytes
   constexpr int SLOT_BYTES = (G * H / 32) * 512;
   static_assert(4 * SLOT_BYTES <= 2 * MAXS * X2 * 8, "four payload slots fit where the two tagged parities lived");
   char* xg = (char*)(a.xbuf + (long)grp * 2 * MAXS * X2);
-  const int srow = SP ? li : (li & 7), half = li >> 3;
   const bool need = (li & 7) < Ns;
   const int spidx = (li & 8) ? 0xEEEE : 0x4444;
   const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)xg, 0, 4 * SLOT_BYTES, 0x00020000);
 
   const int e = tid & 1, pid = tid >> 1;      // thread bits as in k_rnn_persist_fwd4
-  const int gi_i = SP ? (pid >> 3) & 7 : (pid >> 2) & 7;
-  const int up = SP ? (pid >> 6) * 8 + (pid & 3) * 2 + ((pid >> 2) & 1) : ((pid >> 5) & 3) * 4 + (pid & 3);
+  const int gi_i = (pid >> 3) & 7;
+  const int up = (pid >> 6) * 8 + (pid & 3) * 2 + ((pid >> 2) & 1);
   const bool gate_thread = gi_i < Ns;
   const int n = slice + a.gpd * gi_i;
   const int j = p * U + 2 * up, ju = j + e;
@@ -1414,7 +1320,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
   const bool local = group_is_xcd_local(a.xcc + grp * 32, p, tid, a.err, a.lerr, a.startup_ms, dead);
   unsigned rounds = 0;
   const int pidx = partial_t_index((2 * up + e) / 16, gi_i, (2 * up + e) % 16);
-  const int xoff = SP ? xsp_pair_bytes(j, gi_i) : xtf_pair_bytes(j, gi_i);     // this pair's dword of gate 0 inside a slot
+  const int xoff = xsp_pair_bytes(j, gi_i);     // this pair's dword of gate 0 inside a slot
 
   DS2_PROBE_ONLY(unsigned long long c_gather = 0, c_bar = 0, c_gate = 0;)
   // Everything the gate phase of a step needs (2-byte loads of this thread's unit: dOut, the saved planes, h_prev, c_prev) is
@@ -1497,7 +1403,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
     if (s > 0) __builtin_amdgcn_s_sleep(DS2_BWD_SLEEP);
 #endif
     if (s > 0)
-      gather_mma_tf<TILES, KS, SP>(acc, w, rsrc, ((s + 3) & 3) * SLOT_BYTES, wave * KS, lq, srow, half, need, a.err, a.lerr, dead, rounds, touch, spidx);
+      gather_mma_tf<TILES, KS>(acc, w, rsrc, ((s + 3) & 3) * SLOT_BYTES, wave * KS, lq, li, need, a.err, a.lerr, dead, rounds, touch, spidx);
     else
       touch();
     // this step's values first (loaded two steps ago; the gather has just drained vmcnt), THEN the new loads: converted after
@@ -1517,7 +1423,6 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
     __builtin_amdgcn_sched_barrier(0);
     DS2_PROBE_ONLY(const unsigned long long t1 = __builtin_readcyclecounter();)
     DS2_TL(2);
-    if (SP && DS2_PREADD) preadd_rows<TILES>(acc);
     store_partials_t<TILES>(part[par], acc, wave, lane);
     __syncthreads();
     DS2_PROBE_ONLY(const unsigned long long t2 = __builtin_readcyclecounter();)
@@ -1530,7 +1435,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
       const bool act = t < len;
       const float* pp = part[par] + pidx;
       float psum = (pp[0] + pp[TILES * PT_TILE]) + (pp[2 * TILES * PT_TILE] + pp[3 * TILES * PT_TILE]);
-      if (SP && !DS2_PREADD) psum += (pp[8] + pp[TILES * PT_TILE + 8]) + (pp[2 * TILES * PT_TILE + 8] + pp[3 * TILES * PT_TILE + 8]);   // tile row s + 8
+      psum += (pp[8] + pp[TILES * PT_TILE + 8]) + (pp[2 * TILES * PT_TILE + 8] + pp[3 * TILES * PT_TILE + 8]);   // tile row s + 8
       const float din = car + psum;
       car = din;
       if (CELL == CELL_GRU) {
@@ -1580,33 +1485,7 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
 #pragma unroll
       for (int g = 0; g < G; ++g) pk[g] = pack_bf16x2(e == 0 ? gx[g] : go[g], e == 0 ? go[g] : gx[g]);
       const uint32_t pkn = pack_bf16x2(e == 0 ? gn : gn_o, e == 0 ? gn_o : gn);
-#ifdef DS2_QUAD_STORES
-      u32x4q pubv[G], stv[G];
-#pragma unroll
-      for (int g = 0; g < G; ++g) {
-        stv[g] = row4(pk[g]);
-        pubv[g] = row4(xtf_word(pk[g]));
-      }
-      const u32x4q nv = row4(pkn);
-      if (gate_thread && (tid & 7) == 0) {
-        const int xo = (s & 3) * SLOT_BYTES + xoff, xr = ((s + 2) & 3) * SLOT_BYTES + xoff;
-#pragma unroll
-        for (int g = 0; g < G; ++g) publish128(rsrc, xo + g * (H / 32) * 512, pubv[g], local);
-#pragma unroll
-        for (int g = 0; g < G; ++g) publish128(rsrc, xr + g * (H / 32) * 512, u32x4q{XSENT, XSENT, XSENT, XSENT}, local);
-        if (CELL == CELL_GRU) {
-          *reinterpret_cast<u32x4q*>(dgi_ptr) = stv[0];
-          *reinterpret_cast<u32x4q*>(dgi_ptr + H) = stv[1 % G];
-          *reinterpret_cast<u32x4q*>(dgi_ptr + 2 * H) = nv;
-          *reinterpret_cast<u32x4q*>(dgh_ptr) = stv[2 % G];
-        } else {
-#pragma unroll
-          for (int g = 0; g < G; ++g) *reinterpret_cast<u32x4q*>(dgi_ptr + (long)g * H) = stv[g];
-        }
-      }
-#endif
       if (gate_thread) {
-#ifndef DS2_QUAD_STORES
         if (e == 0) {
           char* xo = xg + (s & 3) * SLOT_BYTES + xoff;         // gate g, units (j, j+1): element k = g*H + j -> k-step 32*g + p
           char* xr = xg + ((s + 2) & 3) * SLOT_BYTES + xoff;   // re-armed for step s + 2
@@ -1625,7 +1504,6 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
             for (int g = 0; g < G; ++g) *reinterpret_cast<uint32_t*>(dgi_ptr + (long)g * H) = pk[g];
           }
         }
-#endif
         // own unit's rounded values: low half of the pair word on the even lane, high half on the odd lane
         if (CELL == CELL_GRU) {
           bsum[0] += e == 0 ? bf_lo(pk[0]) : bf_hi(pk[0]);
@@ -1671,22 +1549,17 @@ __global__ void __launch_bounds__(256, 1) k_rnn_persist_bwd4(PArgs a) {
   }
 }
 
-// dense = the round-2..4 form of the 8-clip kernels (half of every 16-row tile is padding); default: the structured-sparse form
 template <int CELL, int H, int P>
-int launch(bool bwd, const PArgs& a, hipStream_t st, bool dense) {
-  const bool split = (a.N + a.gpd - 1) / a.gpd <= 8;   // <= 8 samples per group: lane pairs share the gather
+int launch(bool bwd, const PArgs& a, hipStream_t st) {
+  const bool split = (a.N + a.gpd - 1) / a.gpd <= 8;   // <= 8 samples per group: the structured-sparse, tag-free kernels
   if (bwd) {
-    if (split && dense)
-      hipLaunchKernelGGL((k_rnn_persist_bwd4<CELL, H, P, false>), dim3(NGROUPS * P), dim3(256), 0, st, a);
-    else if (split)
-      hipLaunchKernelGGL((k_rnn_persist_bwd4<CELL, H, P, true>), dim3(NGROUPS * P), dim3(256), 0, st, a);
+    if (split)
+      hipLaunchKernelGGL((k_rnn_persist_bwd4<CELL, H, P>), dim3(NGROUPS * P), dim3(256), 0, st, a);
     else
       hipLaunchKernelGGL((k_rnn_persist_bwd<CELL, H, P, 1>), dim3(NGROUPS * P), dim3(256), 0, st, a);
   } else {
-    if (split && dense)
-      hipLaunchKernelGGL((k_rnn_persist_fwd4<CELL, H, P, false>), dim3(NGROUPS * P), dim3(256), 0, st, a);
-    else if (split)
-      hipLaunchKernelGGL((k_rnn_persist_fwd4<CELL, H, P, true>), dim3(NGROUPS * P), dim3(256), 0, st, a);
+    if (split)
+      hipLaunchKernelGGL((k_rnn_persist_fwd4<CELL, H, P>), dim3(NGROUPS * P), dim3(256), 0, st, a);
     else
       hipLaunchKernelGGL((k_rnn_persist_fwd<CELL, H, P, 1>), dim3(NGROUPS * P), dim3(256), 0, st, a);
   }

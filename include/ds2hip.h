@@ -176,10 +176,11 @@ int ds2_rnn_bwd(int dtype, int cell, int D, int N, int H, int Tp, const int* len
 /* Per-launch options of the persistent sweeps; pass NULL for the defaults.  (Rounds 2-5 had process-wide setters here --
  * ds2_rnn_persist_set_variant / _set_spin_limit; options travel with the call now: the entries are re-entrant, backward may run on
  * autograd's worker thread beside a forward, and nothing a caller sets outlives its call.)
- *   variant     routing A/B bits for measurements, 0 = the shipping routing: bit 0 the shapes of the round-4 general kernels
- *               (csrc/ds2_rnn_persist3_impl.h) run on the round-2 general kernels (or one launch per time step) instead, 1 two-set
- *               groups execute every half-step, 3 the round-4 kernels also take H = 1024 with <= 8 clips per group, 4 the tuned kernels
- *               keep 9-16 clips per group, 5 the 8-clip tuned kernels use dense products instead of the structured-sparse ones.
+ *   variant     routing bits for tests and measurements, 0 = the shipping routing.  Three bits are live: bit 0 (1) the shapes of the
+ *               round-4 general kernels (csrc/ds2_rnn_persist3_impl.h) run on the round-2 general kernels (or one launch per time
+ *               step) instead, bit 3 (8) the round-4 kernels also take H = 1024, bit 4 (16) the tuned kernels keep 9-16 clips per
+ *               group.  Any other bit is refused: ds2_rnn_persist_plan / _supported / _kind / _ws_bytes answer 0 and the sweeps
+ *               return DS2_ERR_ARG.  (Bits 1, 5, 6 and 7 selected rejected A/B paths; removed, last present in 099aa25.)
  *               The queries below take the same bits, so that a caller sizes the scratch for the routing it will launch.
  *   spin_limit  fault injection: polls a workgroup may spend on ONE mid-sweep exchange wait before it gives up (raises *err = 1,
  *               NaN-poisons its outputs, ends); 0 = the built-in budget (~seconds).

@@ -195,22 +195,24 @@ def check_persist_routing(answer, covered):
     """Compares a routing of the persistent recurrent sweeps with the recorded table tests/golden/routing/persist_routing.npz (written by
     tests/golden/make_persist_routing.py from the parent of the routing refactor, on an MI355X), row by row.
     answer(dtype, cell, D, N, H, variant) -> (supported, kind, ws_bytes); covered(dtype, cell, D, N, H) -> shape_covered.
-    Returns the number of rows compared."""
+    Of the recorded variants only the columns of the live routing bits are compared (0, 1, 8, 16 for bf16; 0, 1 for fp32): the bits
+    2, 32, 64 and 128 of the recording are retired and a variant that carries one is refused.  Returns the number of rows compared."""
     z = np.load(os.path.join(GOLDEN_DIR, "routing", "persist_routing.npz"))
     assert b"recorded from commit 35ac4a121fe5370703d8e3e01c8a6a90900492fd" in bytes(z["header"]) and b"does NOT" not in bytes(z["header"])
     Hs, Ns, variants = z["H"].tolist(), z["N"].tolist(), z["variants"].tolist()
     assert Hs == list(range(16, 1601, 16)) and len(Ns) == 90 and variants == [0, 1, 2, 8, 16, 32, 64, 128]
     rows, bad = 0, []
-    for name, dtype, vs in (("bf16", 1, variants), ("f32", 0, variants[:2])):
+    for name, dtype, vs, live in (("bf16", 1, variants, (0, 1, 8, 16)), ("f32", 0, variants[:2], (0, 1))):
         sup, kind, ws, cov = (z["%s_%s" % (name, k)] for k in ("supported", "kind", "ws", "covered"))
         assert sup.shape == (3, 2, len(Hs), len(Ns), len(vs)) and cov.shape == sup.shape[:4]
+        columns = [(vs.index(v), v) for v in live]
         for cell in range(3):
             for D in (1, 2):
                 for hi, H in enumerate(Hs):
                     for ni, N in enumerate(Ns):
                         if int(covered(dtype, cell, D, N, H)) != cov[cell, D - 1, hi, ni]:
                             bad.append((name, cell, D, N, H, "covered"))
-                        for vi, v in enumerate(vs):
+                        for vi, v in columns:
                             got = tuple(int(x) for x in answer(dtype, cell, D, N, H, v))
                             want = (int(sup[cell, D - 1, hi, ni, vi]), int(kind[cell, D - 1, hi, ni, vi]), int(ws[cell, D - 1, hi, ni, vi]))
                             rows += 1

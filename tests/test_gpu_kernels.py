@@ -396,25 +396,6 @@ def test_rnn_persistent_sweeps(kind, D, N, H, Tp):
         assert np.abs(a - b).max() <= 2e-2 * max(1.0, np.abs(b).max()), np.abs(a - b).max()
 
 
-@pytest.mark.parametrize("kind,D,N,H,Tp", [("gru", 2, 32, 1024, 9), ("gru", 2, 11, 1024, 13), ("lstm", 1, 5, 1024, 6), ("rnn", 2, 9, 1024, 11),
-                                           ("gru", 2, 1, 1024, 7)])
-def test_rnn_persistent_sparse_and_dense_forms_agree(kind, D, N, H, Tp):
-    """Groups of <= 8 clips (round 5): the sweeps' products run on the structured-sparse instruction -- a clip's k = 0, 1 (mod 4)
-    elements on tile row s, its k = 2, 3 (mod 4) elements on row s + 8 -- instead of leaving half of the dense tile to padding.
-    Both forms multiply the same bf16 operands and are held to the oracle by _rnn_sweep_case; against each other only the fp32
-    summation order may differ."""
-    o = ops()
-    from deepspeech.pytorch_amd._lib import query
-    assert o.use_persistent(kind, torch.bfloat16, D, N, H)
-    res_sp = _rnn_sweep_case(torch.bfloat16, kind, D, N, H, Tp, 1.0 / np.sqrt(H))
-    o.check_persistent_kernels()
-    with o.persist_options(variant=32):                    # bit 5: dense products (round 4's form)
-        res_de = _rnn_sweep_case(torch.bfloat16, kind, D, N, H, Tp, 1.0 / np.sqrt(H))
-        o.check_persistent_kernels()
-    for a, b in zip(res_sp, res_de):
-        assert np.abs(a - b).max() <= 2e-2 * max(1.0, np.abs(b).max()), np.abs(a - b).max()
-
-
 GENERAL_PERSISTENT_CASES = [
     # fp32 storage (the 1e-3 parity mode): BASELINE config 2's width (H = 800; 25 / 150 k-steps: ragged K split) and 1024
     (torch.float32, "gru", 2, 8, 800, 9), (torch.float32, "lstm", 1, 5, 800, 7), (torch.float32, "gru", 2, 32, 1024, 6),
@@ -441,37 +422,18 @@ PERSIST3_CASES = [
     # round 5: the widths in between (every bf16 hidden size up to 1536 is at most 128 zero units away from a persistent kernel)
     ("gru", 2, 9, 384, 6), ("lstm", 1, 40, 384, 5), ("gru", 2, 33, 640, 5), ("lstm", 2, 8, 640, 6), ("gru", 1, 7, 896, 6),
     ("lstm", 2, 64, 896, 4), ("gru", 2, 64, 1152, 4), ("lstm", 2, 11, 1152, 5), ("gru", 2, 16, 1408, 5), ("gru", 1, 40, 1408, 4),
-    # round 6: sets of <= 8 clips on the structured-sparse products (H % 256 == 0, <= 16 clips per group): one set (<= 8 clips) and
-    # two sets (8 + the rest), XCD-local groups and groups across XCDs, LDS-resident k-blocks in BPTT (LSTM-1280: 6 of 20 per wave)
+    # round 6: groups of <= 8 clips as ONE set on the structured-sparse products (H >= 1024, H % 256 == 0; above: ("lstm", 1, 3, 1280, 6),
+    # ("gru", 2, 7, 1280, 8), ("gru", 1, 9, 1536, 5)) and their neighbours on dense tiles: 9-16 clips per group, widths below 1024;
+    # XCD-local groups and groups across XCDs, LDS-resident k-blocks in BPTT (LSTM-1280: 6 of 20 per wave)
     ("lstm", 1, 64, 1280, 6), ("lstm", 2, 64, 1024, 5), ("gru", 2, 48, 512, 6), ("gru", 1, 100, 768, 5), ("lstm", 1, 90, 1536 // 2, 4),
     ("gru", 2, 27, 1280, 7), ("lstm", 2, 32, 1280, 5),
+    # the boundary: exactly 8 clips per group (sparse set); ("gru", 2, 27, 1280, 7) above has 9 (dense)
+    ("lstm", 2, 24, 1280, 5),
 ]
-SPARSE3_CASES = [("lstm", 1, 64, 1280, 9), ("lstm", 1, 3, 1280, 6), ("gru", 2, 30, 1536, 4), ("gru", 2, 64, 1024, 6), ("lstm", 2, 48, 512, 7),
-                 ("gru", 1, 100, 768, 5), ("gru", 2, 7, 1280, 8)]
-
-
-@pytest.mark.parametrize("kind,D,N,H,Tp", SPARSE3_CASES)
-def test_rnn_persist3_sparse_and_dense_sets_agree(kind, D, N, H, Tp):
-    """Round 6: sets of <= 8 clips run on the structured-sparse instruction in the general kernels too (tile row s = a clip's
-    k = 0, 1 (mod 4) elements, row s + 8 its k = 2, 3 (mod 4) ones): by default groups of <= 8 clips (one set); routing bit 7 also
-    cuts groups of 9-16 into two sparse sets (measured slower than one dense set, kept for A/B and covered here).  Same bf16 operands
-    as the dense 16-row tiles (routing bit 6 keeps those); every form is held to the oracle by _rnn_sweep_case; against each other
-    only the fp32 summation order differs."""
-    o = ops()
-    assert o.use_persistent(kind, torch.bfloat16, D, N, H) and o.persist_kind(torch.bfloat16, kind, D, N, H) == 3
-    with o.persist_options(variant=128):                   # sparse sets wherever they exist (<= 16 clips per group)
-        res_sp = _rnn_sweep_case(torch.bfloat16, kind, D, N, H, Tp, 1.0 / np.sqrt(H))
-        o.check_persistent_kernels()
-    with o.persist_options(variant=64):                    # dense tiles everywhere
-        assert o.persist_kind(torch.bfloat16, kind, D, N, H) == 3
-        res_de = _rnn_sweep_case(torch.bfloat16, kind, D, N, H, Tp, 1.0 / np.sqrt(H))
-        o.check_persistent_kernels()
-    for a, b in zip(res_sp, res_de):
-        assert np.abs(a - b).max() <= 2e-2 * max(1.0, np.abs(b).max()), np.abs(a - b).max()
 
 
 def test_persist_routing_on_the_device_matches_the_recorded_table():
-    """The live routing entries on this device (support, kernel family, scratch bytes under every A/B variant; shape_covered) against
+    """The live routing entries on this device (support, kernel family, scratch bytes under every live routing bit; shape_covered) against
     the table recorded from the commit before the routing was unified (tests/golden/routing, tests/fixtures.check_persist_routing)."""
     from deepspeech.pytorch_amd._lib import query
     from fixtures import check_persist_routing
@@ -481,7 +443,7 @@ def test_persist_routing_on_the_device_matches_the_recorded_table():
     def answer(*problem):
         return tuple(query("ds2_rnn_persist_" + q, *problem) for q in ("supported", "kind", "ws_bytes"))
 
-    assert check_persist_routing(answer, lambda *shape: query("ds2_rnn_persist_shape_covered", *shape)) == 54000 * 10
+    assert check_persist_routing(answer, lambda *shape: query("ds2_rnn_persist_shape_covered", *shape)) == 54000 * 6
 
 
 @pytest.mark.parametrize("kind,D,N,H,Tp", PERSIST3_CASES)

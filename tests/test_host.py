@@ -44,7 +44,8 @@ def test_library_exports_every_declared_symbol(lib):
 def test_persist_routing_matches_the_recorded_table(lib):
     """The one routing decision of the persistent sweeps (ds2_rnn_persist.hip, plan), asked with 256 CUs given explicitly, against
     every row of the table recorded from the live entries of the commit before the routing was unified: support, kernel family and
-    scratch bytes under every A/B variant, and shape_covered (which the recording on the MI355X and this host must answer alike)."""
+    scratch bytes under every live routing bit, and shape_covered (which the recording on the MI355X and this host must answer alike).
+    A variant with a retired bit is refused."""
     import ctypes as C
     from fixtures import check_persist_routing
 
@@ -54,7 +55,13 @@ def test_persist_routing_matches_the_recorded_table(lib):
         assert lib.ds2_rnn_persist_plan(dtype, cell, D, N, H, 256, variant, None) == family
         return int(family != 0), family, ws.value
 
-    assert check_persist_routing(answer, lib.ds2_rnn_persist_shape_covered) == 54000 * 8 + 54000 * 2
+    assert check_persist_routing(answer, lib.ds2_rnn_persist_shape_covered) == 54000 * 6
+    # bits outside the live mask (1 | 8 | 16) are a caller's mistake: no family, on a shape that every live variant covers
+    for variant in (0, 1, 8, 16):
+        assert lib.ds2_rnn_persist_plan(1, 0, 2, 32, 1024, 256, variant, None) != 0
+    for variant in (2, 32, 64, 128, 1 | 64):
+        ws = C.c_long(-1)
+        assert lib.ds2_rnn_persist_plan(1, 0, 2, 32, 1024, 256, variant, C.byref(ws)) == 0 and ws.value == 0
     # a device below 256 CUs runs none of them
     assert lib.ds2_rnn_persist_plan(1, 0, 2, 32, 1024, 255, 0, None) == 0 and lib.ds2_rnn_persist_plan(1, 0, 2, 32, 1024, 256, 0, None) == 1
 

@@ -6,7 +6,7 @@ tag=${1:-ev}
 out=gpurun_out/$tag; mkdir -p $out
 export TMPDIR=/tmp
 here=$PWD
-if [ -z "$SKIP_DEFAULT" ]; then   # the default line includes the CPU leg (minutes): the end-of-round gate (tools/r06_gate.sh) runs the driver's command instead
+if [ -z "$SKIP_DEFAULT" ]; then   # the default line includes the CPU leg (minutes): an end-of-round gate runs the driver's command instead
   timeout 600 python bench.py --full > $out/bench_default.json 2> $out/bench_default.err; echo "bench default rc=$?"; tail -c 600 $out/bench_default.json; echo
 fi
 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-stock-baseline --no-other-configs > $out/bench_cfg3.json 2> $out/bench_cfg3.err; echo "bench cfg3 rc=$?"; grep -o '"ms_per_step": [0-9.]*' $out/bench_cfg3.json | head -1

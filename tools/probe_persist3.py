@@ -3,7 +3,10 @@
 (gather + products | partial sums + barrier | gate math + publish, re-polls) of workgroup 0 of every group, and the wall time per time
 step, with work switched off piece by piece (DS2_PERSIST_DBG bits: 1 no prefetch loads of the gate operands, 2 no output stores, 8 no
 gather and no products, 32 no products with the LDS-resident fragments, 64 plain-store publishes whatever the placement, 128 gather but no
-products).  Timing only: with any bit set the results are wrong.
+products).  Timing only: with any bit set the results are wrong.  The counters are divided by the number of dense sample sets of a
+group (one up to 16 clips, two up to 32), so the shapes must run on dense sets: more than 8 clips per group, or H < 1024 (every case
+below does; groups of <= 8 clips at H >= 1024 run as one structured-sparse set).  DS2_PROBE_VARIANT sets the live routing bits
+(ds2_persist_opts.variant: 1, 8, 16); the default is the shipping routing.
 
     gpurun -- 'python tools/probe_persist3.py > gpurun_out/probe_persist3.txt'
 """
@@ -19,7 +22,7 @@ from deepspeech.pytorch_amd import _lib, build  # noqa: E402
 _lib.LIB_PATH = build.build(probe=True, verbose=False)
 from deepspeech.pytorch_amd import ops  # noqa: E402
 
-ops._OPTS["variant"] = int(os.environ.get("DS2_PROBE_VARIANT", "64"))     # 64: dense 16-row tiles for <= 16 clips (the counters' nset assumes it)
+ops._OPTS["variant"] = int(os.environ.get("DS2_PROBE_VARIANT", "0"))
 
 CASES = [("lstm", 2, 64, 1280, 751, "cfg5a"), ("lstm", 1, 64, 1280, 751, "cfg5b"), ("gru", 2, 8, 800, 401, "bf16 GRU-800 bi (XCD-local)"),
          ("lstm", 2, 128, 1024, 301, "LSTM-1024 bi, 128 clips (XCD-local, 2 sets)")]

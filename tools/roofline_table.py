@@ -61,7 +61,7 @@ def main():
         ("k_opt_matrix4(", "AdamW + bf16 layouts of a recurrent weight matrix (32 B per parameter)", "hbm", GH * H * 32.0, 8e12, "TB/s"),
         ("k_add2", "direction sum (2 reads + 1 write of [T'N][H])", "hbm", 3.0 * R * H * esz, 8e12, "TB/s"),
         ("k_bn_apply<bf16_t, false", "SequenceWise BatchNorm apply (read + write of [T'N][H])", "hbm", 2.0 * R * H * esz, 8e12, "TB/s"),
-        ("k_bn_bwd_apply<bf16_t, false", "SequenceWise BatchNorm backward apply (2 reads + 1 write)", "hbm", 3.0 * R * H * esz, 8e12, "TB/s"),
+        ("k_bn_bwd_apply_cols<bf16_t, false", "SequenceWise BatchNorm backward apply (2 reads + 1 write)", "hbm", 3.0 * R * H * esz, 8e12, "TB/s"),
     ]
     got = {}
     for line in open(stats):
