@@ -14,6 +14,11 @@
 //                       writes the sequence layout X0[(j*N + n)][rld] the recurrent stack reads
 //   k_stream_lookahead  hardtanh(sum_k w[h][k] * V[t + k]); taps ascending with fmaf, as k_lookahead_fwd (ds2_seqops.hip)
 // Shapes are small (1..32 streams, a few to ~100 frames a feed): one short launch each, no persistent loops.
+//
+// Every kernel has a second instantiation, ROWS, for a pool of streams that each follow their own plan:
+// one ds2_stream_row per batch row gives the carry slot, the row of x, which of the two carry buffers holds the slot's carry
+// (per stage), whether that carry reads as zero (a stream's first feed) and the row's own len / off / cnt of every stage.  The
+// tile bodies, the fmaf order and the epilogues are shared, so a pool in lock step computes what the un-tabled kernels compute.
 #include "ds2_common.h"
 
 namespace {
@@ -30,26 +35,43 @@ constexpr int C1_PR = (C1_FB - 1) * 2 + K1F;               // 47 input rows
 constexpr int C1_PC = (C1_TB - 1) * 2 + K1T;               // 137 input cols
 constexpr int C1_PCP = C1_PC + 1;
 
-template <typename T>
+// ROWS: carry / next are the two buffers [S][F0][10] of the pool, the row's slot is read from one and written into the other
+template <typename T, bool ROWS>
 __global__ void __launch_bounds__(256) k_stream_conv1(const float* __restrict__ x, const float* __restrict__ carry,
                                                        float* __restrict__ next, const float* __restrict__ w1k,
                                                        const float* __restrict__ b1, const float* __restrict__ scale,
                                                        const float* __restrict__ shift, const int* __restrict__ len,
                                                        const int* __restrict__ live, T* __restrict__ y, int N, int Tc, int off, int J,
-                                                       int f0, int f1, int ntiles) {
+                                                       int f0, int f1, int ntiles, const ds2_stream_row* __restrict__ rows) {
   __shared__ float patch[C1_PR * C1_PCP];
   const int tid = threadIdx.x, n = blockIdx.z;
-  const int ln = len ? min(max(len[n], 0), Tc) : Tc;
-  const float* xn = x + (long)n * f0 * Tc;
-  const float* cn = carry + (long)n * f0 * SK;
+  int ln, nlive = 0;                                 // ROWS: the row's own count of output frames
+  bool fresh = false;
+  const float *xn, *cn;
+  float* nn;
+  if constexpr (ROWS) {
+    const ds2_stream_row R = rows[n];
+    const bool cur = (R.cur & 1) != 0;
+    ln = min(max(R.len, 0), Tc);
+    off = R.off1;
+    nlive = R.cnt1;
+    fresh = (R.fresh & 1) != 0;
+    xn = x + (long)R.src * f0 * Tc;
+    cn = (cur ? (const float*)next : carry) + (long)R.slot * f0 * SK;
+    nn = (cur ? const_cast<float*>(carry) : next) + (long)R.slot * f0 * SK;
+  } else {
+    ln = len ? min(max(len[n], 0), Tc) : Tc;
+    xn = x + (long)n * f0 * Tc;
+    cn = carry + (long)n * f0 * SK;
+    nn = next + (long)n * f0 * SK;
+  }
   if ((int)blockIdx.x == ntiles) {
     // the carry blocks: rows [r0, r1) of this stream, next[f][i] = V[f][ln + i]
     const int per = ds2_cdiv_dev(f0, gridDim.y);
     const int r0 = blockIdx.y * per, r1 = min(r0 + per, f0);
-    float* nn = next + (long)n * f0 * SK;
     for (int e = r0 * SK + tid; e < r1 * SK; e += 256) {
       const int f = e / SK, p = ln + (e - f * SK);        // p < SK + ln always
-      nn[e] = p < SK ? cn[f * SK + p] : xn[(long)f * Tc + (p - SK)];
+      nn[e] = p < SK ? (fresh ? 0.f : cn[f * SK + p]) : xn[(long)f * Tc + (p - SK)];
     }
     return;
   }
@@ -62,7 +84,7 @@ __global__ void __launch_bounds__(256) k_stream_conv1(const float* __restrict__ 
     // unconditional load from an address that always exists (the carry's when the position is not in the chunk), zeroed by a
     // select afterwards: keeps all of a thread's ~25 loads in flight
     const bool inx = p >= SK && p < SK + ln;
-    const bool ok = fi >= 0 && fi < f0 && p >= 0 && (p < SK || inx);
+    const bool ok = fi >= 0 && fi < f0 && p >= 0 && ((p < SK && !fresh) || inx);
     const float* src = inx ? xn + (long)fc * Tc + (p - SK) : cn + fc * SK + min(max(p, 0), SK - 1);
     const float v = *src;
     patch[pr * C1_PCP + pc] = ok ? v : 0.f;
@@ -84,7 +106,7 @@ __global__ void __launch_bounds__(256) k_stream_conv1(const float* __restrict__ 
     }
   }
   if (fo < f1 && to < J) {
-    const bool lv = live ? (to < live[n]) : true;
+    const bool lv = ROWS ? to < nlive : (live ? (to < live[n]) : true);
     T* dst = y + (((long)n * f1 + fo) * J + to) * CH;
     constexpr int V = Vec16<T>::N;
 #pragma unroll
@@ -121,9 +143,11 @@ struct StreamConv2Args {
   const int *len, *live;               // [N] or null
   void* X0;            // [(j*N + n)][rld]
   int N, Jin, off, J, F1, F2, rld;
+  const ds2_stream_row* rows;          // ROWS: carry / next are the pool's two buffers [S][F1][10][32]; X0 [(j*nrnn + n)][rld]
+  int nrnn;                            //       holds the rows n < nrnn, the rows behind them only move their carry
 };
 
-template <typename T>
+template <typename T, bool ROWS>
 __global__ void __launch_bounds__(256, 1) k_stream_conv2(StreamConv2Args a, int ntiles) {
   constexpr int V = Vec16<T>::N;
   constexpr int NPASS = (CH * (int)sizeof(T)) / 64;   // bf16: 1 pass of 32 channels; f32: 2 passes of 16 channels
@@ -132,27 +156,49 @@ __global__ void __launch_bounds__(256, 1) k_stream_conv2(StreamConv2Args a, int 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int li = lane & 31, lq = lane >> 5;
   const int n = blockIdx.z;
-  const int ln = a.len ? min(max(a.len[n], 0), a.Jin) : a.Jin;
+  int ln, off = a.off, nlive = 0, NR = a.N;         // nlive (ROWS): the row's own count of output frames
+  uint32_t cmask = 0xffffffffu;                       // 0: the carry reads as zero
   const T* An = (const T*)a.A + (long)n * a.F1 * a.Jin * CH;
-  const T* Cn = (const T*)a.carry + (long)n * a.F1 * SK * CH;
+  const T* Cn;
+  T* Nn;
+  if constexpr (ROWS) {
+    const ds2_stream_row R = a.rows[n];
+    const bool cur = (R.cur & 2) != 0;
+    ln = min(max(R.cnt1, 0), a.Jin);
+    off = R.off2;
+    nlive = R.cnt2;
+    NR = a.nrnn;
+    cmask = (R.fresh & 2) ? 0u : 0xffffffffu;
+    Cn = (const T*)(cur ? a.next : a.carry) + (long)R.slot * a.F1 * SK * CH;
+    Nn = (T*)(cur ? const_cast<void*>(a.carry) : a.next) + (long)R.slot * a.F1 * SK * CH;
+  } else {
+    ln = a.len ? min(max(a.len[n], 0), a.Jin) : a.Jin;
+    Cn = (const T*)a.carry + (long)n * a.F1 * SK * CH;
+    Nn = (T*)a.next + (long)n * a.F1 * SK * CH;
+  }
   if ((int)blockIdx.x == ntiles) {
     // the carry blocks: rows [r0, r1) of this stream, 16-byte pieces of next[f][i][32] = V[f][ln + i][32]
     constexpr int PV = CH / V;                        // pieces per position
     const int per = ds2_cdiv_dev(a.F1, gridDim.y);
     const int r0 = blockIdx.y * per, r1 = min(r0 + per, a.F1);
-    T* Nn = (T*)a.next + (long)n * a.F1 * SK * CH;
     for (int e = r0 * SK * PV + tid; e < r1 * SK * PV; e += 256) {
       const int v = e % PV, pos = e / PV;
       const int f = pos / SK, p = ln + (pos - f * SK);
       const T* src = p < SK ? Cn + ((long)f * SK + p) * CH : An + ((long)f * a.Jin + (p - SK)) * CH;
-      *reinterpret_cast<uint4*>(Nn + (long)pos * CH + v * V) = *reinterpret_cast<const uint4*>(src + v * V);
+      uint4 val = *reinterpret_cast<const uint4*>(src + v * V);
+      if constexpr (ROWS) {
+        const uint32_t m = p < SK ? cmask : 0xffffffffu;
+        val.x &= m; val.y &= m; val.z &= m; val.w &= m;
+      }
+      *reinterpret_cast<uint4*>(Nn + (long)pos * CH + v * V) = val;
     }
     return;
   }
+  if (ROWS && n >= NR) return;                       // no RNN frame this feed: the carry block above was this row's whole work
   const int to0 = blockIdx.x * CT_TB, u0 = blockIdx.y * CT_UB;
   unsigned char* patch = smem;
   unsigned char* wst = smem + CT_PATCH_BYTES;
-  const int fi0 = u0 * 2 - 10, p0 = a.off + to0;
+  const int fi0 = u0 * 2 - 10, p0 = off + to0;
   const T* Wg = (const T*)a.W;
 
   ds2_f32x16 acc;
@@ -169,7 +215,8 @@ __global__ void __launch_bounds__(256, 1) k_stream_conv2(StreamConv2Args a, int 
       const int fi = fi0 + pr, p = p0 + pc;
       // unconditional load from an address that always exists + bit mask (see k_conv_tap)
       const bool inx = p >= SK && p < SK + ln;
-      const uint32_t m = (fi >= 0 && fi < a.F1 && p >= 0 && (p < SK || inx)) ? 0xffffffffu : 0u;
+      uint32_t m = (fi >= 0 && fi < a.F1 && p >= 0 && (p < SK || inx)) ? 0xffffffffu : 0u;
+      if constexpr (ROWS) m &= inx ? 0xffffffffu : cmask;
       const int fc = min(max(fi, 0), a.F1 - 1);
       const T* src = inx ? An + ((long)fc * a.Jin + (p - SK)) * CH : Cn + ((long)fc * SK + min(max(p, 0), SK - 1)) * CH;
       uint4 val = *reinterpret_cast<const uint4*>(src + c0 + v * V);
@@ -213,8 +260,8 @@ __global__ void __launch_bounds__(256, 1) k_stream_conv2(StreamConv2Args a, int 
   const int pos = lane >> 1, half = lane & 1;
   const int to = to0 + pos;
   if (u < a.F2 && to < a.J) {
-    const bool lv = a.live ? (to < a.live[n]) : true;
-    T* row = (T*)a.X0 + ((long)to * a.N + n) * a.rld;
+    const bool lv = ROWS ? to < nlive : (a.live ? (to < a.live[n]) : true);
+    T* row = (T*)a.X0 + ((long)to * NR + n) * a.rld;
     T* dst = row + u * CH + half * 16;
 #pragma unroll
     for (int v = 0; v < 16 / V; ++v) {
@@ -241,10 +288,12 @@ __global__ void __launch_bounds__(256, 1) k_stream_conv2(StreamConv2Args a, int 
 // ============================================================================================================
 // lookahead over the window of rows [carry ctx-1 | chunk J][N][H]
 // ============================================================================================================
-template <typename T>
+// ROWS: x and y hold the N rows that run the recurrent stack this feed; carry / next are the pool's two buffers [ctx-1][S][H]
+template <typename T, bool ROWS>
 __global__ void __launch_bounds__(256) k_stream_lookahead(const T* __restrict__ x, const T* __restrict__ carry, T* __restrict__ next,
                                                            const float* __restrict__ w, const int* __restrict__ len,
-                                                           T* __restrict__ y, int N, int H, int ctx, int Jin, int off, int J) {
+                                                           T* __restrict__ y, int N, int H, int ctx, int Jin, int off, int J,
+                                                           const ds2_stream_row* __restrict__ rows, int S) {
   constexpr int V = Vec16<T>::N;
   const int hv = H / V, K = ctx - 1;
   const long nout = (long)J * N * hv, total = nout + (long)K * N * hv;
@@ -254,21 +303,42 @@ __global__ void __launch_bounds__(256) k_stream_lookahead(const T* __restrict__ 
     const int h0 = (int)(q % hv) * V;
     const long rest = q / hv;
     const int n = (int)(rest % N), t = (int)(rest / N);
-    const int ln = len ? min(max(len[n], 0), Jin) : Jin;
+    int ln, nlive = J, cs = N, cn = n;                     // cs, cn: the carry's row stride and this stream's row in it
+    bool fresh = false;
+    const T* cr = carry;
+    T* nx = next;
+    if constexpr (ROWS) {
+      const ds2_stream_row R = rows[n];
+      ln = min(max(R.cnt2, 0), Jin);
+      off = R.off3;
+      nlive = R.cnt3;
+      cs = S;
+      cn = R.slot;
+      fresh = (R.fresh & 4) != 0;
+      if (R.cur & 4) {
+        cr = next;
+        nx = const_cast<T*>(carry);
+      }
+    } else {
+      ln = len ? min(max(len[n], 0), Jin) : Jin;
+    }
     if (!is_out) {                                         // next[t] = V[ln + t], t < K
       const int p = ln + t;
-      const T* src = p < K ? carry + ((long)p * N + n) * H + h0 : x + ((long)(p - K) * N + n) * H + h0;
-      *reinterpret_cast<uint4*>(next + ((long)t * N + n) * H + h0) = *reinterpret_cast<const uint4*>(src);
+      const T* src = p < K ? cr + ((long)p * cs + cn) * H + h0 : x + ((long)(p - K) * N + n) * H + h0;
+      uint4 val = *reinterpret_cast<const uint4*>(src);
+      if (ROWS && fresh && p < K) val = make_uint4(0u, 0u, 0u, 0u);
+      *reinterpret_cast<uint4*>(nx + ((long)t * cs + cn) * H + h0) = val;
       continue;
     }
     float acc[V];
 #pragma unroll
     for (int i = 0; i < V; ++i) acc[i] = 0.f;
-    for (int k = 0; k < ctx; ++k) {
+    for (int k = (ROWS && t >= nlive) ? ctx : 0; k < ctx; ++k) {      // ROWS: rows t >= cnt3 are written as zeros
       const int p = off + t + k;
       if (p >= K + ln) break;                              // everything beyond the chunk is zero
+      if (ROWS && fresh && p < K) continue;                // fmaf(w, 0, acc) == acc
       float xv[V];
-      Vec16<T>::load(p < K ? carry + ((long)p * N + n) * H + h0 : x + ((long)(p - K) * N + n) * H + h0, xv);
+      Vec16<T>::load(p < K ? cr + ((long)p * cs + cn) * H + h0 : x + ((long)(p - K) * N + n) * H + h0, xv);
 #pragma unroll
       for (int i = 0; i < V; ++i) acc[i] = fmaf(w[(long)(h0 + i) * ctx + k], xv[i], acc[i]);
     }
@@ -286,14 +356,14 @@ inline bool conv_geometry(int f0, int& f1, int& f2) {
 
 inline long align256(long b) { return (b + 255) / 256 * 256; }
 
-template <typename T>
+template <typename T, bool ROWS>
 int stream_conv2_launch(const StreamConv2Args& a, hipStream_t st) {
   static bool attr[DS2_MAX_DEVICES];
   if (ds2_first_use_on_device(attr))
-    (void)hipFuncSetAttribute((const void*)k_stream_conv2<T>, hipFuncAttributeMaxDynamicSharedMemorySize, CT_SMEM);
+    (void)hipFuncSetAttribute((const void*)k_stream_conv2<T, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, CT_SMEM);
   const int ntiles = ds2_cdiv(a.J, CT_TB);
   dim3 grid(ntiles + 1, ds2_cdiv(a.F2, CT_UB), a.N);
-  hipLaunchKernelGGL(k_stream_conv2<T>, grid, dim3(256), CT_SMEM, st, a, ntiles);
+  hipLaunchKernelGGL((k_stream_conv2<T, ROWS>), grid, dim3(256), CT_SMEM, st, a, ntiles);
   DS2_CHECK_LAUNCH();
   return 0;
 }
@@ -347,11 +417,11 @@ int ds2_stream_conv1(int dtype, const float* x, const float* carry, float* next,
   const int ntiles = ds2_cdiv(J, C1_TB);
   dim3 grid(ntiles + 1, ds2_cdiv(f1, C1_FB), N);
   if (dtype == DS2_F32)
-    hipLaunchKernelGGL(k_stream_conv1<float>, grid, dim3(256), 0, st, x, carry, next, w1k, b1, scale, shift, len, live, (float*)y, N, Tc,
-                       off, J, F0_, f1, ntiles);
+    hipLaunchKernelGGL((k_stream_conv1<float, false>), grid, dim3(256), 0, st, x, carry, next, w1k, b1, scale, shift, len, live, (float*)y,
+                       N, Tc, off, J, F0_, f1, ntiles, nullptr);
   else
-    hipLaunchKernelGGL(k_stream_conv1<bf16_t>, grid, dim3(256), 0, st, x, carry, next, w1k, b1, scale, shift, len, live, (bf16_t*)y, N, Tc,
-                       off, J, F0_, f1, ntiles);
+    hipLaunchKernelGGL((k_stream_conv1<bf16_t, false>), grid, dim3(256), 0, st, x, carry, next, w1k, b1, scale, shift, len, live,
+                       (bf16_t*)y, N, Tc, off, J, F0_, f1, ntiles, nullptr);
   DS2_CHECK_LAUNCH();
   return 0;
 }
@@ -365,8 +435,8 @@ int ds2_stream_conv2(int dtype, const void* a1, const void* carry, void* next, c
   DS2_REQUIRE(N > 0 && N <= 65535 && Jin >= 0 && J >= 0 && off >= 0 && conv_geometry(F0_, f1, f2), DS2_ERR_ARG);
   DS2_REQUIRE(rld >= f2 * CH && rld % 16 == 0 && (long)J * N * rld < (1L << 31), DS2_ERR_ARG);
   DS2_REQUIRE(carry && next && carry != next && w2t && b2 && scale && shift && (a1 || Jin == 0) && (x0 || J == 0), DS2_ERR_ARG);
-  StreamConv2Args a{a1, carry, next, w2t, b2, scale, shift, len, live, x0, N, Jin, off, J, f1, f2, rld};
-  return dtype == DS2_F32 ? stream_conv2_launch<float>(a, st) : stream_conv2_launch<bf16_t>(a, st);
+  StreamConv2Args a{a1, carry, next, w2t, b2, scale, shift, len, live, x0, N, Jin, off, J, f1, f2, rld, nullptr, N};
+  return dtype == DS2_F32 ? stream_conv2_launch<float, false>(a, st) : stream_conv2_launch<bf16_t, false>(a, st);
 }
 
 int ds2_stream_lookahead(int dtype, const void* x, const void* carry, void* next, const float* w, const int* len, void* y, int N,
@@ -380,11 +450,67 @@ int ds2_stream_lookahead(int dtype, const void* x, const void* carry, void* next
   if (total == 0) return 0;
   const int grid = (int)(ds2_cdiv(total, 256) < 4096 ? ds2_cdiv(total, 256) : 4096);
   if (dtype == DS2_F32)
-    hipLaunchKernelGGL(k_stream_lookahead<float>, dim3(grid), dim3(256), 0, st, (const float*)x, (const float*)carry, (float*)next, w, len,
-                       (float*)y, N, H, ctx, Jin, off, J);
+    hipLaunchKernelGGL((k_stream_lookahead<float, false>), dim3(grid), dim3(256), 0, st, (const float*)x, (const float*)carry,
+                       (float*)next, w, len, (float*)y, N, H, ctx, Jin, off, J, nullptr, N);
   else
-    hipLaunchKernelGGL(k_stream_lookahead<bf16_t>, dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)carry, (bf16_t*)next, w,
-                       len, (bf16_t*)y, N, H, ctx, Jin, off, J);
+    hipLaunchKernelGGL((k_stream_lookahead<bf16_t, false>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)carry,
+                       (bf16_t*)next, w, len, (bf16_t*)y, N, H, ctx, Jin, off, J, nullptr, N);
+  DS2_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- the row-table entries: carry0 / carry1 are the two buffers of a stage's carries over the pool's S slots ----------------
+int ds2_stream_conv1_rows(int dtype, const float* x, float* carry0, float* carry1, const ds2_stream_row* rows, const float* w1k,
+                          const float* b1, const float* scale, const float* shift, void* y, int n_rows, int F0_, int Tc, int J,
+                          ds2_stream_t st_) {
+  hipStream_t st = (hipStream_t)st_;
+  DS2_REQUIRE(dtype == DS2_F32 || dtype == DS2_BF16, DS2_ERR_DTYPE);
+  int f1, f2;
+  DS2_REQUIRE(n_rows > 0 && n_rows <= 65535 && Tc >= 0 && J >= 0 && conv_geometry(F0_, f1, f2), DS2_ERR_ARG);
+  DS2_REQUIRE(rows && carry0 && carry1 && carry0 != carry1 && w1k && b1 && scale && shift && (x || Tc == 0) && (y || J == 0), DS2_ERR_ARG);
+  const int ntiles = ds2_cdiv(J, C1_TB);
+  dim3 grid(ntiles + 1, ds2_cdiv(f1, C1_FB), n_rows);
+  if (dtype == DS2_F32)
+    hipLaunchKernelGGL((k_stream_conv1<float, true>), grid, dim3(256), 0, st, x, carry0, carry1, w1k, b1, scale, shift, nullptr, nullptr,
+                       (float*)y, n_rows, Tc, 0, J, F0_, f1, ntiles, rows);
+  else
+    hipLaunchKernelGGL((k_stream_conv1<bf16_t, true>), grid, dim3(256), 0, st, x, carry0, carry1, w1k, b1, scale, shift, nullptr, nullptr,
+                       (bf16_t*)y, n_rows, Tc, 0, J, F0_, f1, ntiles, rows);
+  DS2_CHECK_LAUNCH();
+  return 0;
+}
+
+int ds2_stream_conv2_rows(int dtype, const void* a1, void* carry0, void* carry1, const ds2_stream_row* rows, const void* w2t,
+                          const float* b2, const float* scale, const float* shift, void* x0, int n_rows, int n_rnn, int F0_, int Jin,
+                          int J, int rld, ds2_stream_t st_) {
+  hipStream_t st = (hipStream_t)st_;
+  DS2_REQUIRE(dtype == DS2_F32 || dtype == DS2_BF16, DS2_ERR_DTYPE);
+  int f1, f2;
+  DS2_REQUIRE(n_rows > 0 && n_rows <= 65535 && n_rnn >= 0 && n_rnn <= n_rows && Jin >= 0 && J >= 0 && conv_geometry(F0_, f1, f2),
+              DS2_ERR_ARG);
+  DS2_REQUIRE(rld >= f2 * CH && rld % 16 == 0 && (long)J * n_rnn * rld < (1L << 31) && (J == 0) == (n_rnn == 0), DS2_ERR_ARG);
+  DS2_REQUIRE(rows && carry0 && carry1 && carry0 != carry1 && w2t && b2 && scale && shift && (a1 || Jin == 0) && (x0 || J == 0),
+              DS2_ERR_ARG);
+  StreamConv2Args a{a1, carry0, carry1, w2t, b2, scale, shift, nullptr, nullptr, x0, n_rows, Jin, 0, J, f1, f2, rld, rows, n_rnn};
+  return dtype == DS2_F32 ? stream_conv2_launch<float, true>(a, st) : stream_conv2_launch<bf16_t, true>(a, st);
+}
+
+int ds2_stream_lookahead_rows(int dtype, const void* x, void* carry0, void* carry1, const ds2_stream_row* rows, const float* w, void* y,
+                              int n_rnn, int S, int H, int ctx, int Jin, int J, ds2_stream_t st_) {
+  hipStream_t st = (hipStream_t)st_;
+  DS2_REQUIRE(dtype == DS2_F32 || dtype == DS2_BF16, DS2_ERR_DTYPE);
+  const int V = dtype == DS2_F32 ? 4 : 8;
+  DS2_REQUIRE(n_rnn > 0 && S >= n_rnn && H > 0 && H % V == 0 && ctx >= 1 && Jin >= 0 && J >= 0, DS2_ERR_ARG);
+  DS2_REQUIRE(rows && w && (x || Jin == 0) && (y || J == 0) && (ctx == 1 || (carry0 && carry1 && carry0 != carry1)), DS2_ERR_ARG);
+  const long total = ((long)J + ctx - 1) * n_rnn * (H / V);
+  if (total == 0) return 0;
+  const int grid = (int)(ds2_cdiv(total, 256) < 4096 ? ds2_cdiv(total, 256) : 4096);
+  if (dtype == DS2_F32)
+    hipLaunchKernelGGL((k_stream_lookahead<float, true>), dim3(grid), dim3(256), 0, st, (const float*)x, (const float*)carry0,
+                       (float*)carry1, w, nullptr, (float*)y, n_rnn, H, ctx, Jin, 0, J, rows, S);
+  else
+    hipLaunchKernelGGL((k_stream_lookahead<bf16_t, true>), dim3(grid), dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)carry0,
+                       (bf16_t*)carry1, w, nullptr, (bf16_t*)y, n_rnn, H, ctx, Jin, 0, J, rows, S);
   DS2_CHECK_LAUNCH();
   return 0;
 }

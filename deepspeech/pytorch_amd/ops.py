@@ -1568,3 +1568,70 @@ def stream_lookahead(x, carry, nxt, w, N, H, off, J, lens=None):
     call("ds2_stream_lookahead", dt(x), P(x) if Jin else C.c_void_p(0), P(carry), P(nxt), PF(w), P(lens), P(y) if J else C.c_void_p(0),
          N, H, ctx, Jin, off, J, S())
     return y
+
+
+# ---- ... for a pool of streams that start and end on their own (streaming.StreamPool) --------------
+STREAM_ROW_WORDS = 16      # int32 words of one ds2_stream_row: slot, src, cur, fresh, len, off1, cnt1, off2, cnt2, off3, cnt3, 5 reserved
+_STREAM_STAGING = PinnedRing()
+
+
+def stream_rows(rows, S, n_src, Tc, device):
+    """The row table of one feed on the device, through pinned memory in one queued copy.  rows: per batch row the 11 ints of a
+    ds2_stream_row (slot, src, cur, fresh, len, off1, cnt1, off2, cnt2, off3, cnt3), already in launch order (cnt2 descending).
+    Checks on the host what the kernels cannot refuse: distinct slots in [0, S), src in [0, n_src), len in [0, Tc], counts and
+    offsets >= 0, cnt3 > 0 only with cnt2 > 0.  Returns (table [n][16] int32, cnt2 [n] int32, slots [n] int64) device tensors,
+    views of one buffer."""
+    t = np.zeros((len(rows), STREAM_ROW_WORDS), dtype=np.int32)
+    if len(rows) == 0:
+        raise ValueError("a feed needs at least one row")
+    t[:, :11] = np.asarray(rows, dtype=np.int64).reshape(len(rows), 11)
+    slot, src, cur, fresh = t[:, 0], t[:, 1], t[:, 2], t[:, 3]
+    if slot.min() < 0 or slot.max() >= S or len(set(slot.tolist())) != len(rows):
+        raise ValueError("row slots must be distinct and lie in [0, %d), got %s" % (S, slot.tolist()))
+    if src.min() < 0 or src.max() >= n_src:
+        raise ValueError("source rows must lie in [0, %d), got %s" % (n_src, src.tolist()))
+    if ((cur | fresh) & ~7).any() or t[:, 4].min() < 0 or t[:, 4].max() > Tc or t[:, 5:11].min() < 0:
+        raise ValueError("bad row table (bits beyond the three stages, a length outside [0, %d] or a negative offset or count):\n%s"
+                         % (Tc, t[:, :11]))
+    cnt2 = t[:, 8]
+    if (np.diff(cnt2) > 0).any() or ((t[:, 10] > 0) & (cnt2 == 0)).any():
+        raise ValueError("rows must be ordered by cnt2 descending, and only a row with RNN frames has output frames: cnt2 %s, cnt3 %s"
+                         % (cnt2.tolist(), t[:, 10].tolist()))
+    n = len(rows)
+    pad = np.zeros((n * (STREAM_ROW_WORDS + 1)) % 2, dtype=np.int32)                 # the int64 slots start on 8 bytes
+    buf = _STREAM_STAGING.stage(device, [t.reshape(-1), cnt2, pad, slot.astype(np.int64).view(np.int32)])
+    o = n * STREAM_ROW_WORDS
+    return buf[:o].view(n, STREAM_ROW_WORDS), buf[o:o + n], buf[o + n + pad.size:].view(torch.int64)
+
+
+def stream_conv1_rows(x, carry, rows, w1k, b1, scale, shift, J, dtype):
+    """stream_conv1 by the row table: x (n_src, 1, F0, Tc) f32 as the caller holds it (row r reads x[src]), carry the pool's two
+    buffers [S][F0][10] f32, rows the device table [n][16].  Returns [n][F1][J][32] in `dtype`, in table order."""
+    _, _, F0, Tc = x.shape
+    n = rows.shape[0]
+    y = torch.empty((n, conv_rows(F0)[0], J, 32), dtype=dtype, device=x.device)
+    call("ds2_stream_conv1_rows", dt(dtype), PF(x) if Tc else C.c_void_p(0), PF(carry[0]), PF(carry[1]), P(rows), PF(w1k), PF(b1),
+         PF(scale), PF(shift), P(y) if J else C.c_void_p(0), n, F0, Tc, J, S())
+    return y
+
+
+def stream_conv2_rows(a1, carry, rows, n_rnn, w2t, b2, scale, shift, J, rld, F0=161, out=None):
+    """stream_conv2 by the row table: a1 [n][F1][Jin][32] (stream_conv1_rows' result), carry the pool's two buffers
+    [S][F1][10][32].  Returns the sequence layout of the first n_rnn rows, X0 [(j*n_rnn + r)][rld]."""
+    n, F1, Jin, _ = a1.shape
+    assert F1 == conv_rows(F0)[0] and carry[0].dtype == a1.dtype == carry[1].dtype == w2t.dtype and rows.shape[0] == n
+    x0 = torch.empty((J * n_rnn, rld), dtype=a1.dtype, device=a1.device) if out is None else out
+    assert tuple(x0.shape) == (J * n_rnn, rld) and x0.is_contiguous() and x0.dtype == a1.dtype
+    call("ds2_stream_conv2_rows", dt(a1), P(a1) if Jin else C.c_void_p(0), P(carry[0]), P(carry[1]), P(rows), P(w2t), PF(b2), PF(scale),
+         PF(shift), P(x0) if J else C.c_void_p(0), n, n_rnn, F0, Jin, J, rld, S())
+    return x0
+
+
+def stream_lookahead_rows(x, carry, rows, w, n_rnn, S_, H, J):
+    """stream_lookahead by the row table over its first n_rnn rows: x [Jin*n_rnn][H], carry the pool's two buffers [ctx-1][S_][H]
+    (None, None for ctx = 1).  Returns [J*n_rnn][H]."""
+    ctx, Jin = w.shape[1], x.shape[0] // n_rnn
+    y = torch.empty((J * n_rnn, H), dtype=x.dtype, device=x.device)
+    call("ds2_stream_lookahead_rows", dt(x), P(x) if Jin else C.c_void_p(0), P(carry[0]), P(carry[1]), P(rows), PF(w),
+         P(y) if J else C.c_void_p(0), n_rnn, S_, H, ctx, Jin, J, S())
+    return y

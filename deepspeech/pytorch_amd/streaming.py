@@ -21,7 +21,10 @@ carry their time context from feed to feed on the device (csrc/ds2_stream.hip), 
 concatenated per stream, are the one-shot eval ``forward`` of the whole utterance up to floating-point summation details.  A
 frame is emitted once nothing that a later feed brings can change it (``plan_feed``): with lookahead context C the first output
 arrives after 2 * C + 14 input frames (``latency_frames``; 54 frames = 0.54 s at C = 20) -- the model's latency, not the
-implementation's.  Streams start and end together; the last feed (``final=True``, or ``end()``) may be ragged."""
+implementation's.  Streams start and end together; the last feed (``final=True``, or ``end()``) may be ragged.
+
+``StreamPool`` is the exact mode for streams that start and end on their own: every stream has a slot with its own frame counter
+and plan, and a feed advances any subset of the open slots as one batch."""
 import collections
 
 import torch
@@ -234,3 +237,213 @@ class StreamingTranscriber:
         self._fed += chunk
         self._ended = final
         return list(self._text)
+
+
+# ---- a pool of streams that start and end on their own ----------------------------------------------
+RowPlan = collections.namedtuple("RowPlan", "plans off1 off2 off3 cnt1 cnt2 cnt3 J1 J2 J3 order n_rnn")
+
+
+def plan_rows(fed, lens, finals, ctx):
+    """One feed of streams that each follow their own plan.  Per row r: fed[r] input frames so far, a chunk of lens[r] >= 0 more,
+    finals[r] whether the utterance ends with it.  Returns per row plans[r] = plan_feed(fed[r], lens[r], ctx, finals[r]), its
+    window offsets off1..3 and the counts cnt1..3 = j*_new - j*_old; for the launch the maxima J1..3 of the counts, `order` (the
+    rows sorted by cnt2 descending, stable: what the recurrent stack takes) and n_rnn, the rows with cnt2 > 0 -- a prefix of
+    `order`; only they run the recurrent stack, the lookahead and the head."""
+    if not len(fed) == len(lens) == len(finals):
+        raise ValueError("plan_rows: %d / %d / %d entries" % (len(fed), len(lens), len(finals)))
+    plans = [plan_feed(g, c, ctx, f) for g, c, f in zip(fed, lens, finals)]
+    cnt = [[p.j1_new - p.j1_old for p in plans], [p.j2_new - p.j2_old for p in plans], [p.j3_new - p.j3_old for p in plans]]
+    assert all(c2 > 0 or c3 == 0 for c2, c3 in zip(cnt[1], cnt[2]))          # an output frame needs an RNN frame of the same feed
+    order = sorted(range(len(plans)), key=lambda r: -cnt[1][r])               # sorted() is stable
+    J = [max(c, default=0) for c in cnt]
+    return RowPlan(plans, [p.off1 for p in plans], [p.off2 for p in plans], [p.off3 for p in plans], cnt[0], cnt[1], cnt[2],
+                   J[0], J[1], J[2], order, sum(c > 0 for c in cnt[1]))
+
+
+class StreamPool:
+    """Exact chunked inference (``StreamingTranscriber(carry_context=True)``'s guarantee) for up to `capacity` streams that join,
+    advance and end whenever their callers do.  Every stream has a slot: its carries, its hidden state, its decoder stream and its
+    own frame counter.  A feed serves any subset of the open slots with chunks of any lengths as ONE batch -- one conv1, one conv2,
+    one recurrent stack over the rows that retire an RNN frame, one lookahead, one head, one decoder feed -- and per stream the
+    probabilities emitted over its feeds, concatenated, are the one-shot eval ``forward`` of that utterance alone."""
+
+    def __init__(self, model, decoder, capacity, max_frames=6000):
+        """model: a uni-directional DeepSpeech on a HIP device (run in eval mode, no autograd); decoder: a BeamCTCDecoder or
+        GreedyDecoder over its labels; max_frames bounds the output frames per stream of a beam decoder."""
+        if model.bidirectional:
+            raise ValueError("a StreamPool needs a uni-directional model: a reverse direction cannot be streamed exactly")
+        if int(capacity) < 1:
+            raise ValueError("capacity must be >= 1, got %s" % (capacity,))
+        self.model, self.decoder, self.capacity, self.max_frames = model, decoder, int(capacity), int(max_frames)
+        S = self.capacity
+        self.stream, self._state, self._h = None, None, None
+        self._open = [False] * S
+        self._fed, self._ended, self._text = [0] * S, [False] * S, [''] * S
+        self._cur, self._fresh = [0] * S, [7] * S          # per slot, bit s - 1: stage s's carry buffer / its carry reads as zero
+        self._h_zero = [True] * S                          # the slot's hidden state is the zero state of a new stream
+        self.last_output = {}                              # slot -> (cnt3, C) probabilities of the last feed that held the slot
+
+    # ---- slots ------------------------------------------------------------------------------------------------------------------
+    def open(self):
+        """A free slot with fresh state: zero hidden state, carries that read as zero, a reset decoder stream, no frames fed."""
+        if all(self._open):
+            raise ValueError("the pool is full: all %d slots are open" % self.capacity)
+        s = self._open.index(False)
+        self._open[s] = True
+        self._fed[s], self._ended[s], self._text[s], self._fresh[s] = 0, False, '', 7
+        self.last_output.pop(s, None)
+        if self.stream is not None:
+            self.stream.reset([s])
+        if self._h is not None and not self._h_zero[s]:
+            self._h[:, :, s].zero_()
+        self._h_zero[s] = True
+        return s
+
+    def close(self, slot):
+        """Frees the slot for the next ``open``."""
+        self._check_slots([slot])
+        self._open[int(slot)] = False
+
+    def frames(self, slot):
+        """output frames emitted so far for the slot's stream"""
+        self._check_slots([slot])
+        return self.stream.frames[int(slot)] if self.stream is not None else 0
+
+    @property
+    def latency_frames(self):
+        """input frames a stream must be fed before its first output frame: 2 * lookahead_context + 14"""
+        return 2 * int(self.model.lookahead[0].context) + 14
+
+    def _check_slots(self, slots):
+        sl = [int(s) for s in slots]
+        for s in sl:
+            if not 0 <= s < self.capacity or not self._open[s]:
+                raise ValueError("slot %d is not an open slot of this pool" % s)
+        if len(set(sl)) != len(sl):
+            raise ValueError("a slot appears twice: %s" % sl)
+        return sl
+
+    def finish(self, slot):
+        """(strings, offsets) of the slot's stream in the shape of one entry of ``decoder.decode``, for everything emitted so far"""
+        s = self._check_slots([slot])[0]
+        if self.stream is None or self.stream.frames[s] == 0:
+            return [''], [torch.zeros(0, dtype=torch.int)]
+        if isinstance(self.decoder, BeamCTCDecoder):
+            strings, offsets, _ = self.stream.result()
+            return strings[s], offsets[s]
+        return [self.stream.text[s]], [self.stream.offsets[s]]
+
+    def end(self, slots):
+        """The end of these streams' utterances as a final feed of nothing: every frame still held back is emitted."""
+        sl = self._check_slots(slots)
+        dev = next(self.model.parameters()).device
+        return self.feed(sl, torch.empty((len(sl), 1, self.model._F0, 0), dtype=torch.float32, device=dev), [0] * len(sl), final=sl)
+
+    # ---- the feed ---------------------------------------------------------------------------------------------------------------
+    def feed(self, slots, spect, lengths, final=()):
+        """spect: (len(slots), 1, F0, Tc) spectrogram chunks on the model's device, row i for slots[i] (any order); lengths[i] in
+        [0, Tc]: the valid input frames of row i; final: the slots whose utterance ends with this chunk.  Returns the transcript so
+        far of every slot in `slots`, in that order.  Only the fetch of the text waits for the device."""
+        from . import ops
+        m, S = self.model, self.capacity
+        sl = self._check_slots(slots)
+        fin = set(self._check_slots(final))
+        if not fin <= set(sl):
+            raise ValueError("final names slots that are not in this feed: %s" % sorted(fin - set(sl)))
+        if not sl:
+            return []
+        for s in sl:
+            if self._ended[s]:
+                raise ValueError("the stream of slot %d has ended (a final feed or end()); close() it and open() the next one" % s)
+        if spect.dim() != 4 or spect.shape[0] != len(sl) or spect.shape[1] != 1 or spect.shape[2] != m._F0:
+            raise ValueError("expected a (%d, 1, %d, Tc) spectrogram chunk, got %s" % (len(sl), m._F0, tuple(spect.shape)))
+        Tc = spect.shape[3]
+        lens = [int(v) for v in lengths]
+        if len(lens) != len(sl) or any(v < 0 or v > Tc for v in lens):
+            raise ValueError("lengths must be %d ints in [0, %d], got %s" % (len(sl), Tc, lens))
+        ctx, H, dev = int(m.lookahead[0].context), m._Hp, spect.device
+        rp = plan_rows([self._fed[s] for s in sl], lens, [s in fin for s in sl], ctx)
+        beam = isinstance(self.decoder, BeamCTCDecoder)
+        if beam:
+            for i, s in enumerate(sl):
+                have = self.stream.frames[s] if self.stream is not None else 0
+                if have + rp.cnt3[i] > self.max_frames:
+                    raise ValueError("slot %d: %d frames emitted + %d more pass max_frames=%d" % (s, have, rp.cnt3[i], self.max_frames))
+        if self.stream is None:
+            self.stream = self.decoder.stream(S, self.max_frames, dev) if beam else self.decoder.stream(S, dev)
+        dtype = m._stream_begin()
+        st = self._state
+        if st is None or st["dtype"] != dtype:
+            if st is not None and any(f != 7 for s, f in enumerate(self._fresh) if self._open[s]):
+                raise ValueError("the model's compute dtype changed while streams are open")
+            cin, cact, cla, buf = ops.stream_state_views(dtype, S, m._F0, H, ctx, dev)
+            st = self._state = dict(cin=cin, cact=cact, cla=cla, buf=buf, dtype=dtype)
+        J1, J2, J3, n_rnn, order = rp.J1, rp.J2, rp.J3, rp.n_rnn, rp.order
+        run1 = max(lens) > 0 or J1 > 0                    # the stages that launch, for all rows alike (StreamingTranscriber's rule)
+        run2 = J1 > 0 or J2 > 0
+        run3 = J2 > 0
+        table = [(sl[i], i, self._cur[sl[i]], self._fresh[sl[i]], lens[i], rp.off1[i], rp.cnt1[i], rp.off2[i], rp.cnt2[i], rp.off3[i],
+                  rp.cnt3[i]) for i in order]
+        x = spect.contiguous().float()
+        with torch.no_grad():
+            rows, rnn_lens, idx = ops.stream_rows(table, S, len(sl), Tc, dev)
+            w1k, b1, s1, h1, w2t, b2, s2, h2 = m.stream_front_weights(dtype)
+            a1 = probs = None
+            if run1:
+                a1 = ops.stream_conv1_rows(x, st["cin"], rows, w1k, b1, s1, h1, J1, dtype)
+                self._advance(sl, 1)
+            if run2:
+                if a1 is None:
+                    a1 = torch.empty((len(sl), m._F1, 0, 32), dtype=dtype, device=dev)
+                x0 = ops.stream_conv2_rows(a1, st["cact"], rows, n_rnn, w2t, b2, s2, h2, J2, m._rnn_ld, F0=m._F0)
+                self._advance(sl, 2)
+            if run3:
+                rslots = [sl[i] for i in order[:n_rnn]]
+                out_rows = self._run_rnn(x0, rnn_lens[:n_rnn], idx[:n_rnn], rslots, n_rnn, J2)
+                y = ops.stream_lookahead_rows(out_rows, st["cla"], rows, m.stream_lookahead_weight(), n_rnn, S, H, J3)
+                if ctx > 1:
+                    self._advance(rslots, 4)
+                if J3 > 0:
+                    probs = m.stream_head(y, n_rnn, J3)                      # (n_rnn, J3, C), rows in table order
+        for i, s in enumerate(sl):
+            self._fed[s] += lens[i]
+            self._ended[s] = s in fin
+            self.last_output.pop(s, None)
+        if probs is not None:
+            # the decoder streams are the pool's S slots: a slot that emitted nothing takes nothing (size 0)
+            full = probs.new_zeros((S, J3, probs.shape[2]))
+            full.index_copy_(0, idx[:n_rnn], probs)
+            sizes = [0] * S
+            for r, i in enumerate(order[:n_rnn]):
+                sizes[sl[i]] = rp.cnt3[i]
+                if rp.cnt3[i] > 0:
+                    self.last_output[sl[i]] = probs[r, :rp.cnt3[i]]
+            self.stream.feed(full, torch.tensor(sizes, dtype=torch.int))
+            text = self.stream.best()[0] if beam else self.stream.text
+            for s in sl:
+                self._text[s] = text[s]
+        return [self._text[s] for s in sl]
+
+    def _advance(self, slots, bit):
+        """a launched stage wrote its next carry for these slots: the other buffer holds it now, and it is no longer fresh"""
+        for s in slots:
+            self._cur[s] ^= bit
+            self._fresh[s] &= ~bit
+
+    def _run_rnn(self, x0, rnn_lens, idx, rslots, n_rnn, J2):
+        """The recurrent stack over the n_rnn rows that retire an RNN frame: their hidden states are gathered from the pool's one
+        state tensor ([layers * states][directions][S][width], fp32 as ``forward`` returns them) and scattered back."""
+        m = self.model
+        lstm = m._kind == "lstm"
+        hs = None
+        if not all(self._h_zero[s] for s in rslots):       # all new: no initial state, as the first feed of a one-shot session
+            g = self._h.index_select(2, idx)
+            hs = [(g[2 * l], g[2 * l + 1]) for l in range(g.shape[0] // 2)] if lstm else list(g.unbind(0))
+        out_rows, new_hs = m.stream_rnn(x0, rnn_lens, n_rnn, J2, hs)
+        new = torch.stack([t for pair in new_hs for t in pair] if lstm else list(new_hs))
+        if self._h is None:
+            self._h = new.new_zeros(new.shape[:2] + (self.capacity, new.shape[3]))
+        self._h.index_copy_(2, idx, new)
+        for s in rslots:
+            self._h_zero[s] = False
+        return out_rows

@@ -525,6 +525,46 @@ int ds2_stream_conv2(int dtype, const void* a1, const void* carry, void* next, c
 int ds2_stream_lookahead(int dtype, const void* x, const void* carry, void* next, const float* w, const int* len, void* y, int N,
                          int H, int ctx, int Jin, int off, int J, ds2_stream_t stream);
 
+/* ---- exact chunked inference for a pool of streams that start and end on their own ---------------
+ * The same three kernels with one ds2_stream_row per batch row instead of one off / J for the batch: every stream follows its
+ * own ds2_stream_plan, and a feed may hold any subset of the pool's S slots.  rows: [n_rows] on the device.  The carries of a
+ * stage are two buffers over all S slots, carry0 / carry1, in ds2_stream_state_bytes' layouts with N = S; bit s - 1 of `cur`
+ * says which of the two holds the slot's carry of stage s (1 = conv1, 2 = conv2, 3 = lookahead): the call reads that buffer's
+ * slot and writes the other one's, so the caller flips the bit of every row of a launched stage, and slots that are not in
+ * `rows` keep both buffers as they are.  Bit s - 1 of `fresh` makes the carry of stage s read as zero whatever the buffer holds
+ * (a stream's feeds until that stage has written its first carry).
+ * The window of stage s for row r is [carry K | the row's new positions], zero beyond: len input frames for conv1, cnt1 conv1
+ * activations for conv2, cnt2 RNN rows for the lookahead (each clamped to the launch's Tc / Jin).  Output frame j < cnt_s reads
+ * it from off_s + stride * j on, frames cnt_s <= j < J are written as zeros, J >= every row's cnt_s.  The next carry is
+ * V[new positions + i], i < K: a plain copy for a row with nothing new.
+ * ds2_stream_conv1_rows: x is the caller's tensor [.][F0][Tc], row r reads x[src]; y [n_rows][F1][J][32] in table order.
+ * ds2_stream_conv2_rows: a1 [n_rows][F1][Jin][32] (conv1_rows' y); x0[(j * n_rnn + r) * rld + ...] for the rows r < n_rnn,
+ *   which must be the rows with cnt2 > 0 (the table is ordered by cnt2 descending, what the recurrent stack takes); the rows
+ *   behind them only move their carry.  J = 0 exactly when n_rnn = 0.
+ * ds2_stream_lookahead_rows: x [Jin][n_rnn][H] and y [J][n_rnn][H] over the first n_rnn rows of the table; S is the slot
+ *   count of the carry buffers [ctx - 1][S][H].
+ * The table lives on the device, so the entries cannot check it: slot must lie in [0, S) and be distinct over the rows, src
+ * inside x, offsets >= 0 (ops.stream_rows checks them on the host).  Otherwise the arguments, limits and errors are those above. */
+typedef struct ds2_stream_row {
+  int32_t slot;        /* the stream's carry slot, 0 <= slot < S */
+  int32_t src;         /* the stream's row of x in the caller's tensor */
+  int32_t cur;         /* bit s - 1: the buffer that holds the carry of stage s */
+  int32_t fresh;       /* bit s - 1: the carry of stage s reads as zero */
+  int32_t len;         /* input frames of the row's chunk */
+  int32_t off1, cnt1;  /* conv1: window offset and output frames */
+  int32_t off2, cnt2;  /* conv2 (= RNN frames) */
+  int32_t off3, cnt3;  /* lookahead (= output frames) */
+  int32_t reserved[5]; /* 64 bytes a row */
+} ds2_stream_row;
+int ds2_stream_conv1_rows(int dtype, const float* x, float* carry0, float* carry1, const ds2_stream_row* rows, const float* w1k,
+                          const float* b1, const float* scale, const float* shift, void* y, int n_rows, int F0, int Tc, int J,
+                          ds2_stream_t stream);
+int ds2_stream_conv2_rows(int dtype, const void* a1, void* carry0, void* carry1, const ds2_stream_row* rows, const void* w2t,
+                          const float* b2, const float* scale, const float* shift, void* x0, int n_rows, int n_rnn, int F0, int Jin,
+                          int J, int rld, ds2_stream_t stream);
+int ds2_stream_lookahead_rows(int dtype, const void* x, void* carry0, void* carry1, const ds2_stream_row* rows, const float* w, void* y,
+                              int n_rnn, int S, int H, int ctx, int Jin, int J, ds2_stream_t stream);
+
 /* ---- character / word error counts on the device (the edit distances of validation.py:66-132, decoder.CharErrorRate /
  * WordErrorRate) ----
  * hyp: P rows of int32 labels, row p at hyp + p * hyp_stride with hyp_lens[p] labels; ref: the references' labels back to back,

@@ -7,6 +7,7 @@ forward sweep takes h0/c0 and returns hn/cn).  Prints one JSON line per model: p
     python tools/bench_stream.py [--seconds 30 --chunk 2.0 --stock]
     python tools/bench_stream.py --decode beam [--beam-width 100]
     python tools/bench_stream.py --carry [--decode greedy --chunk 0.2 --streams 1]
+    python tools/bench_stream.py --pool 8 [--chunk 0.2 --seconds 10 --pool-modes sessions,pool,session,pool_lockstep --pool-launches]
 
 With --decode greedy|beam the drop-in class runs inside a streaming.StreamingTranscriber: every chunk's output goes to the decoder
 stream on the device and the best transcript so far comes back per chunk (no output leaves the device, nothing is decoded twice).
@@ -15,6 +16,12 @@ stream on the device and the best transcript so far comes back per chunk (no out
 own, as in the reference) and carry_context=True (exact chunked inference: conv and lookahead context carried on the device, DESIGN.md
 section 3.6.2); the exact mode ends the utterance with end().  It also prints, for a small uni-directional GRU in bf16, the error of
 the streamed probabilities and of the one-shot forward against the fp64 oracle (e_stream, e_oneshot).
+
+--pool S times one TICK of S exact streams of the uni-directional model, a tick being one chunk for every open stream, stream k
+joining at tick k, in four modes: `sessions`, S StreamingTranscriber(carry_context=True) sessions of one
+stream each, fed one after another (the only way to serve staggered streams without a pool); `pool`, one StreamPool feed per tick;
+and, with all streams joining at tick 0, `session` (one lock-step session of S streams) against `pool_lockstep`.  Only the ticks
+in which all S streams are open and none ends are timed.  --pool-launches adds the device kernels of one such tick (torch.profiler).
 """
 import argparse
 import json
@@ -118,6 +125,95 @@ def carry_error():
                       "e_oneshot": err([one[n, :out_lens[n]] for n in range(2)])}))
 
 
+def _uni_lstm(dev):
+    from deepspeech.pytorch_amd import configs
+    from deepspeech.pytorch_amd.model import DeepSpeech
+    from oracle import ds2_torch_port as TP
+    cfg = dict(rnn_type="lstm", hidden_size=1024, hidden_layers=5, bidirectional=False, lookahead_context=20)
+    mc = configs.UniDirectionalConfig(rnn_type=configs.RNNType.lstm, hidden_size=1024, hidden_layers=5, lookahead_context=20)
+    m = DeepSpeech(configs.LABELS, mc, "bf16", configs.AdamConfig(), configs.SpectConfig())
+    m.load_state_dict({k: v.clone() for k, v in TP.random_state(cfg, 0).items()}, strict=True)
+    return m.to(dev).eval()
+
+
+def run_pool(a):
+    """--pool: see the module docstring.  One JSON line per mode."""
+    from deepspeech.pytorch_amd import configs, decoder as D, streaming
+    dev, S, tc = "cuda", a.pool, int(a.chunk * 100)
+    nch = int(a.seconds * 100) // tc
+    m = _uni_lstm(dev)
+    mk_dec = lambda: D.BeamCTCDecoder(configs.LABELS, beam_width=a.beam_width) if a.decode == "beam" else D.GreedyDecoder(configs.LABELS)
+    audio = torch.from_numpy(np.random.RandomState(0).standard_normal((S, 1, 161, nch * tc)).astype(np.float32)).to(dev)
+    piece = lambda k, j: audio[k:k + 1, :, :, j * tc:(j + 1) * tc]
+    max_frames = nch * tc // 2 + 2
+
+    def ticks_of(starts):
+        """per tick the streams that are open, (stream, its chunk index), and whether the tick is timed"""
+        out = []
+        for t in range(max(starts) + nch):
+            rows = [(k, t - starts[k]) for k in range(S) if 0 <= t - starts[k] < nch]
+            out.append((rows, len(rows) == S and all(j < nch - 1 for _, j in rows)))
+        return out
+
+    def measure(mode):
+        starts = list(range(S)) if mode in ("sessions", "pool") else [0] * S
+        plan = ticks_of(starts)
+        batches = [torch.cat([piece(k, j) for k, j in rows]).contiguous() for rows, _ in plan]      # the caller's batch, not timed
+        if mode == "sessions":
+            sess = [streaming.StreamingTranscriber(m, mk_dec(), max_frames=max_frames, carry_context=True) for _ in range(S)]
+            xs = [[piece(k, j).contiguous() for k, j in rows] for rows, _ in plan]
+        elif mode == "session":
+            sess = streaming.StreamingTranscriber(m, mk_dec(), max_frames=max_frames, carry_context=True)
+        else:
+            pool = streaming.StreamPool(m, mk_dec(), S, max_frames=max_frames)
+        lat, launches = [], None
+        for r in range(a.reps + 1 + int(a.pool_launches)):
+            if mode == "sessions":
+                for st in sess:
+                    st.reset()
+            elif mode == "session":
+                sess.reset()
+            else:
+                slot = {}
+            prof_tick = next(i for i, (_, timed) in enumerate(plan) if timed) + 2 if a.pool_launches and r == a.reps + 1 else -1
+            for i, (rows, timed) in enumerate(plan):
+                if i == prof_tick:
+                    prof = torch.profiler.profile(activities=[torch.profiler.ProfilerActivity.CUDA])
+                    prof.__enter__()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if mode == "sessions":
+                    for x, (k, j) in zip(xs[i], rows):
+                        sess[k].feed(x, [tc], final=(j == nch - 1))
+                elif mode == "session":
+                    sess.feed(batches[i], [tc] * S, final=(rows[0][1] == nch - 1))
+                else:
+                    for k, j in rows:
+                        if j == 0:
+                            slot[k] = pool.open()
+                    pool.feed([slot[k] for k, _ in rows], batches[i], [tc] * len(rows), final=[slot[k] for k, j in rows if j == nch - 1])
+                    for k, j in rows:
+                        if j == nch - 1:
+                            pool.close(slot[k])
+                torch.cuda.synchronize()
+                if i == prof_tick:
+                    prof.__exit__(None, None, None)
+                    launches = sum(e.count for e in prof.key_averages() if e.device_type == torch.autograd.DeviceType.CUDA)
+                elif timed and 0 < r <= a.reps:
+                    lat.append(time.perf_counter() - t0)
+        lat = np.array(lat)
+        print(json.dumps({"metric": "one tick of S exact streams (every open stream advances one chunk)", "mode": mode, "streams": S,
+                          "model": "uni-LSTM-1024x5+lookahead", "decode": a.decode or "greedy", "chunk_seconds": a.chunk,
+                          "chunks_per_stream": nch, "ticks_timed": int(lat.size), "ms_per_tick_median": round(float(np.median(lat)) * 1e3, 3),
+                          "ms_per_tick_p95": round(float(np.percentile(lat, 95)) * 1e3, 3), "device_kernels_per_tick": launches,
+                          "dtype": "bf16"}), flush=True)
+
+    for mode in a.pool_modes.split(","):
+        if mode not in ("sessions", "pool", "session", "pool_lockstep"):
+            raise SystemExit("unknown --pool-modes entry %r" % mode)
+        measure(mode)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=30.0)
@@ -128,7 +224,12 @@ def main():
     ap.add_argument("--beam-width", type=int, default=100)
     ap.add_argument("--carry", action="store_true", help="time a session feed with and without carry_context (uni-directional model)")
     ap.add_argument("--streams", type=int, default=1, help="--carry: streams fed in lock step")
+    ap.add_argument("--pool", type=int, default=0, help="time one tick of this many exact streams (StreamPool and its baselines)")
+    ap.add_argument("--pool-modes", default="sessions,pool,session,pool_lockstep")
+    ap.add_argument("--pool-launches", action="store_true", help="--pool: also count the device kernels of one tick")
     a = ap.parse_args()
+    if a.pool:
+        return run_pool(a)
     from deepspeech.pytorch_amd import configs
     from deepspeech.pytorch_amd.model import DeepSpeech
     from oracle import ds2_torch_port as TP
