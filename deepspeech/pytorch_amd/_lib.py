@@ -12,7 +12,7 @@ LIB_PATH = os.path.join(HERE, "libds2hip.so")
 F32, BF16 = 0, 1
 CELL_GRU, CELL_LSTM, CELL_RNN_TANH = 0, 1, 2
 
-_vp, _i, _l, _f, _ll = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_longlong
+_vp, _i, _l, _f, _ll, _d = C.c_void_p, C.c_int, C.c_long, C.c_float, C.c_longlong, C.c_double
 
 # name -> (restype, [argtypes]); mirrors include/ds2hip.h one to one (tests check every symbol is exported)
 SIGNATURES = {
@@ -81,6 +81,12 @@ SIGNATURES = {
     "ds2_spect_ws_bytes": (_l, [_i, _i]),
     "ds2_spectrogram": (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "ds2_spectrogram_aug": (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "ds2_spect_running_ws_bytes": (_l, [_i, _i]),
+    "ds2_spectrogram_running": (_i, [_vp, _l, _vp, _i, _i, _vp, _i, _d, _d, _d, _d, _vp, _vp, _i, _vp, _i, _vp, _i, _vp, _i, _vp, _vp]),
+    "ds2_spect_stream_plan": (_i, [_l, _i, _i, _vp]),
+    "ds2_spect_stream_state_bytes": (_l, [_i]),
+    "ds2_spect_stream_ws_bytes": (_l, [_i, _i, _i]),
+    "ds2_spect_stream_feed": (_i, [_vp, _l, _vp, _i, _i, _i, _i, _vp, _i, _d, _d, _d, _d, _vp, _vp, _vp, _vp]),
     "ds2_spec_augment_coef": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "ds2_spec_augment": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "ds2_wsola_segments": (_i, [_i, _f]),

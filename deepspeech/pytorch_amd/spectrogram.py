@@ -12,6 +12,7 @@ The reference's STFT lives in a third-party dependency that is not vendored and 
 ``center=True`` padding is zeros in librosa >= 0.10 (``pad_mode="constant"``, the default here) and reflection before
 (``pad_mode="reflect"`` = ``np.pad(y, 160, "reflect")`` for every length >= 1: a clip shorter than the pad is folded as often as
 it takes, a single sample repeats)."""
+import collections
 import math
 
 import numpy as np
@@ -49,9 +50,34 @@ def dft_basis(window):
     return np.concatenate([np.cos(ang) * w, -np.sin(ang) * w], 0).astype(np.float32)
 
 
+WavePlan = collections.namedtuple("WavePlan", "frames_before emit carried window new_carry first")
+
+
+def plan_wave(samples_before, n_new, final=False):
+    """ds2_spect_stream_plan: after `samples_before` samples of a stream, a feed of `n_new` more (final: the utterance ends with
+    it).  G samples complete G // 160 frames -- frame t covers samples [160 t - 160, 160 t + 160) -- and the end completes
+    1 + G // 160, so the feed emits the difference: possibly nothing, possibly one frame from no new samples (the flush).  The
+    feed's window is [carried | new | 160 zeros if final]: `carried` = 160 + samples_before % 160 samples in front of the new ones
+    (the left centre padding while it is in reach), `window` its length, `new_carry` the samples behind the last emitted frame's
+    hop that the next feed needs (at most 319; 0 after a final feed), `first` the clip position of the window's first sample."""
+    G0, n = int(samples_before), int(n_new)
+    if G0 < 0 or n < 0:
+        raise ValueError("plan_wave: samples_before and n_new must be >= 0")
+    f0, G1 = G0 // HOP, G0 + n
+    f1 = 1 + G1 // HOP if final else G1 // HOP
+    carried = HOP + G0 % HOP
+    window = carried + n + (HOP if final else 0)
+    return WavePlan(f0, f1 - f0, carried, window, 0 if final else window - HOP * (f1 - f0), HOP * f0 - HOP)
+
+
 class SpectrogramFrontEnd:
-    def __init__(self, spect_cfg=None, normalize=True, pad_mode="constant", spec_augment=None, rng=None, wave_augment=None):
-        """spec_augment: an ``augment.SpecAugment`` (None = its defaults) used by calls with ``augment=True``; rng: the
+    def __init__(self, spect_cfg=None, normalize=True, pad_mode="constant", spec_augment=None, rng=None, wave_augment=None,
+                 running_floor=1e-5, running_prior=None):
+        """normalize: True = (x - mean) / std over the whole utterance (the reference's), False = raw log-magnitudes, "running" =
+        the causal mode: frame t is normalised with the statistics of frames 0..t, which is what
+        ``stream()`` can reproduce bit for bit while the audio arrives.  running_floor: the mode's lower bound of the standard
+        deviation (digital silence gives zeros, not NaN); running_prior: (mean, std, frames) pseudo-counts the statistics start
+        from, None = none.  spec_augment: an ``augment.SpecAugment`` (None = its defaults) used by calls with ``augment=True``; rng: the
         numpy.random.Generator its draws come from (None = a fresh default_rng()).  wave_augment: an ``augment.WaveAugment``
         (None = none) applied to the waveforms of EVERY call, as the reference's loader applies tempo / gain / noise whenever its
         configuration asks for them; its draws come from rng too, before those of SpecAugment."""
@@ -63,7 +89,16 @@ class SpectrogramFrontEnd:
         if pad_mode not in ("constant", "reflect"):
             raise ValueError("pad_mode must be 'constant' (librosa >= 0.10) or 'reflect'")
         self.window = getattr(spect_cfg, "window", "hamming")
-        self.normalize, self.reflect = bool(normalize), pad_mode == "reflect"
+        if isinstance(normalize, str) and normalize != "running":
+            raise ValueError("normalize must be True, False or 'running', got %r" % (normalize,))
+        self.running = normalize == "running"
+        self.normalize, self.reflect = "running" if self.running else bool(normalize), pad_mode == "reflect"
+        self.running_floor = float(running_floor)
+        if not self.running_floor > 0.0:
+            raise ValueError("running_floor must be > 0, got %r" % (running_floor,))
+        self.running_prior = (0.0, 0.0, 0.0) if running_prior is None else tuple(float(v) for v in running_prior)
+        if len(self.running_prior) != 3 or not (self.running_prior[1] >= 0.0 and 0.0 <= self.running_prior[2] < 1e9):
+            raise ValueError("running_prior must be (mean, std >= 0, frames >= 0), got %r" % (running_prior,))
         self.spec_augment = spec_augment if spec_augment is not None else SpecAugment()
         self.rng = rng if rng is not None else np.random.default_rng()
         self._basis = {}
@@ -96,8 +131,6 @@ class SpectrogramFrontEnd:
             return self._call_wave_augmented(wav, ns, augment)
         Tmax = 1 + Lm // HOP
         out = torch.empty((N, 1, N_BIN, Tmax), dtype=torch.float32, device=wav.device)
-        ws = torch.empty(query("ds2_spect_ws_bytes", N, Lm), dtype=torch.uint8, device=wav.device)
-        basis = self._basis_on(wav.device)
         ns_dev = ns.to(wav.device)       # held in a local until the launch is enqueued (a temporary would be freed -- and its block
         #                                  possibly re-used by the basis upload -- before the kernels read it)
         frames = 1 + ns.to(torch.int64) // HOP
@@ -106,14 +139,31 @@ class SpectrogramFrontEnd:
             draws = sa.draw(frames.numpy(), N_BIN, self.rng)
             warp, fmask, tmask = self.upload_draws(draws, wav.device)
             self.last_coef = torch.empty((N, 3), dtype=torch.float32, device=wav.device)
-            call("ds2_spectrogram_aug", ops.P(wav), wav.stride(0), ops.P(ns_dev), N, Lm, ops.P(basis),
-                 1 if self.reflect else 0, 1 if self.normalize else 0, ops.P(out), ops.P(ws), ops.P(warp), sa.W,
-                 ops.P(fmask), draws[1].shape[1], ops.P(tmask), draws[2].shape[1], ops.P(self.last_coef), ops.S())
+            self._launch(wav, ns_dev, N, Lm, out, (warp, sa.W, fmask, draws[1].shape[1], tmask, draws[2].shape[1], self.last_coef))
         else:
-            call("ds2_spectrogram", ops.P(wav), wav.stride(0), ops.P(ns_dev), N, Lm, ops.P(basis),
-                 1 if self.reflect else 0, 1 if self.normalize else 0, ops.P(out), ops.P(ws), ops.S())
+            self._launch(wav, ns_dev, N, Lm, out, None)
         pct = (frames.to(torch.float64) / float(Tmax)).to(torch.float32)      # _collate_fn: seq_length / float(max_seqlength)
         return out, pct, frames
+
+    def _launch(self, wav, ns_dev, N, Lm, out, aug):
+        """The spectrogram call in the front-end's normalisation mode.  aug: None, or (warp draws, W, frequency masks, their count
+        per clip, time masks, their count, coefficients out) for the call with SpecAugment folded in."""
+        dev = wav.device
+        basis = self._basis_on(dev)
+        head = (ops.P(wav), wav.stride(0), ops.P(ns_dev), N, Lm, ops.P(basis), 1 if self.reflect else 0)
+        if self.running:
+            ws = torch.empty(query("ds2_spect_running_ws_bytes", N, Lm), dtype=torch.uint8, device=dev)
+            tail = (ops.P(None), 0, ops.P(None), 0, ops.P(None), 0, ops.P(None)) if aug is None else \
+                (ops.P(aug[0]), aug[1], ops.P(aug[2]), aug[3], ops.P(aug[4]), aug[5], ops.P(aug[6]))
+            call("ds2_spectrogram_running", *head, self.running_floor, *self.running_prior, ops.P(out), ops.P(ws),
+                 0 if aug is None else 1, *tail, ops.S())
+            return
+        ws = torch.empty(query("ds2_spect_ws_bytes", N, Lm), dtype=torch.uint8, device=dev)
+        head += (1 if self.normalize else 0, ops.P(out), ops.P(ws))
+        if aug is None:
+            call("ds2_spectrogram", *head, ops.S())
+        else:
+            call("ds2_spectrogram_aug", *head, ops.P(aug[0]), aug[1], ops.P(aug[2]), aug[3], ops.P(aug[4]), aug[5], ops.P(aug[6]), ops.S())
 
     def _call_wave_augmented(self, wav, ns, augment, wd=None):
         """__call__ with the waveform augmentations in front: tempo (ds2_wsola), then gain / noise (ds2_wave_energy +
@@ -141,19 +191,20 @@ class SpectrogramFrontEnd:
             wav = ops.wave_mix(wav, ns_dev, gain, level, bank, noise_off, noise_start)
         self.last_wave = (wd, offsets)
         out = torch.empty((N, 1, N_BIN, Tmax), dtype=torch.float32, device=dev)
-        ws = torch.empty(query("ds2_spect_ws_bytes", N, Lm), dtype=torch.uint8, device=dev)
-        basis = self._basis_on(dev)
-        head = (ops.P(wav), wav.stride(0), ops.P(ns_dev), N, Lm, ops.P(basis), 1 if self.reflect else 0, 1 if self.normalize else 0,
-                ops.P(out), ops.P(ws))
         if augment:
             warp, fmask, tmask = views[6:]
             self.last_coef = torch.empty((N, 3), dtype=torch.float32, device=dev)
-            call("ds2_spectrogram_aug", *head, ops.P(warp), sa.W, ops.P(fmask), sdraws[1].shape[1], ops.P(tmask), sdraws[2].shape[1],
-                 ops.P(self.last_coef), ops.S())
+            self._launch(wav, ns_dev, N, Lm, out, (warp, sa.W, fmask, sdraws[1].shape[1], tmask, sdraws[2].shape[1], self.last_coef))
         else:
-            call("ds2_spectrogram", *head, ops.S())
+            self._launch(wav, ns_dev, N, Lm, out, None)
         pct = (frames.to(torch.float64) / float(Tmax)).to(torch.float32)
         return out, pct, frames
+
+    def stream(self, capacity, device):
+        """A streaming handle over `capacity` slots (``SpectStream``): audio fed in chunks of any lengths gives the frames of this
+        front-end's one-shot call on the whole clip, bit for bit.  Needs a causal front-end: zero centre padding and
+        normalize="running" or False."""
+        return SpectStream(self, capacity, device)
 
     @staticmethod
     def upload_draws(draws, dev):
@@ -211,3 +262,81 @@ class SpectrogramFrontEnd:
         target_sizes = torch.tensor([len(t) for t in tg], dtype=torch.int32)
         targets = torch.cat(tg) if tg else torch.zeros(0, dtype=torch.int64)
         return inputs, targets, pct, target_sizes
+
+
+SPECT_ROW_WORDS = 8        # int32 words of one ds2_spect_stream_row: slot, src, carried, n_new, frames_before, emit, final, fresh
+_ROW_STAGING = ops.PinnedRing()
+
+
+class SpectStream:
+    """The streaming form of a ``SpectrogramFrontEnd`` (csrc/ds2_spect.hip, ds2_spect_stream_feed): per slot the device keeps the
+    samples that frames not yet complete need and the running statistics; the host keeps the sample count, from which every count
+    of a feed follows in closed form (``plan_wave``), so nothing is read back."""
+
+    def __init__(self, front_end, capacity, device):
+        if front_end.reflect:
+            raise ValueError("streaming needs pad_mode='constant': reflect padding reads samples that have not arrived")
+        if front_end.normalize is True:
+            raise ValueError("streaming needs normalize='running' (or False): the mean and the standard deviation of the whole "
+                             "utterance are not causal")
+        if front_end.wave_augment is not None and front_end.wave_augment.active:
+            raise ValueError("streaming takes the audio as it arrives: a front-end with wave_augment cannot be streamed")
+        if int(capacity) < 1:
+            raise ValueError("capacity must be >= 1, got %s" % (capacity,))
+        self.front_end, self.capacity, self.device = front_end, int(capacity), torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        S = self.capacity
+        self._state = torch.zeros(query("ds2_spect_stream_state_bytes", S), dtype=torch.uint8, device=self.device)
+        self.samples, self.ended, self._fresh = [0] * S, [False] * S, [True] * S
+
+    def reset(self, slots=None):
+        """These slots (None = all) start a new stream: their carry and statistics read as empty from the next feed on; nothing
+        is launched."""
+        for s in (range(self.capacity) if slots is None else [int(v) for v in slots]):
+            if not 0 <= s < self.capacity:
+                raise ValueError("slot %d is not a slot of this stream (capacity %d)" % (s, self.capacity))
+            self.samples[s], self.ended[s], self._fresh[s] = 0, False, True
+
+    def frames(self, slot):
+        """frames emitted so far for the slot's stream"""
+        s = int(slot)
+        return 1 + self.samples[s] // HOP if self.ended[s] else self.samples[s] // HOP
+
+    def feed(self, slots, wav, nsamples, final=()):
+        """wav: [len(slots)][L] float32 on the device, row i = the nsamples[i] >= 0 new samples of slots[i]; final: the slots
+        whose utterance ends with this feed.  Returns (spect (len(slots), 1, 161, Tc) float32 with Tc the largest count of new
+        frames -- possibly 0 --, frames [len(slots)] ints): row i holds frames[i] new frames, zero beyond them."""
+        fe, S = self.front_end, self.capacity
+        sl, fin = [int(s) for s in slots], set(int(s) for s in final)
+        if not sl or len(set(sl)) != len(sl) or any(not 0 <= s < S for s in sl):
+            raise ValueError("slots must be distinct and lie in [0, %d), got %s" % (S, sl))
+        if not fin <= set(sl):
+            raise ValueError("final names slots that are not in this feed: %s" % sorted(fin - set(sl)))
+        ns = [int(v) for v in nsamples]
+        if wav.dim() != 2 or wav.shape[0] != len(sl) or len(ns) != len(sl) or any(v < 0 or v > wav.shape[1] for v in ns):
+            raise ValueError("expected a [%d][L] waveform chunk and %d sample counts in [0, L], got %s and %s"
+                             % (len(sl), len(sl), tuple(wav.shape), ns))
+        for s in sl:
+            if self.ended[s]:
+                raise ValueError("the stream of slot %d has ended (a final feed); reset it first" % s)
+        if not wav.is_cuda or wav.device != self.device:
+            raise Ds2HipError("SpectStream needs the waveforms on %s; there is no CPU path" % self.device)
+        wav = wav.float()
+        if wav.shape[1] and wav.stride(1) != 1:
+            wav = wav.contiguous()
+        plans = [plan_wave(self.samples[s], n, s in fin) for s, n in zip(sl, ns)]
+        table = np.array([(s, i, 0 if self._fresh[s] else p.carried, n, p.frames_before, p.emit, int(s in fin), int(self._fresh[s]))
+                          for i, (s, n, p) in enumerate(zip(sl, ns, plans))], dtype=np.int32)
+        assert all(self.samples[s] == 0 for s in sl if self._fresh[s]) and all(0 <= p.new_carry < N_FFT for p in plans)
+        max_new, Tc = max(ns), max(p.emit for p in plans)
+        rows = _ROW_STAGING.stage(self.device, [table.reshape(-1)])
+        out = torch.empty((len(sl), 1, N_BIN, Tc), dtype=torch.float32, device=self.device)
+        ws = torch.empty(query("ds2_spect_stream_ws_bytes", len(sl), max_new, Tc), dtype=torch.uint8, device=self.device)
+        call("ds2_spect_stream_feed", ops.P(wav) if max_new else ops.P(None), wav.stride(0) if max_new else 0, ops.P(rows), len(sl),
+             max_new, Tc, S, ops.P(fe._basis_on(self.device)), 2 if fe.running else 0, fe.running_floor, *fe.running_prior,
+             ops.P(self._state), ops.P(out) if Tc else ops.P(None), ops.P(ws), ops.S())
+        for s, n in zip(sl, ns):
+            self.samples[s] += n
+            self.ended[s], self._fresh[s] = s in fin, False
+        return out, [p.emit for p in plans]

@@ -21,7 +21,9 @@ carry their time context from feed to feed on the device (csrc/ds2_stream.hip), 
 concatenated per stream, are the one-shot eval ``forward`` of the whole utterance up to floating-point summation details.  A
 frame is emitted once nothing that a later feed brings can change it (``plan_feed``): with lookahead context C the first output
 arrives after 2 * C + 14 input frames (``latency_frames``; 54 frames = 0.54 s at C = 20) -- the model's latency, not the
-implementation's.  Streams start and end together; the last feed (``final=True``, or ``end()``) may be ragged.
+implementation's.  Streams start and end together; the last feed (``final=True``, or ``end()``) may be ragged.  ``feed_wave`` takes
+raw audio in this mode too: the front-end's running normalisation is causal (``SpectrogramFrontEnd(normalize="running")``,
+DESIGN.md section 3.6.4) and its streaming form gives the one-shot spectrogram's frames bit for bit however the audio is cut.
 
 ``StreamPool`` is the exact mode for streams that start and end on their own: every stream has a slot with its own frame counter
 and plan, and a feed advances any subset of the open slots as one batch."""
@@ -71,6 +73,7 @@ class StreamingTranscriber:
             raise ValueError("carry_context=True needs a uni-directional model: a reverse direction cannot be streamed exactly")
         self._state = None                 # the carries (allocated at the first feed)
         self._fed, self._ended, self._text = 0, False, None
+        self._wave, self._source = None, None   # exact mode: the front-end's streaming handle; what the utterance is fed with
         self.last_output = None            # exact mode: (probabilities (N, J, C), valid frames per stream) of the last feed, or None
 
     def _open(self, N, device):
@@ -99,6 +102,9 @@ class StreamingTranscriber:
         (descending, as ``forward`` takes them)."""
         m = self.model
         if self.carry_context:
+            if self._source == "wave":
+                raise ValueError("this utterance is fed with feed_wave; spectrogram chunks cannot be mixed in before reset()")
+            self._source = "spect"
             return self._feed_exact(spect, lengths, bool(final))
         if final:
             raise ValueError("final=True is a carry_context=True feed; without it every feed stands on its own")
@@ -116,17 +122,54 @@ class StreamingTranscriber:
         self.stream.feed(out, out_lens)                # (N, T', C) stays on the device
         return self.best()
 
-    def feed_wave(self, wav, nsamples):
-        """wav: [N][Lmax] waveform chunk on the device, nsamples: [N] ints.  The chunk's spectrogram is computed and normalised on
-        its own by the front end, then fed."""
+    def feed_wave(self, wav, nsamples, final=False):
+        """wav: [N][Lmax] waveform chunk on the device, nsamples: [N] ints.  Without carry_context the chunk's spectrogram is
+        computed and normalised on its own by the front end, then fed.  carry_context: the chunk goes through the front-end's
+        streaming form (running normalisation, ``SpectrogramFrontEnd.stream``) and the frames it completes are fed exactly; every
+        stream brings the same sample count (>= 0) unless final=True, the last feed of the utterance, whose counts may be ragged
+        (descending).  A feed that completes no frame only buffers and returns the text so far."""
         if self.carry_context:
-            raise ValueError("feed_wave is not available with carry_context=True: normalising the whole utterance's spectrogram is "
-                             "not causal and normalising each chunk is not what the one-shot forward sees; feed spectrogram chunks")
+            return self._feed_wave_exact(wav, nsamples, bool(final))
+        if final:
+            raise ValueError("final=True is a carry_context=True feed; without it every feed stands on its own")
         if self.front_end is None:
             from .spectrogram import SpectrogramFrontEnd
             self.front_end = SpectrogramFrontEnd(getattr(self.model, "spect_cfg", None))
         inputs, _, frames = self.front_end(wav, nsamples)
         return self.feed(inputs, frames.to(torch.int))
+
+    def _feed_wave_exact(self, wav, nsamples, final):
+        if self._source == "spect":
+            raise ValueError("this utterance is fed with spectrogram chunks; feed_wave cannot be mixed in before reset()")
+        if self._ended:
+            raise ValueError("the utterance has ended (a final feed or end()); reset() starts the next one")
+        if not wav.is_cuda:
+            raise ValueError("feed_wave needs the waveform chunk on the model's HIP device, got a %s tensor: the streaming front-end "
+                             "has no CPU path" % wav.device)
+        if self.front_end is None:
+            from .spectrogram import SpectrogramFrontEnd
+            self.front_end = SpectrogramFrontEnd(getattr(self.model, "spect_cfg", None), normalize="running")
+        if self.front_end.normalize is True:
+            raise ValueError("carry_context=True needs a causal front-end: normalize=True takes the mean and the standard deviation "
+                             "of the whole utterance, which a stream does not have yet; build it with normalize='running'")
+        ns = [int(v) for v in nsamples]
+        N = wav.shape[0] if wav.dim() == 2 else -1
+        if N < 1 or len(ns) != N:
+            raise ValueError("expected a [N][L] waveform chunk and N sample counts, got %s and %s" % (tuple(wav.shape), ns))
+        if not final and any(v != ns[0] for v in ns):
+            raise ValueError("a feed that is not final needs the same sample count for every stream, got %s" % ns)
+        if final and any(a < b for a, b in zip(ns, ns[1:])):
+            raise ValueError("the final feed's sample counts must descend, got %s" % ns)
+        if self._wave is None:
+            self._wave = self.front_end.stream(N, wav.device)
+        elif N != self._wave.capacity:
+            raise ValueError("this session has %d streams, the chunk has %d" % (self._wave.capacity, N))
+        spect, frames = self._wave.feed(range(N), wav, ns, final=range(N) if final else ())
+        self._source = "wave"
+        if not final and frames[0] == 0:
+            self.last_output = None
+            return list(self._text) if self._text is not None else [''] * N
+        return self._feed_exact(spect, frames, final)
 
     def best(self):
         """the best transcript so far per stream"""
@@ -156,15 +199,21 @@ class StreamingTranscriber:
             self._state["buf"].zero_()
             self._state["cur"] = [0, 0, 0]
         self._fed, self._ended, self.last_output = 0, False, None
+        self._source = None
+        if self._wave is not None:
+            self._wave.reset()
         if self._text is not None:
             self._text = [''] * len(self._text)
 
     # ---- exact mode -----------------------------------------------------------------------------------------------------------
     def end(self):
-        """carry_context: the end of the utterance as a final feed of nothing -- every frame still held back is emitted.  Returns
-        the transcripts."""
+        """carry_context: the end of the utterance as a final feed of nothing -- every frame still held back is emitted (after a
+        ``feed_wave``: the front-end's last frame first).  Returns the transcripts."""
         if not self.carry_context:
             raise ValueError("end() belongs to carry_context=True; without it there is nothing held back")
+        if self._source == "wave":
+            N = self._wave.capacity
+            return self._feed_wave_exact(torch.empty((N, 0), dtype=torch.float32, device=self._wave.device), [0] * N, True)
         if self._state is None:
             raise ValueError("StreamingTranscriber.end: nothing has been fed")
         N, F0 = self._state["N"], self.model._F0
@@ -267,9 +316,10 @@ class StreamPool:
     one recurrent stack over the rows that retire an RNN frame, one lookahead, one head, one decoder feed -- and per stream the
     probabilities emitted over its feeds, concatenated, are the one-shot eval ``forward`` of that utterance alone."""
 
-    def __init__(self, model, decoder, capacity, max_frames=6000):
+    def __init__(self, model, decoder, capacity, max_frames=6000, front_end=None):
         """model: a uni-directional DeepSpeech on a HIP device (run in eval mode, no autograd); decoder: a BeamCTCDecoder or
-        GreedyDecoder over its labels; max_frames bounds the output frames per stream of a beam decoder."""
+        GreedyDecoder over its labels; max_frames bounds the output frames per stream of a beam decoder; front_end: a causal
+        SpectrogramFrontEnd for feed_wave (None = one with the model's spect_cfg and normalize="running", made on first use)."""
         if model.bidirectional:
             raise ValueError("a StreamPool needs a uni-directional model: a reverse direction cannot be streamed exactly")
         if int(capacity) < 1:
@@ -281,6 +331,8 @@ class StreamPool:
         self._fed, self._ended, self._text = [0] * S, [False] * S, [''] * S
         self._cur, self._fresh = [0] * S, [7] * S          # per slot, bit s - 1: stage s's carry buffer / its carry reads as zero
         self._h_zero = [True] * S                          # the slot's hidden state is the zero state of a new stream
+        self.front_end, self._wave = front_end, None       # feed_wave: the front-end and its streaming handle over the S slots
+        self._source = [None] * S                          # per slot: "spect" or "wave", what its stream is fed with
         self.last_output = {}                              # slot -> (cnt3, C) probabilities of the last feed that held the slot
 
     # ---- slots ------------------------------------------------------------------------------------------------------------------
@@ -291,6 +343,9 @@ class StreamPool:
         s = self._open.index(False)
         self._open[s] = True
         self._fed[s], self._ended[s], self._text[s], self._fresh[s] = 0, False, '', 7
+        self._source[s] = None
+        if self._wave is not None:
+            self._wave.reset([s])
         self.last_output.pop(s, None)
         if self.stream is not None:
             self.stream.reset([s])
@@ -334,16 +389,61 @@ class StreamPool:
         return [self.stream.text[s]], [self.stream.offsets[s]]
 
     def end(self, slots):
-        """The end of these streams' utterances as a final feed of nothing: every frame still held back is emitted."""
+        """The end of these streams' utterances as a final feed of nothing: every frame still held back is emitted (for a slot
+        fed with ``feed_wave``: the front-end's last frame first)."""
         sl = self._check_slots(slots)
         dev = next(self.model.parameters()).device
-        return self.feed(sl, torch.empty((len(sl), 1, self.model._F0, 0), dtype=torch.float32, device=dev), [0] * len(sl), final=sl)
+        wave = [s for s in sl if self._source[s] == "wave"]
+        rest = [s for s in sl if self._source[s] != "wave"]
+        text = {}
+        if wave:
+            text.update(zip(wave, self.feed_wave(wave, torch.empty((len(wave), 0), dtype=torch.float32, device=dev), [0] * len(wave), final=wave)))
+        if rest:
+            text.update(zip(rest, self.feed(rest, torch.empty((len(rest), 1, self.model._F0, 0), dtype=torch.float32, device=dev),
+                                            [0] * len(rest), final=rest)))
+        return [text[s] for s in sl]
+
+    def feed_wave(self, slots, wav, nsamples, final=()):
+        """wav: [len(slots)][L] waveform chunks on the model's device, row i = the nsamples[i] >= 0 new samples of slots[i] (any
+        counts, 0 included); final: the slots whose utterance ends with this chunk.  The chunks go through the front-end's
+        streaming form (``SpectrogramFrontEnd.stream``, running normalisation) and the frames they complete are fed as ``feed``
+        feeds them.  Returns the transcript so far of every slot in `slots`."""
+        sl = self._check_slots(slots)
+        fin = self._check_slots(final)
+        for s in sl:
+            if self._source[s] == "spect":
+                raise ValueError("slot %d is fed with spectrogram chunks; feed_wave cannot be mixed in" % s)
+            if self._ended[s]:
+                raise ValueError("the stream of slot %d has ended (a final feed or end()); close() it and open() the next one" % s)
+        if not sl:
+            return []
+        if self.front_end is None:
+            from .spectrogram import SpectrogramFrontEnd
+            self.front_end = SpectrogramFrontEnd(getattr(self.model, "spect_cfg", None), normalize="running")
+        if self.front_end.normalize is True:
+            raise ValueError("a StreamPool needs a causal front-end: normalize=True takes the mean and the standard deviation of the "
+                             "whole utterance, which a stream does not have yet; build it with normalize='running'")
+        if self._wave is None:
+            self._wave = self.front_end.stream(self.capacity, wav.device)
+        spect, frames = self._wave.feed(sl, wav, nsamples, final=fin)
+        for s in sl:
+            self._source[s] = "wave"
+        return self._feed(sl, spect, frames, fin)
 
     # ---- the feed ---------------------------------------------------------------------------------------------------------------
     def feed(self, slots, spect, lengths, final=()):
         """spect: (len(slots), 1, F0, Tc) spectrogram chunks on the model's device, row i for slots[i] (any order); lengths[i] in
         [0, Tc]: the valid input frames of row i; final: the slots whose utterance ends with this chunk.  Returns the transcript so
         far of every slot in `slots`, in that order.  Only the fetch of the text waits for the device."""
+        for s in self._check_slots(slots):
+            if self._source[s] == "wave":
+                raise ValueError("slot %d is fed with feed_wave; spectrogram chunks cannot be mixed in" % s)
+        text = self._feed(slots, spect, lengths, final)
+        for s in slots:
+            self._source[int(s)] = "spect"
+        return text
+
+    def _feed(self, slots, spect, lengths, final):
         from . import ops
         m, S = self.model, self.capacity
         sl = self._check_slots(slots)

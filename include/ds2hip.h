@@ -355,6 +355,54 @@ int ds2_spec_augment_coef(const float* x, int N, int F, int Tmax, const int* fra
 int ds2_spec_augment(const float* in, float* out, int N, int F, int Tmax, const int* frames, const float* coef, const int* fmask,
                      int MF, const int* tmask, int MT, ds2_stream_t stream);
 
+/* ---- running (causal) normalisation and the streaming front-end ----------------------------------------
+ * normalize = 2.  With v[t][f] = log1p(|X[t][f]|) in fp32, s[t] = sum_f (double) v and q[t] = sum_f (double) v^2 (an order that
+ * depends on f alone), the state (S, Q) is a STRICT left fold in frame order, S_t = S_(t-1) + s[t], Q_t = Q_(t-1) + q[t], and
+ *   cnt_t = 161 (t + 1) + prior_cnt, mean_t = S_t / cnt_t, var_t = max((Q_t - cnt_t mean_t^2) / (cnt_t - 1), 0),
+ *   rstd_t = 1 / max(sqrt(var_t), floor), out[f][t] = (v[t][f] - (float) mean_t) * (float) rstd_t          (all fp64 until the casts).
+ * floor > 0 belongs to the mode: digital silence gives zeros, never NaN.  prior_frames > 0 starts the fold from pseudo-counts,
+ * S0 = prior_mean 161 prior_frames, Q0 = (prior_std^2 + prior_mean^2) 161 prior_frames, prior_cnt = 161 prior_frames; 0 = none.
+ * ds2_spectrogram_running: ds2_spectrogram (aug = 0; the arguments behind it are ignored) or ds2_spectrogram_aug (aug != 0) in this
+ *   mode; the warp's two source frames and its control value are each normalised with their own frame's statistics.
+ *   ws: ds2_spect_running_ws_bytes(N, Lmax).  N <= 65535.
+ * The streaming form gives, for audio cut into feeds of ANY lengths, the frames of the one-shot call on the whole clip bit for bit
+ * (zero centre padding only).  After G samples of a stream G / 160 frames are complete, frame t covers samples [160 t - 160,
+ * 160 t + 160); the end of the utterance completes 1 + G / 160.  A slot keeps the samples that incomplete frames need (at most 319)
+ * and (S, Q); the frame count is the caller's.
+ * ds2_spect_stream_plan (host only): after samples_before samples, a feed of n_new more (final != 0: the utterance ends) -> out[0]
+ *   frames complete before, out[1] frames emitted, out[2] window samples in front of the new ones (160 + samples_before % 160, the
+ *   left padding included), out[3] the window's length (with the 160 zeros behind a final feed), out[4] the samples carried on (0
+ *   after a final feed), out[5] the clip position of the window's first sample (-160 inside the left padding).
+ * ds2_spect_stream_state_bytes(S): [S][2] f64 + [S][320] f32; ds2_spect_stream_ws_bytes(n_rows, max_new, Tc): the workspace.
+ * ds2_spect_stream_feed: row r reads its n_new <= max_new <= ldw new samples from wav[src] and writes out[r] of out (n_rows, 1, 161,
+ *   Tc) f32, frames >= emit zero; Tc >= every emit, Tc = 0 moves the carries alone.  A row with fresh != 0 reads its slot's carry as
+ *   the 160 zeros of the left padding and its statistics as the prior, whatever the slot holds (carried must be 0 then).
+ *   normalize 0 (raw log-magnitudes, no statistics) or 2; 1 is refused: per-utterance statistics are not causal.  The table lives
+ *   on the device, so the entry cannot check it: slots distinct and in [0, S), src inside wav, the counts those of the plan.
+ * DS2_ERR_ARG: a null buffer that is read or written, N or n_rows outside [1, 65535], S < n_rows, floor <= 0, a negative or NaN
+ *   prior, Tc beyond what max_new samples can complete. */
+typedef struct ds2_spect_stream_row {
+  int32_t slot;          /* the stream's state slot, 0 <= slot < S */
+  int32_t src;           /* the stream's row of wav */
+  int32_t carried;       /* samples the window takes from the slot's carry (0 for a fresh slot) */
+  int32_t n_new;         /* new samples */
+  int32_t frames_before; /* frames of the stream emitted before this feed */
+  int32_t emit;          /* frames this feed emits */
+  int32_t final;         /* the utterance ends with this feed */
+  int32_t fresh;         /* the slot's carry and statistics read as those of a new stream */
+} ds2_spect_stream_row;
+long ds2_spect_running_ws_bytes(int N, int Lmax);
+int ds2_spectrogram_running(const float* wav, long ldw, const int* nsamples, int N, int Lmax, const float* basis, int reflect,
+                            double floor, double prior_mean, double prior_std, double prior_frames, float* out, void* ws, int aug,
+                            const float* warp_draw, int W, const int* fmask, int MF, const int* tmask, int MT, float* coef_out,
+                            ds2_stream_t stream);
+int ds2_spect_stream_plan(long samples_before, int n_new, int final, int* out);
+long ds2_spect_stream_state_bytes(int S);
+long ds2_spect_stream_ws_bytes(int n_rows, int max_new, int Tc);
+int ds2_spect_stream_feed(const float* wav, long ldw, const ds2_spect_stream_row* rows, int n_rows, int max_new, int Tc, int S,
+                          const float* basis, int normalize, double floor, double prior_mean, double prior_std, double prior_frames,
+                          void* state, float* out, void* ws, ds2_stream_t stream);
+
 /* ---- waveform augmentation on the device (what SpectrogramParser.parse_audio does to the samples before the STFT,
  * loader/data_loader.py:151-159: load_randomly_augmented_audio, :377-404 = sox `tempo t gain g`, then NoiseInjection.inject_noise,
  * :97-128).  Every entry works on a batch wav [N][ldw] f32 (clip n = the first nsamples[n] entries of row n; nsamples [N] int32 on

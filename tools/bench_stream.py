@@ -8,6 +8,7 @@ forward sweep takes h0/c0 and returns hn/cn).  Prints one JSON line per model: p
     python tools/bench_stream.py --decode beam [--beam-width 100]
     python tools/bench_stream.py --carry [--decode greedy --chunk 0.2 --streams 1]
     python tools/bench_stream.py --pool 8 [--chunk 0.2 --seconds 10 --pool-modes sessions,pool,session,pool_lockstep --pool-launches]
+    python tools/bench_stream.py --carry --wave      /      --pool 8 --wave
 
 With --decode greedy|beam the drop-in class runs inside a streaming.StreamingTranscriber: every chunk's output goes to the decoder
 stream on the device and the best transcript so far comes back per chunk (no output leaves the device, nothing is decoded twice).
@@ -22,6 +23,9 @@ joining at tick k, in four modes: `sessions`, S Stream
 stream each, fed one after another (the only way to serve staggered streams without a pool); `pool`, one StreamPool feed per tick;
 and, with all streams joining at tick 0, `session` (one lock-step session of S streams) against `pool_lockstep`.  Only the ticks
 in which all S streams are open and none ends are timed.  --pool-launches adds the device kernels of one such tick (torch.profiler).
+
+--wave (with --carry or --pool): the exact modes are fed raw audio, feed_wave instead of feed, in the same chunking (chunk seconds
+* 16000 samples a feed): the streaming front-end with running normalisation runs inside the timed feed.
 """
 import argparse
 import json
@@ -70,7 +74,7 @@ def run_decoding(st, chunks, reps):
     return np.array(lat), total, text, st.frames
 
 
-def run_carry(st, chunks, reps, N):
+def run_carry(st, chunks, reps, N, wave=False):
     """run_decoding() for either mode of a session over N streams; the exact mode ends the utterance (end()) outside the timed feeds"""
     lat, emitted = [], 0
     for r in range(reps + 1):
@@ -79,7 +83,7 @@ def run_carry(st, chunks, reps, N):
         t_all = time.perf_counter()
         for c in chunks:
             t0 = time.perf_counter()
-            text = st.feed(c, [c.shape[3]] * N)
+            text = st.feed_wave(c, [c.shape[1]] * N) if wave else st.feed(c, [c.shape[3]] * N)
             if r > 0:
                 lat.append(time.perf_counter() - t0)
         emitted = st.frames[0]
@@ -143,8 +147,14 @@ def run_pool(a):
     nch = int(a.seconds * 100) // tc
     m = _uni_lstm(dev)
     mk_dec = lambda: D.BeamCTCDecoder(configs.LABELS, beam_width=a.beam_width) if a.decode == "beam" else D.GreedyDecoder(configs.LABELS)
-    audio = torch.from_numpy(np.random.RandomState(0).standard_normal((S, 1, 161, nch * tc)).astype(np.float32)).to(dev)
-    piece = lambda k, j: audio[k:k + 1, :, :, j * tc:(j + 1) * tc]
+    if a.wave:
+        audio = torch.from_numpy(0.1 * np.random.RandomState(0).standard_normal((S, nch * tc * 160)).astype(np.float32)).to(dev)
+        piece = lambda k, j: audio[k:k + 1, j * tc * 160:(j + 1) * tc * 160]
+    else:
+        audio = torch.from_numpy(np.random.RandomState(0).standard_normal((S, 1, 161, nch * tc)).astype(np.float32)).to(dev)
+        piece = lambda k, j: audio[k:k + 1, :, :, j * tc:(j + 1) * tc]
+    per = tc * 160 if a.wave else tc                      # what a feed brings per stream: samples or frames
+    feed_of = lambda obj: obj.feed_wave if a.wave else obj.feed
     max_frames = nch * tc // 2 + 2
 
     def ticks_of(starts):
@@ -184,14 +194,14 @@ def run_pool(a):
                 t0 = time.perf_counter()
                 if mode == "sessions":
                     for x, (k, j) in zip(xs[i], rows):
-                        sess[k].feed(x, [tc], final=(j == nch - 1))
+                        feed_of(sess[k])(x, [per], final=(j == nch - 1))
                 elif mode == "session":
-                    sess.feed(batches[i], [tc] * S, final=(rows[0][1] == nch - 1))
+                    feed_of(sess)(batches[i], [per] * S, final=(rows[0][1] == nch - 1))
                 else:
                     for k, j in rows:
                         if j == 0:
                             slot[k] = pool.open()
-                    pool.feed([slot[k] for k, _ in rows], batches[i], [tc] * len(rows), final=[slot[k] for k, j in rows if j == nch - 1])
+                    feed_of(pool)([slot[k] for k, _ in rows], batches[i], [per] * len(rows), final=[slot[k] for k, j in rows if j == nch - 1])
                     for k, j in rows:
                         if j == nch - 1:
                             pool.close(slot[k])
@@ -203,7 +213,8 @@ def run_pool(a):
                     lat.append(time.perf_counter() - t0)
         lat = np.array(lat)
         print(json.dumps({"metric": "one tick of S exact streams (every open stream advances one chunk)", "mode": mode, "streams": S,
-                          "model": "uni-LSTM-1024x5+lookahead", "decode": a.decode or "greedy", "chunk_seconds": a.chunk,
+                          "model": "uni-LSTM-1024x5+lookahead", "decode": a.decode or "greedy", "input": "wave" if a.wave else "spectrogram",
+                          "chunk_seconds": a.chunk,
                           "chunks_per_stream": nch, "ticks_timed": int(lat.size), "ms_per_tick_median": round(float(np.median(lat)) * 1e3, 3),
                           "ms_per_tick_p95": round(float(np.percentile(lat, 95)) * 1e3, 3), "device_kernels_per_tick": launches,
                           "dtype": "bf16"}), flush=True)
@@ -227,7 +238,10 @@ def main():
     ap.add_argument("--pool", type=int, default=0, help="time one tick of this many exact streams (StreamPool and its baselines)")
     ap.add_argument("--pool-modes", default="sessions,pool,session,pool_lockstep")
     ap.add_argument("--pool-launches", action="store_true", help="--pool: also count the device kernels of one tick")
+    ap.add_argument("--wave", action="store_true", help="--carry / --pool: feed raw audio (feed_wave) to the exact modes")
     a = ap.parse_args()
+    if a.wave and not (a.pool or a.carry):
+        raise SystemExit("--wave goes with --carry or --pool")
     if a.pool:
         return run_pool(a)
     from deepspeech.pytorch_amd import configs
@@ -269,11 +283,15 @@ def main():
                 Ns = a.streams
                 dec = D.BeamCTCDecoder(configs.LABELS, beam_width=a.beam_width) if a.decode == "beam" else D.GreedyDecoder(configs.LABELS)
                 even = [c.expand(Ns, -1, -1, -1).contiguous() for c in chunks if c.shape[3] == tc]      # equal chunks only
-                for carry in (False, True):
+                if a.wave:
+                    wav = torch.from_numpy(0.1 * rs.standard_normal((Ns, len(even) * tc * 160)).astype(np.float32)).to(dev)
+                    even = [wav[:, i * tc * 160:(i + 1) * tc * 160].contiguous() for i in range(len(even))]
+                for carry in ((True,) if a.wave else (False, True)):
                     st = StreamingTranscriber(m, dec, max_frames=T // 2 + len(chunks), carry_context=carry)
-                    lat, total, text, emitted, frames = run_carry(st, even, a.reps, Ns)
+                    lat, total, text, emitted, frames = run_carry(st, even, a.reps, Ns, a.wave)
                     print(json.dumps({"metric": "session feed, chunked inference (StreamingTranscriber)", "model": name,
-                                      "carry_context": carry, "decode": a.decode or "greedy", "streams": Ns, "audio_seconds": a.seconds,
+                                      "carry_context": carry, "input": "wave" if a.wave else "spectrogram", "decode": a.decode or "greedy",
+                                      "streams": Ns, "audio_seconds": a.seconds,
                                       "chunk_seconds": a.chunk, "chunks": len(even), "latency_frames": st.latency_frames,
                                       "ms_per_feed_median": round(float(np.median(lat)) * 1e3, 3),
                                       "ms_per_feed_p95": round(float(np.percentile(lat, 95)) * 1e3, 3),
@@ -307,5 +325,5 @@ def main():
 
 if __name__ == "__main__":
     main()
-    if "--carry" in sys.argv:
+    if "--carry" in sys.argv and "--wave" not in sys.argv:
         carry_error()
