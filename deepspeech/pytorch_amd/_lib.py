@@ -24,6 +24,8 @@ SIGNATURES = {
     "ds2_gemm8_nt": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _vp]),
     "ds2_gemm8_tn_grouped": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "ds2_gemm8_nt_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _vp, _i, _vp]),
+    "ds2_gemm8_nt_rows_stagger": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _i, _vp, _i, _i, _vp]),
+    "ds2_gemm8_stagger_plan": (_i, [_i, _i, _i]),
     "ds2_gemm8_tn_grouped_rows": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "ds2_gemm8_wgrad_dx_rows": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _l, _l, _l, _vp, _i, _vp]),
     "ds2_zero_pad_rows": (_i, [_i, _vp, _l, _i, _vp, _i, _i, _vp]),

@@ -48,6 +48,7 @@ struct G8Problem {
 struct G8Args {
   G8Problem p[G8_MAX_GROUPS];
   int n_problems;
+  int stag_cus, stag_ticks;   // start offsets of the first round (g8_stagger_wait): CU count, span in 10 ns ticks (0 = none)
 };
 
 #define G8_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
@@ -444,6 +445,21 @@ __device__ __forceinline__ void g8_tile(const G8Problem& P, int t_id, unsigned c
 }
 
 
+// Start offsets (NT launches of at least two rounds; policy: ds2_gemm8_stagger_plan).  One workgroup fits a CU, so the first `cus`
+// workgroups open the CUs together, run the same K and reach their first epilogues together.  A workgroup of the first round
+// therefore waits id * span / cus before its first tile; every later workgroup inherits its CU's phase from the dispatcher.  The
+// dispatcher deals consecutive ids to the eight XCDs in turn, so the CUs of one XCD (ids x, x + 8, ...) are spread over the whole
+// span and neighbouring slots lie on different XCDs.  The wait touches no memory, comes before the workgroup's first barrier and is
+// bounded twice: the span is clamped on the host (G8_STAGGER_MAX_US) and the loop ends after a fixed number of sleeps even if the
+// clock stood still.  It decides when a tile runs, never what it computes.
+constexpr int G8_STAGGER_MAX_US = 200;
+__device__ __forceinline__ void g8_stagger_wait(int id, int cus, int ticks) {
+  if (ticks <= 0 || id >= cus) return;                                  // wave-uniform
+  const unsigned long long wait = (unsigned long long)id * (unsigned)ticks / (unsigned)cus;
+  const unsigned long long t0 = wall_clock64();                         // 100 MHz
+  for (int spins = 0; spins < G8_STAGGER_MAX_US * 100 && wall_clock64() - t0 < wait; ++spins) __builtin_amdgcn_s_sleep(8);
+}
+
 // MODE 0: every problem NT, 1: every problem TN, 2: mixed.  Workgroup -> (problem, tile): problems own consecutive id ranges (the
 // host orders them by decreasing K, so the long tiles are dispatched first); inside a problem's range the ids that the dispatcher
 // places on one XCD (id % 8) get a contiguous run of its tiles (neighbouring tiles share operand panels in that XCD's L2).
@@ -451,6 +467,7 @@ template <int MODE, bool SPREAD>
 __global__ void __launch_bounds__(512, 2) k_gemm8(G8Args g) {
   __shared__ __attribute__((aligned(1024))) unsigned char lds[131072];
   const int id = blockIdx.x;
+  g8_stagger_wait(id, g.stag_cus, g.stag_ticks);
   int pi = 0, first = 0;
 #pragma unroll
   for (int i = 0; i < G8_MAX_GROUPS - 1; ++i)
@@ -495,8 +512,24 @@ void g8_launch(int total, const G8Args& g, hipStream_t st) {
 //   NT: C[rows[r]][:] = A[rows[r]][:] * B^T (+ bias) for r < n_rows; other rows of C are NOT written.
 //   TN: C = sum over k < n_rows of At[rows[k]][m] * Bt[rows[k]][n].
 // rows == null: every row (n_rows = n_phys).  n_phys bounds the operands (n_phys * ld < 2^31 elements).
+
+// Span of the first round's start offsets in microseconds for a launch of `tiles` tiles on `cus` CUs (kind 0 NT, 1 grouped TN,
+// 2 mixed); 0 = none.  NT launches of at least two rounds only: with fewer tiles there is no later round whose tile ends the
+// offsets could keep apart, and a TN or mixed launch runs tiles of different K, which do not end together in the first place.
+// 25 us is the span with the lowest k_gemm8<0> time per cfg3 step in the sweep 0 / 6 / 12 / 25 / 40 / 60 / 100 us
+// (profiles/gemm8_tile_boundaries.md: 1.63 -> 1.55 ms per step, and the step 20.00 -> 19.6 ms); -DG8_STAGGER_DEFAULT_US=n rebuilds
+// with another span for such a sweep (build.build_variant).
+#ifndef G8_STAGGER_DEFAULT_US
+#define G8_STAGGER_DEFAULT_US 25
+#endif
+static int g8_stagger_plan(int kind, int tiles, int cus) {
+  return (kind == 0 && cus > 0 && tiles >= 2 * cus) ? G8_STAGGER_DEFAULT_US : 0;
+}
+static int g8_stagger_clamp(int us) { return us < 0 ? 0 : (us > G8_STAGGER_MAX_US ? G8_STAGGER_MAX_US : us); }
+
+// stagger_us < 0: the policy's span; otherwise the given one (clamped to [0, G8_STAGGER_MAX_US]) whatever the tile count
 static int g8_nt(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc, int out_f32,
-                 const int* rows, int n_phys, hipStream_t st) {
+                 const int* rows, int n_phys, int stagger_us, hipStream_t st) {
   DS2_REQUIRE(M > 0 && N > 0 && K > 0 && K % 64 == 0 && lda % 8 == 0 && ldb % 8 == 0 && n_phys >= M, DS2_ERR_ARG);
   DS2_REQUIRE((((uintptr_t)A) & 15) == 0 && (((uintptr_t)B) & 15) == 0, DS2_ERR_ALIGN);
   DS2_REQUIRE((long)n_phys * lda < (1L << 31) && (long)N * ldb < (1L << 31), DS2_ERR_ARG);
@@ -504,6 +537,8 @@ static int g8_nt(const void* A, const void* B, void* C, const float* bias, int M
   g.n_problems = 1;
   const int tm = ds2_cdiv(M, 256), tn = ds2_cdiv(N, 256);
   g.p[0] = G8Problem{(const bf16_t*)A, nullptr, (const bf16_t*)B, C, bias, M, N, 0, lda, 0, ldb, ldc, tn, tm * tn, out_f32, K, 0, rows};
+  g.stag_cus = ds2_cu_count();
+  g.stag_ticks = 100 * g8_stagger_clamp(stagger_us < 0 ? g8_stagger_plan(0, tm * tn, g.stag_cus) : stagger_us);
   g8_launch<0>(tm * tn, g, st);
   DS2_CHECK_LAUNCH();
   return 0;
@@ -534,12 +569,21 @@ extern "C" {
 // K % 64 == 0, lda/ldb % 8 == 0, 16-byte aligned operands of < 2^31 elements.
 int ds2_gemm8_nt(const void* A, const void* B, void* C, const float* bias, int M, int N, int K, long lda, long ldb, long ldc, int out_f32,
                  ds2_stream_t st) {
-  return g8_nt(A, B, C, bias, M, N, K, lda, ldb, ldc, out_f32, nullptr, M, (hipStream_t)st);
+  return g8_nt(A, B, C, bias, M, N, K, lda, ldb, ldc, out_f32, nullptr, M, -1, (hipStream_t)st);
 }
 int ds2_gemm8_nt_rows(const void* A, const void* B, void* C, const float* bias, int n_phys, int N, int K, long lda, long ldb, long ldc,
                       int out_f32, const int* rows, int n_rows, ds2_stream_t st) {
-  return g8_nt(A, B, C, bias, rows ? n_rows : n_phys, N, K, lda, ldb, ldc, out_f32, rows, n_phys, (hipStream_t)st);
+  return g8_nt(A, B, C, bias, rows ? n_rows : n_phys, N, K, lda, ldb, ldc, out_f32, rows, n_phys, -1, (hipStream_t)st);
 }
+// ds2_gemm8_nt_rows with the span of the start offsets given (tests, A/B): stagger_us < 0 = the policy's, else clamped to
+// [0, ds2_gemm8_stagger_plan(-1, 0, 0)] microseconds and applied whatever the tile count.  The result does not depend on it.
+int ds2_gemm8_nt_rows_stagger(const void* A, const void* B, void* C, const float* bias, int n_phys, int N, int K, long lda, long ldb, long ldc,
+                              int out_f32, const int* rows, int n_rows, int stagger_us, ds2_stream_t st) {
+  return g8_nt(A, B, C, bias, rows ? n_rows : n_phys, N, K, lda, ldb, ldc, out_f32, rows, n_phys, stagger_us, (hipStream_t)st);
+}
+// The start-offset policy, askable without a device: the span in microseconds that a launch of `tiles` tiles of kind 0 (NT: ds2_gemm8_nt,
+// _nt_rows), 1 (grouped TN) or 2 (mixed: _wgrad_dx) gets on `cus` CUs.  kind < 0: the clamp, i.e. the longest span an entry accepts.
+int ds2_gemm8_stagger_plan(int kind, int tiles, int cus) { return kind < 0 ? G8_STAGGER_MAX_US : g8_stagger_clamp(g8_stagger_plan(kind, tiles, cus)); }
 
 // Grouped TN products, one launch:  for every problem i   C_i[M_i][N_i] f32 = sum_k At_i[k][m] * Bt_i[k][n],  k < K
 // (At_i [K][lda_i], Bt_i [K][ldb_i]: the contraction index is the ROW of both operands).  A problem's A operand may be two

@@ -94,6 +94,15 @@ int ds2_gemm8_nt_rows(const void* A, const void* B, void* C, const float* bias, 
 int ds2_gemm8_tn_grouped_rows(int n_problems, const void* const* At, const void* const* At2, const int* m_split, const void* const* Bt,
                               void* const* C, const int* M, const int* N, const long* lda, const long* lda2, const long* ldb, const long* ldc,
                               int n_phys, const int* rows, int n_rows, ds2_stream_t stream);
+/* Start offsets of an NT launch's first round (csrc/ds2_gemm8.hip, g8_stagger_wait): the workgroups that open the CUs wait
+ * id * span / CUs before their first tile, so that the tiles of a CU round do not reach their store epilogues at one moment.
+ * Results do not depend on the span.  ds2_gemm8_stagger_plan: the span in microseconds that a launch of `tiles` tiles gets on
+ * `cus` CUs -- kind 0 NT (ds2_gemm8_nt, _nt_rows: non-zero only from 2 * cus tiles), 1 grouped TN and 2 mixed (always 0); kind < 0:
+ * the longest span an entry accepts.  Host only, no device is asked.  ds2_gemm8_nt_rows_stagger: ds2_gemm8_nt_rows with the span
+ * given (stagger_us < 0: the policy's; otherwise clamped to the longest span and applied whatever the tile count). */
+int ds2_gemm8_stagger_plan(int kind, int tiles, int cus);
+int ds2_gemm8_nt_rows_stagger(const void* A, const void* B, void* C, const float* bias, int n_phys, int N, int K, long lda, long ldb, long ldc,
+                              int out_f32, const int* rows, int n_rows, int stagger_us, ds2_stream_t stream);
 int ds2_gemm8_wgrad_dx_rows(int n_tn, const void* const* At, const void* const* At2, const int* m_split, const void* const* Bt, void* const* C,
                             const int* M, const int* N, const long* lda, const long* lda2, const long* ldb, const long* ldc, int K_tn,
                             const void* A_nt, const void* B_nt, void* C_nt, int M_nt, int N_nt, int K_nt, long lda_nt, long ldb_nt, long ldc_nt,
