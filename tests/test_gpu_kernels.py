@@ -283,7 +283,9 @@ def test_conv1_fwd_and_wgrad(dtype, N, T, F0):
 def test_conv1_fwd_persistent_blocks_equal_single_block_runs():
     """The bf16 conv1 forward is a persistent kernel: a workgroup walks several (sample, frame block, row block) tiles through one
     LDS patch.  A batch of 20 long clips is 1 080 tiles on 256 workgroups (4-5 tiles each); every sample run ALONE is 54 tiles (one
-    per workgroup).  Same arithmetic per tile, so the two must agree bit for bit (the kernel tests above are all single-tile)."""
+    per workgroup).  Same arithmetic per tile, so the two must agree bit for bit.  (The conv tests of this file give a workgroup of the
+    matrix-pipe kernels -- k_conv1_fwd_mfma, k_conv1_wgrad_mfma, k_conv_rtap -- at most one tile: 54 and 220 at the largest shapes.  A
+    second and a third tile per workgroup are held to an exact reference in tests/test_gpu_conv_exact.py.)"""
     rs = np.random.RandomState(77)
     N, T = 20, 1501
     x = torch.from_numpy(rs.standard_normal((N, 1, 161, T)).astype(np.float32)).to(DEV)
