@@ -102,6 +102,9 @@ SIGNATURES = {
     "ds2_beam_decode": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ds2_beam_decode_lm": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _f, _f, _i,
                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_beam_decode_hot": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_beam_decode_lm_hot": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _f, _f, _i,
+                                    _vp, _l, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ds2_beam_grid_ws_bytes": (_l, [_i, _i, _i, _i]),
     "ds2_beam_decode_lm_grid": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -113,6 +116,10 @@ SIGNATURES = {
     "ds2_beam_stream_feed": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp]),
     "ds2_beam_stream_feed_lm": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _f, _f, _i,
                                      _vp, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_beam_stream_feed_hot": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _i, _vp, _vp, _l, _i, _vp,
+                                      _vp, _vp, _vp, _vp]),
+    "ds2_beam_stream_feed_lm_hot": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _f, _f, _i,
+                                         _vp, _l, _f, _vp, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp]),
     "ds2_stream_plan": (_i, [_l, _i, _i, _i, _vp]),
     "ds2_stream_state_bytes": (_l, [_i, _i, _i, _i, _i]),
     "ds2_stream_conv1": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

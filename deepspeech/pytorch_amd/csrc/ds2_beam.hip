@@ -40,6 +40,11 @@
 // k_beam_search<false, StreamArgs> / <true, LmArgs, StreamArgs> (ds2_beam_stream_feed / _feed_lm) is the resumable search: workgroup
 // n loads the state of stream n (nb, BeamState, LmState) from a device buffer, runs this chunk's frames numbered from the start of
 // the stream in a node pool that outlives the launch, and stores the state back; the output stage is optional and changes nothing.
+// k_beam_search<false, HotArgs> / <true, LmArgs, HotArgs>, and both with StreamArgs last (ds2_beam_decode_hot, _lm_hot,
+// ds2_beam_stream_feed_hot, _feed_lm_hot) add the hot words of DESIGN.md "ds2_beam": what the selection compares gains hot = done
+// + v(match), from a second per-beam state (HotState) that is a function of the string alone.  P2 probes the phrase table with
+// two keys at once per new candidate, P6 repeats that for a new string and probes once more for its space extension.  Every
+// addition sits under `if constexpr (HOT)`; the six instantiations above compile to the instructions they had without it.
 #include <float.h>
 
 #include "ds2_common.h"
@@ -82,6 +87,7 @@ constexpr uint64_t kNgramMul = 0x9e3779b97f4a7c15ull;
 constexpr double kLog10e = 0.4342944819032518;
 constexpr double kOovScore = -1000.0;                  // ln P of a word event with an unknown word or context
 constexpr int kWordAbsent = -2;                        // word-table answers besides a word id; -1 = a proper prefix
+constexpr int kHotWord = -2;                           // in a context (hot-word instantiations): a covered out-of-vocabulary hot word
 
 struct LmArgs {
   const ulonglong2* wtab;   // word table [wmask + 1] x (key, value)
@@ -126,11 +132,14 @@ __device__ __forceinline__ float lm_bonus(const LmArgs& A, double lnp) {
 // The bonus of completing word w after the context c[0] (most recent), c[1], ...: backoff over the stored n-grams.  Keys of
 // (c[m-1] .. c[0], w) for m = 0 .. order-1 and of the contexts (c[m] .. c[0]) for m = 0 .. order-2; all first probes are loaded
 // before any is looked at, and a later probe round only serves the keys whose slot held another key.
+// HOT (the hot-word instantiations): a context id may also be kHotWord, a covered out-of-vocabulary hot word.  It is not the
+// out-of-vocabulary mark, and no key that would contain it is probed, so it matches no stored n-gram and its contexts add backoff 0.
+template <bool HOT>
 __device__ __forceinline__ float word_bonus(const LmArgs& A, int w, const int (&c)[BEAM_LM_MAX_ORDER - 1]) {
   constexpr int NP = 2 * BEAM_LM_MAX_ORDER - 1;   // 0 .. 4: n-grams ending in w; 5 .. 8: contexts
   bool oov = w < 0;
 #pragma unroll
-  for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) oov |= m < A.order - 1 && c[m] < 0;
+  for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) oov |= m < A.order - 1 && (HOT ? c[m] == -1 : c[m] < 0);
   if (oov) return lm_bonus(A, kOovScore);
   uint64_t key[NP];
   unsigned slot[NP], pending = 0, found = 0;
@@ -138,13 +147,19 @@ __device__ __forceinline__ float word_bonus(const LmArgs& A, int w, const int (&
   uint64_t h = ngram_mix(kNgramSeed, w), g = kNgramSeed;
   key[0] = h;
   pending = 1u;
+  [[maybe_unused]] bool clean = true;             // no kHotWord among c[0 .. m]
 #pragma unroll
   for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) {
     h = ngram_mix(h, c[m]);
     g = ngram_mix(g, c[m]);
     key[m + 1] = h;
     key[BEAM_LM_MAX_ORDER + m] = g;
-    if (m < A.order - 1) pending |= (1u << (m + 1)) | (1u << (BEAM_LM_MAX_ORDER + m));
+    if constexpr (HOT) {
+      clean &= c[m] != kHotWord;
+      if (m < A.order - 1 && clean) pending |= (1u << (m + 1)) | (1u << (BEAM_LM_MAX_ORDER + m));
+    } else {
+      if (m < A.order - 1) pending |= (1u << (m + 1)) | (1u << (BEAM_LM_MAX_ORDER + m));
+    }
   }
 #pragma unroll
   for (int j = 0; j < NP; ++j) {
@@ -190,6 +205,82 @@ __device__ __forceinline__ LmState* lm_state() {
   return s;
 }
 
+// ---- hot words -----------------------------------------------------------------------------------------------------------
+// DESIGN.md "ds2_beam", hot words.  The table (hotwords.py) has one entry for every non-empty prefix q of every phrase: key = the
+// string hash of q (space label included), value = v(q) bits | c(q) bits << 32 | whole phrase << 63.  A beam carries the hash of its
+// match mu (kHashEmpty: none), done, v(mu), what its space extension adds (hsv: c(mu) when mu is a whole phrase, else v(mu + space)
+// when that is in the table, else 0) and two flags: bit 0 the space is covered, bit 1 mu is a whole phrase.  hot = done + v(mu);
+// hot of the space extension = done + hsv; hot_end = done + hsv when mu is a whole phrase, else done.
+struct HotArgs {
+  const ulonglong2* htab;   // [hmask + 1] x (key, value)
+  unsigned hmask;
+  int space;
+  float oov_logp;           // ln P charged to a covered out-of-vocabulary word event (LM instantiations)
+  float* acoustic;          // [N][B] -lse(pb, pnb), or null (instantiations without an LM; with one LmArgs has it)
+};
+struct NoHot {};
+
+struct HotState {
+  uint64_t mh[BEAM_MAXB];
+  float done[BEAM_MAXB], hv[BEAM_MAXB], hsv[BEAM_MAXB];
+  int flags[BEAM_MAXB];
+};
+struct HotWord {
+  uint64_t whash[BEAM_MAXB];                           // partial word (the LM instantiations have it in LmState)
+};
+constexpr int kHotCovered = 1, kHotComplete = 2;
+
+// like lm_state(): only the hot-word instantiations name these
+__device__ __forceinline__ HotState* hot_state() {
+  __shared__ HotState s[2];
+  return s;
+}
+__device__ __forceinline__ HotWord* hot_word() {
+  __shared__ HotWord s[2];
+  return s;
+}
+
+__device__ __forceinline__ float hot_v(uint64_t e) { return __uint_as_float((unsigned)e); }
+__device__ __forceinline__ float hot_c(uint64_t e) { return __uint_as_float((unsigned)(e >> 32) & 0x7fffffffu); }
+
+// NP keys at once, as word_bonus probes: every key loads in every round, open or not, so the loads are in flight together; the
+// rounds are bounded by the table size.  Returns the mask of the keys found, their values in val.
+template <int NP>
+__device__ __forceinline__ unsigned hot_find(const HotArgs& H, const uint64_t (&key)[NP], unsigned pending, uint64_t (&val)[NP]) {
+  unsigned slot[NP], found = 0;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    slot[j] = tab_slot(key[j], H.hmask);
+    val[j] = 0;
+  }
+  for (unsigned probe = 0; probe <= H.hmask && pending; ++probe) {
+    ulonglong2 e[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) e[j] = H.htab[slot[j]];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const bool open = pending >> j & 1, match = e[j].x == key[j], free_slot = e[j].x == kTabEmpty;
+      val[j] = open && match ? e[j].y : val[j];
+      found |= (unsigned)(open && match) << j;
+      pending &= ~((unsigned)(open && (match || free_slot)) << j);
+      slot[j] = open && !match && !free_slot ? (slot[j] + 1) & H.hmask : slot[j];
+    }
+  }
+  return found;
+}
+
+// the match of a string extended by the non-space label c: mu + c if the table has it (tried only when mu is not empty), else
+// partial word + c (a match anchored at this word's start).  Both keys are probed together.  False: no match.
+__device__ __forceinline__ bool hot_match(const HotArgs& H, uint64_t mh, uint64_t whash, int c, uint64_t& mh2, uint64_t& e) {
+  const uint64_t key[2] = {hash_ext(mh, c), hash_ext(whash, c)};
+  uint64_t val[2];
+  const unsigned found = hot_find<2>(H, key, (mh != kHashEmpty ? 1u : 0u) | 2u, val);
+  const bool first = found & 1u;
+  mh2 = found ? (first ? key[0] : key[1]) : kHashEmpty;
+  e = first ? val[0] : val[1];
+  return found != 0;
+}
+
 // A grid of (alpha, beta) points (ds2_beam_decode_lm_grid): workgroup (n, g) searches sample n with the weights of point g in a
 // node pool of its own, and only its top beam leaves the kernel.
 struct GridArgs {
@@ -225,11 +316,31 @@ struct StreamArgs {
 constexpr int kStreamHeader = 16;                      // bytes
 constexpr int kStreamBeamBytes = 8 + 6 * 4;            // per beam: hash; pb, pnb, lpc, len, last, node
 constexpr int kStreamLmBytes = 8 + (3 + BEAM_LM_MAX_ORDER - 1) * 4;   // whash; lm, spb, wid, ctx[]
+constexpr int kStreamHotBytes = 8 + 4 * 4;             // mh; done, hv, hsv, flags -- and whash (8 more) where no LM stores it
+// the hot-word fields follow the others at the next multiple of 8 bytes (the LM's fields are 36 bytes a beam)
+__host__ __device__ constexpr long stream_hot_off(bool lm, long B) {
+  return ((kStreamBeamBytes + (lm ? kStreamLmBytes : 0)) * B + 7) & ~7l;
+}
 
 __device__ __forceinline__ NoLm lm_args(const StreamArgs&) { return {}; }
 __device__ __forceinline__ LmArgs lm_args(const LmArgs& a, const StreamArgs&) { return a; }
 __device__ __forceinline__ const StreamArgs& stream_args(const StreamArgs& s) { return s; }
 __device__ __forceinline__ const StreamArgs& stream_args(const LmArgs&, const StreamArgs& s) { return s; }
+
+// the packs of the hot-word instantiations: [LmArgs,] HotArgs [, StreamArgs]
+__device__ __forceinline__ NoLm lm_args(const HotArgs&) { return {}; }
+__device__ __forceinline__ LmArgs lm_args(const LmArgs& a, const HotArgs&) { return a; }
+__device__ __forceinline__ NoLm lm_args(const HotArgs&, const StreamArgs&) { return {}; }
+__device__ __forceinline__ LmArgs lm_args(const LmArgs& a, const HotArgs&, const StreamArgs&) { return a; }
+__device__ __forceinline__ const StreamArgs& stream_args(const HotArgs&, const StreamArgs& s) { return s; }
+__device__ __forceinline__ const StreamArgs& stream_args(const LmArgs&, const HotArgs&, const StreamArgs& s) { return s; }
+__device__ __forceinline__ NoHot hot_args() { return {}; }
+template <class A, class... R>
+__device__ __forceinline__ auto hot_args(const A& a, const R&... r) {
+  if constexpr (__is_same(A, HotArgs)) return a;
+  else return hot_args(r...);
+}
+template <class X, class... Extra> struct Has { static constexpr bool value = (__is_same(Extra, X) || ...); };
 
 // whether the last of the kernel's trailing argument types is X
 template <class X, class... Extra> struct LastIs { static constexpr bool value = false; };
@@ -334,7 +445,9 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
   __shared__ unsigned s_need;
 
   constexpr bool GRID = LastIs<GridArgs, Extra...>::value, STREAM = LastIs<StreamArgs, Extra...>::value;
+  constexpr bool HOT = Has<HotArgs, Extra...>::value;
   [[maybe_unused]] const auto A = lm_args(extra...);
+  [[maybe_unused]] const auto H = hot_args(extra...);
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   int size = sizes ? sizes[n] : T;
   size = size < 0 ? 0 : (size > T ? T : size);
@@ -381,6 +494,15 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 #pragma unroll
       for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) L[0].ctx[m][0] = A.bos;
     }
+    if constexpr (HOT) {
+      HotState* HS = hot_state();
+      HS[0].mh[0] = kHashEmpty;
+      HS[0].done[0] = 0.f;
+      HS[0].hv[0] = 0.f;
+      HS[0].hsv[0] = 0.f;
+      HS[0].flags[0] = 0;
+      if constexpr (!LM) hot_word()[0].whash[0] = kHashEmpty;
+    }
   }
   int nb = 1, cur = 0;
   if constexpr (STREAM) {
@@ -409,6 +531,17 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
           L[0].wid[tid] = li[tid];
 #pragma unroll
           for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) L[0].ctx[m][tid] = li[(1 + m) * B + tid];
+        }
+        if constexpr (HOT) {
+          HotState* HS = hot_state();
+          const char* hp = sp + stream_hot_off(LM, B);
+          const float* hf = (const float*)(hp + (LM ? 8l : 16l) * B);
+          HS[0].mh[tid] = ((const uint64_t*)hp)[tid];
+          if constexpr (!LM) hot_word()[0].whash[tid] = ((const uint64_t*)hp)[B + tid];
+          HS[0].done[tid] = hf[tid];
+          HS[0].hv[tid] = hf[B + tid];
+          HS[0].hsv[tid] = hf[2 * B + tid];
+          HS[0].flags[tid] = ((const int*)hf)[3 * B + tid];
         }
       }
     }
@@ -475,7 +608,37 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
           }
         } else {
           s = mass;
-          if constexpr (LM) {
+          if constexpr (HOT) {
+            // hot(i+c): the space label takes the cached value; any other label probes mu+c and partial word+c together.  In
+            // lexicon mode the word table's first slot is loaded before that probe, so the three loads travel together.
+            const HotState& HS = hot_state()[cur];
+            float hot, l = 0.f;
+            if (c == H.space) {
+              hot = HS.done[i] + HS.hsv[i];
+              if constexpr (LM) l = lm_state()[cur].lm[i] + lm_state()[cur].spb[i];
+            } else {
+              uint64_t wh, wk = 0, m2, e;
+              ulonglong2 w0 = {kTabEmpty, 0};
+              bool lex = false;
+              if constexpr (LM) {
+                wh = lm_state()[cur].whash[i];
+                l = lm_state()[cur].lm[i];
+                lex = A.lexicon;
+                wk = hash_ext(wh, c);
+                if (lex) w0 = A.wtab[tab_slot(wk, A.wmask)];
+              } else {
+                wh = hot_word()[cur].whash[i];
+              }
+              const bool matched = hot_match(H, HS.mh[i], wh, c, m2, e);
+              hot = HS.done[i] + (matched ? hot_v(e) : 0.f);
+              if constexpr (LM) {
+                // a candidate that spells no word prefix survives only inside a hot phrase
+                if (lex && !matched && w0.x != wk && (w0.x == kTabEmpty || word_lookup(A, wk) == kWordAbsent)) l = -INFINITY;
+              }
+            }
+            if constexpr (LM) s = (mass + l) + hot;
+            else s = mass + hot;
+          } else if constexpr (LM) {
             const LmState& LS = lm_state()[cur];
             float l = LS.lm[i];
             if (c == A.space) l += LS.spb[i];   // a word event; 0 (open mode) or -inf (lexicon mode) where it is none
@@ -498,7 +661,11 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
       npnb = lse(npnb, ext_mass[i]);
       stay_pb[i] = npb;
       stay_pnb[i] = npnb;
-      if constexpr (LM) cs[i * W] = lse(npb, npnb) + lm_state()[cur].lm[i];
+      if constexpr (HOT) {
+        const float hot = hot_state()[cur].done[i] + hot_state()[cur].hv[i];
+        if constexpr (LM) cs[i * W] = (lse(npb, npnb) + lm_state()[cur].lm[i]) + hot;
+        else cs[i * W] = lse(npb, npnb) + hot;
+      } else if constexpr (LM) cs[i * W] = lse(npb, npnb) + lm_state()[cur].lm[i];
       else cs[i * W] = lse(npb, npnb);
     }
     __syncthreads();
@@ -609,11 +776,21 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 #pragma unroll
           for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) LD.ctx[m2][r] = LS.ctx[m2][i];
         }
+        if constexpr (HOT) {
+          const HotState& HS = hot_state()[cur];
+          HotState& HD = hot_state()[cur ^ 1];
+          HD.mh[r] = HS.mh[i];
+          HD.done[r] = HS.done[i];
+          HD.hv[r] = HS.hv[i];
+          HD.hsv[r] = HS.hsv[i];
+          HD.flags[r] = HS.flags[i];
+          if constexpr (!LM) hot_word()[cur ^ 1].whash[r] = hot_word()[cur].whash[i];
+        }
       } else {
         const int c = kc[m - 1];
         const int id = t * B + r;
         D.pb[r] = -INFINITY;
-        if constexpr (LM) D.pnb[r] = (c == S.last[i] ? S.pb[i] : score[i]) + klp[m - 1];   // the acoustic mass, as P2 formed it
+        if constexpr (LM || HOT) D.pnb[r] = (c == S.last[i] ? S.pb[i] : score[i]) + klp[m - 1];   // the acoustic mass, as P2 formed it
         else D.pnb[r] = cs[q];
         D.lpc[r] = klp[m - 1];
         D.hash[r] = hash_ext(S.hash[i], c);
@@ -623,6 +800,40 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         parent[id] = S.node[i];
         label[id] = c;
         frame[id] = t;
+        [[maybe_unused]] int hflags = 0;                 // the new string's hot-word flags
+        if constexpr (HOT) {
+          const HotState& HS = hot_state()[cur];
+          HotState& HD = hot_state()[cur ^ 1];
+          uint64_t wh;
+          if constexpr (LM) wh = lm_state()[cur].whash[i];
+          else wh = hot_word()[cur].whash[i];
+          if (c == H.space) {
+            // a whole phrase is paid into done; a match that goes on past the space keeps its hash; nothing else survives a space
+            const int f = HS.flags[i];
+            const bool complete = f & kHotComplete, keep = (f & kHotCovered) && !complete;
+            HD.mh[r] = keep ? hash_ext(HS.mh[i], c) : kHashEmpty;
+            HD.done[r] = complete ? HS.done[i] + HS.hsv[i] : HS.done[i];
+            HD.hv[r] = keep ? HS.hsv[i] : 0.f;
+            HD.hsv[r] = 0.f;
+            HD.flags[r] = 0;
+            if constexpr (!LM) hot_word()[cur ^ 1].whash[r] = kHashEmpty;
+          } else {
+            // the probes of P2 again, then one more for mu + space, which fills the cached space values
+            uint64_t m2, e;
+            const bool matched = hot_match(H, HS.mh[i], wh, c, m2, e);
+            const uint64_t key[1] = {hash_ext(m2, H.space)};
+            uint64_t val[1];
+            const bool next = hot_find<1>(H, key, matched ? 1u : 0u, val) != 0;
+            const bool complete = matched && (e >> 63);
+            hflags = (complete || next ? kHotCovered : 0) | (complete ? kHotComplete : 0);
+            HD.mh[r] = m2;
+            HD.done[r] = HS.done[i];
+            HD.hv[r] = matched ? hot_v(e) : 0.f;
+            HD.hsv[r] = complete ? hot_c(e) : (next ? hot_v(val[0]) : 0.f);
+            HD.flags[r] = hflags;
+            if constexpr (!LM) hot_word()[cur ^ 1].whash[r] = hash_ext(wh, c);
+          }
+        }
         if constexpr (LM) {
           const LmState& LS = lm_state()[cur];
           LmState& LD = lm_state()[cur ^ 1];
@@ -644,9 +855,17 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
             const int v = word_lookup(A, wh);
             const int id = v >= 0 ? v : -1;
             LD.lm[r] = LS.lm[i];
-            LD.spb[r] = (A.lexicon && id < 0) ? -INFINITY : word_bonus(A, id, cx);
-            LD.whash[r] = wh;
-            LD.wid[r] = id;
+            if constexpr (HOT) {
+              // an out-of-vocabulary word whose space is covered: charged hot_oov_logp, and kHotWord enters the context
+              const bool cov = id < 0 && (hflags & kHotCovered);
+              LD.spb[r] = cov ? lm_bonus(A, (double)H.oov_logp) : ((A.lexicon && id < 0) ? -INFINITY : word_bonus<true>(A, id, cx));
+              LD.whash[r] = wh;
+              LD.wid[r] = cov ? kHotWord : id;
+            } else {
+              LD.spb[r] = (A.lexicon && id < 0) ? -INFINITY : word_bonus<false>(A, id, cx);
+              LD.whash[r] = wh;
+              LD.wid[r] = id;
+            }
           }
 #pragma unroll
           for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) LD.ctx[m2][r] = cx[m2];
@@ -685,6 +904,17 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 #pragma unroll
           for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) li[(1 + m) * B + tid] = LE.ctx[m][tid];
         }
+        if constexpr (HOT) {
+          const HotState& HE = hot_state()[cur];
+          char* hp = sp + stream_hot_off(LM, B);
+          float* hf = (float*)(hp + (LM ? 8l : 16l) * B);
+          ((uint64_t*)hp)[tid] = HE.mh[tid];
+          if constexpr (!LM) ((uint64_t*)hp)[B + tid] = hot_word()[cur].whash[tid];
+          hf[tid] = HE.done[tid];
+          hf[B + tid] = HE.hv[tid];
+          hf[2 * B + tid] = HE.hsv[tid];
+          ((int*)hf)[3 * B + tid] = HE.flags[tid];
+        }
       }
       if (tid == 0) {
         hdr[0] = tend;
@@ -699,7 +929,38 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
   __threadfence();
   const BeamState& S = st[cur];
   int orank = tid;
-  if constexpr (LM) {
+  [[maybe_unused]] float* acoustic = nullptr;
+  if constexpr (LM) acoustic = A.acoustic;
+  else if constexpr (HOT) acoustic = H.acoustic;
+  if constexpr (HOT) {
+    // end of utterance with hot words: hot_end pays a match that is a whole phrase and nothing for an unfinished one; with an
+    // LM the end is covered only by a whole phrase, so a hot word cut short is out of vocabulary again.  Re-ranked by the total.
+    const HotState& HS = hot_state()[cur];
+    float tot = 0.f;
+    if (tid < nb) {
+      const float ac = lse(S.pb[tid], S.pnb[tid]);
+      const bool complete = HS.flags[tid] & kHotComplete;
+      const float hot_end = complete ? HS.done[tid] + HS.hsv[tid] : HS.done[tid];
+      if constexpr (LM) {
+        const LmState& LS = lm_state()[cur];
+        float l = LS.lm[tid];
+        if (LS.whash[tid] != kHashEmpty) {
+          if (LS.wid[tid] == kHotWord) l += complete ? LS.spb[tid] : lm_bonus(A, kOovScore);
+          else l += LS.spb[tid] == -INFINITY ? lm_bonus(A, kOovScore) : LS.spb[tid];
+        }
+        tot = (ac + l) + hot_end;
+      } else {
+        tot = ac + hot_end;
+      }
+      score[tid] = tot;
+      stay_pb[tid] = ac;
+    }
+    __syncthreads();
+    if (tid < nb) {
+      orank = 0;
+      for (int s = 0; s < nb; ++s) orank += score[s] > tot || (score[s] == tot && s < tid);
+    }
+  } else if constexpr (LM) {
     // end of utterance: a beam that ends inside a word gets that word's bonus too (a mere prefix counts as out of vocabulary in
     // lexicon mode); the beams are re-ranked by the total, ties to the earlier rank
     const LmState& LS = lm_state()[cur];
@@ -741,17 +1002,17 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         node = parent[node];
       }
       lens[o] = len;
-      if constexpr (LM) {
+      if constexpr (LM || HOT) {
         scores[o] = -score[tid] + 0.f;
-        if (A.acoustic) A.acoustic[o] = -stay_pb[tid] + 0.f;
+        if (acoustic) acoustic[o] = -stay_pb[tid] + 0.f;
       } else {
         scores[o] = -lse(S.pb[tid], S.pnb[tid]) + 0.f;
       }
     } else {
       lens[o] = 0;
       scores[o] = INFINITY;
-      if constexpr (LM) {
-        if (A.acoustic) A.acoustic[o] = INFINITY;
+      if constexpr (LM || HOT) {
+        if (acoustic) acoustic[o] = INFINITY;
       }
     }
   }
@@ -780,16 +1041,22 @@ WsLayout ws_layout(int N, int T, int B, int G = 1) {
 
 int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
                 int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
-                const LmArgs* lm, int G = 1, const float* alphas = nullptr, const float* betas = nullptr);
+                const LmArgs* lm, int G = 1, const float* alphas = nullptr, const float* betas = nullptr,
+                const HotArgs* hot = nullptr);
 
 // A stream session's buffer: the states, then the node pool's three arrays
 struct StreamLayout {
   long state_stride, parent, label, frame, total;   // bytes
 };
 
-StreamLayout stream_layout(int N, int B, int max_frames, bool lm) {
+constexpr int kStreamFlagLm = 1, kStreamFlagHot = 2;   // the flag word of the ds2_beam_stream_* size queries and reset
+
+StreamLayout stream_layout(int N, int B, int max_frames, int flags) {
   StreamLayout L;
-  L.state_stride = align256(kStreamHeader + (long)B * (kStreamBeamBytes + (lm ? kStreamLmBytes : 0)));
+  const bool lm = flags & kStreamFlagLm;
+  long beams = (long)B * (kStreamBeamBytes + (lm ? kStreamLmBytes : 0));
+  if (flags & kStreamFlagHot) beams = stream_hot_off(lm, B) + (long)B * (kStreamHotBytes + (lm ? 0 : 8));
+  L.state_stride = align256(kStreamHeader + beams);
   const long pool = align256((long)N * ((long)max_frames + 1) * B * 4);
   L.parent = (long)N * L.state_stride;
   L.label = L.parent + pool;
@@ -815,7 +1082,22 @@ __global__ void k_beam_stream_reset(char* state, long state_stride, int N, const
 
 int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
                      int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets, long row_stride,
-                     int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm);
+                     int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm,
+                     const HotArgs* hot = nullptr);
+
+// the checks and the fields of the hot-word entry points
+int hot_args_from(HotArgs& H, int C, int blank, int space, const void* hot_table, long hot_slots, float oov_logp, float* acoustic) {
+  DS2_REQUIRE(C > 0 && space >= 0 && space < C && space != blank, DS2_ERR_ARG);
+  DS2_REQUIRE(hot_table && hot_slots >= 2 && hot_slots <= (1l << 31) && (hot_slots & (hot_slots - 1)) == 0, DS2_ERR_ARG);
+  DS2_REQUIRE(oov_logp == oov_logp && oov_logp > -INFINITY && oov_logp < INFINITY, DS2_ERR_ARG);
+  DS2_REQUIRE(((uintptr_t)hot_table & 15) == 0, DS2_ERR_ALIGN);
+  H.htab = (const ulonglong2*)hot_table;
+  H.hmask = (unsigned)(hot_slots - 1);
+  H.space = space;
+  H.oov_logp = oov_logp;
+  H.acoustic = acoustic;
+  return 0;
+}
 
 // the checks and the fields that ds2_beam_decode_lm and its grid form share; alpha and beta are left to the caller
 int lm_args_from(LmArgs& A, int C, int blank, int space, const void* word_table, long word_slots, const void* ngram_table,
@@ -877,15 +1159,16 @@ int ds2_beam_decode_lm(const float* x, long stride_n, long stride_t, int N, int 
                      (hipStream_t)st_, &A);
 }
 
-long ds2_beam_stream_bytes(int N, int B, int max_frames, int lm) {
-  if (N <= 0 || B <= 0 || max_frames <= 0) return 0;
-  return stream_layout(N, B, max_frames, lm != 0).total;
+// flags: bit 0 a language model, bit 1 hot words (0 and 1 are the former values of this argument)
+long ds2_beam_stream_bytes(int N, int B, int max_frames, int flags) {
+  if (N <= 0 || B <= 0 || max_frames <= 0 || flags < 0 || flags > 3) return 0;
+  return stream_layout(N, B, max_frames, flags).total;
 }
 
 // bytes between two streams' states at the front of a session's buffer
-long ds2_beam_stream_state_stride(int B, int lm) {
-  if (B <= 0) return 0;
-  return stream_layout(1, B, 1, lm != 0).state_stride;
+long ds2_beam_stream_state_stride(int B, int flags) {
+  if (B <= 0 || flags < 0 || flags > 3) return 0;
+  return stream_layout(1, B, 1, flags).state_stride;
 }
 
 long ds2_beam_stream_ws_bytes(int N, int Tc) {
@@ -893,13 +1176,13 @@ long ds2_beam_stream_ws_bytes(int N, int Tc) {
   return stream_ws_layout(N, Tc).total;
 }
 
-// state: the session's buffer, ds2_beam_stream_bytes(N, B, max_frames, lm) bytes, 256-byte aligned.  mask: [N] device int32, a
+// state: the session's buffer, ds2_beam_stream_bytes(N, B, max_frames, flags) bytes, 256-byte aligned.  mask: [N] device int32, a
 // stream with a non-zero entry starts again from the empty beam (null = every stream); the others are untouched.  A new buffer is
 // reset as a whole before its first feed.
-int ds2_beam_stream_reset(void* state, int N, int B, int max_frames, int lm, const int* mask, ds2_stream_t st_) {
-  DS2_REQUIRE(state && N > 0 && B >= 1 && B <= BEAM_MAXB && max_frames > 0, DS2_ERR_ARG);
+int ds2_beam_stream_reset(void* state, int N, int B, int max_frames, int flags, const int* mask, ds2_stream_t st_) {
+  DS2_REQUIRE(state && N > 0 && B >= 1 && B <= BEAM_MAXB && max_frames > 0 && flags >= 0 && flags <= 3, DS2_ERR_ARG);
   DS2_REQUIRE(((uintptr_t)state & 255) == 0, DS2_ERR_ALIGN);
-  const StreamLayout L = stream_layout(N, B, max_frames, lm != 0);
+  const StreamLayout L = stream_layout(N, B, max_frames, flags);
   hipLaunchKernelGGL(k_beam_stream_reset, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)st_, (char*)state,
                      L.state_stride, N, mask);
   DS2_CHECK_LAUNCH();
@@ -938,6 +1221,70 @@ int ds2_beam_stream_feed_lm(const float* x, long stride_n, long stride_t, int N,
                           offsets, row_stride, out_ranks, lens, scores, ws, (hipStream_t)st_, &A);
 }
 
+// ds2_beam_decode with hot words (DESIGN.md "ds2_beam", hot words).  space: the label that ends a word; hot_table: the
+// open-addressing table of hotwords.py, [hot_slots][2] 64-bit words, hot_slots a power of two, 16-byte aligned.  scores =
+// -(log p + hot_end), the quantity that ranks the beams; acoustic (may be null): -lse(pb, pnb) of the same ranks.
+int ds2_beam_decode_hot(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                        int cutoff_top_n, float cutoff_prob, int space, const void* hot_table, long hot_slots, int* tokens,
+                        int* offsets, int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
+  HotArgs H;
+  const int rc = hot_args_from(H, C, blank, space, hot_table, hot_slots, 0.f, acoustic);
+  if (rc) return rc;
+  return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
+                     (hipStream_t)st_, nullptr, 1, nullptr, nullptr, &H);
+}
+
+// ds2_beam_decode_lm with hot words.  hot_oov_logp: ln P of a word event whose word is out of vocabulary but covered by a hot
+// phrase.  scores = -((log p + lm) + hot_end).
+int ds2_beam_decode_lm_hot(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                           int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                           const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
+                           const void* hot_table, long hot_slots, float hot_oov_logp, int* tokens, int* offsets, int* lens,
+                           float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
+  LmArgs A;
+  int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  if (rc) return rc;
+  A.alpha = alpha;
+  A.beta = beta;
+  HotArgs H;
+  rc = hot_args_from(H, C, blank, space, hot_table, hot_slots, hot_oov_logp, nullptr);
+  if (rc) return rc;
+  return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
+                     (hipStream_t)st_, &A, 1, nullptr, nullptr, &H);
+}
+
+// ds2_beam_stream_feed with hot words (the same table in every call on one state buffer, which was sized with flags = 2).  The
+// output stage includes hot_end and the re-rank, which read the state and leave it unchanged; acoustic [N][out_ranks] may be null.
+int ds2_beam_stream_feed_hot(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                             int cutoff_top_n, float cutoff_prob, int space, const void* hot_table, long hot_slots, void* state,
+                             int max_frames, int* tokens, int* offsets, long row_stride, int out_ranks, int* lens, float* scores,
+                             float* acoustic, void* ws, ds2_stream_t st_) {
+  HotArgs H;
+  const int rc = hot_args_from(H, C, blank, space, hot_table, hot_slots, 0.f, acoustic);
+  if (rc) return rc;
+  return beam_stream_feed(x, stride_n, stride_t, N, Tc, C, sizes, blank, B, cutoff_top_n, cutoff_prob, state, max_frames, tokens,
+                          offsets, row_stride, out_ranks, lens, scores, ws, (hipStream_t)st_, nullptr, &H);
+}
+
+// ds2_beam_stream_feed_lm with hot words (state buffer sized with flags = 3).
+int ds2_beam_stream_feed_lm_hot(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank,
+                                int B, int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                                const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
+                                const void* hot_table, long hot_slots, float hot_oov_logp, void* state, int max_frames, int* tokens,
+                                int* offsets, long row_stride, int out_ranks, int* lens, float* scores, float* acoustic, void* ws,
+                                ds2_stream_t st_) {
+  LmArgs A;
+  int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  if (rc) return rc;
+  A.alpha = alpha;
+  A.beta = beta;
+  HotArgs H;
+  rc = hot_args_from(H, C, blank, space, hot_table, hot_slots, hot_oov_logp, nullptr);
+  if (rc) return rc;
+  return beam_stream_feed(x, stride_n, stride_t, N, Tc, C, sizes, blank, B, cutoff_top_n, cutoff_prob, state, max_frames, tokens,
+                          offsets, row_stride, out_ranks, lens, scores, ws, (hipStream_t)st_, &A, &H);
+}
+
 long ds2_beam_grid_ws_bytes(int G, int N, int T, int B) {
   if (G <= 0 || N <= 0 || T <= 0 || B <= 0) return 0;
   return ws_layout(N, T, B, G).total;
@@ -966,7 +1313,7 @@ namespace {
 
 int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
                 int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
-                const LmArgs* lm, int G, const float* alphas, const float* betas) {
+                const LmArgs* lm, int G, const float* alphas, const float* betas, const HotArgs* hot) {
   DS2_REQUIRE(N > 0 && T > 0 && C > 0 && C <= BEAM_MAXC && blank >= 0 && blank < C, DS2_ERR_ARG);
   DS2_REQUIRE(B >= 1 && B <= BEAM_MAXB && cutoff_top_n >= 1, DS2_ERR_ARG);
   const int K = cutoff_top_n < C ? cutoff_top_n : C;
@@ -983,7 +1330,13 @@ int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int 
   hipLaunchKernelGGL(k_beam_prune, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, x, stride_n, stride_t, N, T, C, sizes, K,
                      use_cut, (double)cutoff_prob, pcnt, pcls, plp);
   DS2_CHECK_LAUNCH();
-  if (lm && alphas) {
+  if (hot && lm)
+    hipLaunchKernelGGL((k_beam_search<true, LmArgs, HotArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls,
+                       plp, (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *lm, *hot);
+  else if (hot)
+    hipLaunchKernelGGL((k_beam_search<false, HotArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls, plp,
+                       (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *hot);
+  else if (lm && alphas) {
     const GridArgs grid = {alphas, betas, L.pool / 4};
     hipLaunchKernelGGL((k_beam_search<true, LmArgs, GridArgs>), dim3(N, G), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt,
                        pcls, plp, (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *lm,
@@ -1000,7 +1353,7 @@ int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int 
 
 int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
                      int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets, long row_stride,
-                     int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm) {
+                     int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm, const HotArgs* hot) {
   DS2_REQUIRE(N > 0 && Tc >= 0 && C > 0 && C <= BEAM_MAXC && blank >= 0 && blank < C, DS2_ERR_ARG);
   DS2_REQUIRE(B >= 1 && B <= BEAM_MAXB && cutoff_top_n >= 1, DS2_ERR_ARG);
   const int K = cutoff_top_n < C ? cutoff_top_n : C;
@@ -1011,7 +1364,7 @@ int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc
   DS2_REQUIRE(!out || (row_stride >= 0 && out_ranks >= 1 && out_ranks <= B), DS2_ERR_ARG);
   DS2_REQUIRE(Tc > 0 ? (x && ws) : out, DS2_ERR_ARG);
   DS2_REQUIRE((((uintptr_t)ws | (uintptr_t)state) & 255) == 0, DS2_ERR_ALIGN);
-  const StreamLayout SL = stream_layout(N, B, max_frames, lm != nullptr);
+  const StreamLayout SL = stream_layout(N, B, max_frames, (lm ? kStreamFlagLm : 0) | (hot ? kStreamFlagHot : 0));
   const WsLayout L = stream_ws_layout(N, Tc);
   char* w = (char*)ws;
   char* sb = (char*)state;
@@ -1026,7 +1379,15 @@ int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc
     DS2_CHECK_LAUNCH();
   }
   const StreamArgs SA = {sb, SL.state_stride, max_frames, row_stride, out_ranks};
-  if (lm)
+  if (hot && lm)
+    hipLaunchKernelGGL((k_beam_search<true, LmArgs, HotArgs, StreamArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, Tc, C, sizes, blank, B, K,
+                       pcnt, pcls, plp, (int*)(sb + SL.parent), (int*)(sb + SL.label), (int*)(sb + SL.frame), tokens, offsets, lens,
+                       scores, *lm, *hot, SA);
+  else if (hot)
+    hipLaunchKernelGGL((k_beam_search<false, HotArgs, StreamArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, Tc, C, sizes, blank, B, K, pcnt,
+                       pcls, plp, (int*)(sb + SL.parent), (int*)(sb + SL.label), (int*)(sb + SL.frame), tokens, offsets, lens, scores,
+                       *hot, SA);
+  else if (lm)
     hipLaunchKernelGGL((k_beam_search<true, LmArgs, StreamArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, Tc, C, sizes, blank, B, K, pcnt,
                        pcls, plp, (int*)(sb + SL.parent), (int*)(sb + SL.label), (int*)(sb + SL.frame), tokens, offsets, lens, scores,
                        *lm, SA);

@@ -115,10 +115,15 @@ class BeamCTCDecoder:
     a word n-gram model of order 1 to 5 (KenLM binaries do not load); every completed word then adds
     ``alpha * ln P(word | context) + beta`` to its beam, and with ``lexicon=True`` (ctcdecode's dictionary, the default) only
     beams that spell vocabulary words survive.  ``alpha`` / ``beta`` are ignored without an LM (as in ctcdecode) and
-    ``num_processes`` is ignored (no CPU threads).  ``lexicon`` is a keyword of this class only."""
+    ``num_processes`` is ignored (no CPU threads).  ``lexicon`` is a keyword of this class only.
+
+    ``hotwords`` is a list of phrases the search should prefer (hotwords.py; DESIGN.md "ds2_beam", hot words): strings, or
+    (string, weight) pairs, the weight in natural-log units per non-space label (default ``hotword_weight``).  With an LM a hot
+    word outside its vocabulary is charged ``ln P = hot_oov_logp`` in place of -1000 and survives the lexicon.  ``None`` or an empty
+    list runs the entry points without hot words.  These three are keywords of this class only."""
 
     def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
-                 num_processes=4, blank_index=0, lexicon=True):
+                 num_processes=4, blank_index=0, lexicon=True, hotwords=None, hotword_weight=2.0, hot_oov_logp=-11.5):
         self.lm, self.lexicon, self._tables = None, bool(lexicon), {}
         if lm_path:
             from . import lm as _lm
@@ -135,6 +140,28 @@ class BeamCTCDecoder:
         self.lm_path, self.alpha, self.beta = lm_path, alpha, beta
         self.cutoff_top_n, self.cutoff_prob, self.beam_width = int(cutoff_top_n), float(cutoff_prob), int(beam_width)
         self.num_processes = num_processes
+        self.hotword_weight, self.hot_oov_logp = float(hotword_weight), float(hot_oov_logp)
+        if self.hot_oov_logp != self.hot_oov_logp or abs(self.hot_oov_logp) > 3.4e38:
+            raise ValueError("hot_oov_logp must be a finite fp32 value, got %r" % (hot_oov_logp,))
+        self.set_hotwords(hotwords)
+
+    def set_hotwords(self, hotwords):
+        """Replaces the hot phrases (None or an empty list: none).  ValueError, naming the phrase, for one that breaks the rules of
+        hotwords.py.  Calls and streams opened from now on use the new table; an open BeamStream keeps the one it was opened with."""
+        hotwords = list(hotwords) if hotwords else []
+        table = None
+        if hotwords:
+            from . import hotwords as _hot
+            table = _hot.build_table(hotwords, self.labels, self.blank_index, self.hotword_weight)
+        self.hotwords, self._hot_host, self._hot_dev = hotwords, table, {}
+
+    def _hot_table(self, device):
+        """The hot-word table on `device` (None without hot words): uploaded on first use, then kept until set_hotwords."""
+        if self._hot_host is None:
+            return None
+        if device not in self._hot_dev:
+            self._hot_dev[device] = torch.from_numpy(self._hot_host).to(device)
+        return self._hot_dev[device]
 
     def decode_beams(self, probs, sizes=None):
         """(strings, offsets, scores): strings[n] = beam_width transcripts (best first), offsets[n] = the matching int tensors of
@@ -155,10 +182,20 @@ class BeamCTCDecoder:
         LM, scores = acoustic - lm (the total that ranked the beams); without one the two are equal."""
         if not probs.is_cuda:
             probs = probs.to("cuda")
-        if self.lm is None:
+        ht = self._hot_table(probs.device)
+        if self.lm is None and ht is not None:
+            toks, offs, scores, acoustic = ops.beam_decode_hot(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
+                                                               self.cutoff_prob, self.space_index, ht)
+        elif self.lm is None:
             toks, offs, scores = ops.beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
                                                  self.cutoff_prob)
             acoustic = scores
+        elif ht is not None:
+            wt, gt = self._lm_tables(probs.device)
+            toks, offs, scores, acoustic = ops.beam_decode_lm_hot(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
+                                                                  self.cutoff_prob, self.space_index, wt, gt, self.lm.order,
+                                                                  self.lm.bos, self.alpha, self.beta, self.lexicon, ht,
+                                                                  self.hot_oov_logp)
         else:
             wt, gt = self._lm_tables(probs.device)
             toks, offs, scores, acoustic = ops.beam_decode_lm(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
@@ -173,6 +210,9 @@ class BeamCTCDecoder:
         (tokens [G, N, T'], offsets, lens [G, N], scores, acoustic).  ``self.alpha`` / ``self.beta`` play no part."""
         if self.lm is None:
             raise ValueError("BeamCTCDecoder.decode_grid searches language-model weights: it needs lm_path")
+        if self.hotwords:
+            raise ValueError("BeamCTCDecoder.decode_grid does not support hot words: the weight search is not boosted; call "
+                             "set_hotwords(None) first")
         points = [(float(a), float(b)) for a, b in points]
         if not points:
             raise ValueError("decode_grid needs at least one (alpha, beta) point")
@@ -222,8 +262,11 @@ class BeamStream:
             wt, gt = d._lm_tables(dev)
             lm = dict(space=d.space_index, word_table=wt, ngram_table=gt, order=d.lm.order, bos=d.lm.bos, alpha=d.alpha,
                       beta=d.beta, lexicon=d.lexicon)
+        ht, hot = d._hot_table(dev), None
+        if ht is not None:
+            hot = dict(space=d.space_index, table=ht, oov_logp=d.hot_oov_logp)
         self._h = ops.beam_stream_open(self.num_streams, self.max_frames, len(d.labels), d.blank_index, d.beam_width,
-                                       d.cutoff_top_n, d.cutoff_prob, dev, lm)
+                                       d.cutoff_top_n, d.cutoff_prob, dev, lm, hot)
         self.frames = [0] * self.num_streams
 
     def feed(self, probs, sizes=None):

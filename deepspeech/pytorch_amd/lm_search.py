@@ -18,6 +18,9 @@ class LMGridSearch:
             raise ValueError("LMGridSearch needs at least one (alpha, beta) point")
         if decoder is not None and getattr(decoder, "lm", None) is None:
             raise ValueError("LMGridSearch needs a BeamCTCDecoder with lm_path")
+        if decoder is not None and getattr(decoder, "hotwords", None):
+            raise ValueError("LMGridSearch does not support hot words: the weight search is not boosted; call "
+                             "set_hotwords(None) on the decoder first")
         self.decoder, self.max_ws_bytes = decoder, max_ws_bytes
         self.reset()
 

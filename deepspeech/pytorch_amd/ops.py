@@ -989,6 +989,91 @@ def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, s
     return toks, offs, sc[0], sc[1]
 
 
+def _hot_checks(Cc, device, blank, space, hot_table, hot_oov_logp=0.0):
+    """The argument checks of the hot-word calls: the space label, the table of hotwords.build_table on `device`, hot_oov_logp."""
+    if not 0 <= space < Cc or space == blank:
+        raise ValueError("space label %d must be one of the %d classes and differ from the blank (%d)" % (space, Cc, blank))
+    t = hot_table
+    if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous()):
+        raise ValueError("hot_table must be a contiguous int64 tensor of shape (slots, 2)")
+    if t.shape[0] < 2 or t.shape[0] & (t.shape[0] - 1):
+        raise ValueError("hot_table: the number of slots must be a power of two >= 2, got %d" % t.shape[0])
+    if t.device != device or not t.is_cuda:
+        raise ValueError("hot_table must live on the device of the probabilities (%s), not %s" % (device, t.device))
+    v = float(hot_oov_logp)
+    if v != v or v in (float("inf"), float("-inf")) or abs(v) > 3.4e38:
+        raise ValueError("hot_oov_logp must be a finite fp32 value, got %r" % (hot_oov_logp,))
+
+
+def _beam_outputs(N, B, T, dev):
+    return (torch.empty((2, N, B, T), dtype=torch.int32, device=dev), torch.empty((N, B), dtype=torch.int32, device=dev),
+            torch.empty((2, N, B), dtype=torch.float32, device=dev))
+
+
+def _beam_to_host(buf, lens, scores, N, B):
+    ln = lens.cpu().numpy()
+    width = max(int(ln.max()), 1)
+    host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
+    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(B)] for n in range(N)]
+    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(B)] for n in range(N)]
+    sc = scores.cpu()
+    return toks, offs, sc[0], sc[1]
+
+
+def _beam_no_frames(N, B):
+    """no frames: the only beam is the empty string, score 0 (it has earned no boost either)"""
+    scores = torch.full((N, B), float("inf"))
+    scores[:, 0] = 0.0
+    return [[[] for _ in range(B)] for _ in range(N)], \
+        [[torch.zeros(0, dtype=torch.int32) for _ in range(B)] for _ in range(N)], scores, scores.clone()
+
+
+def beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, hot_table):
+    """beam_decode with hot words (ds2_beam_decode_hot).  space: the space label; hot_table: the table of hotwords.build_table
+    as an int64 CUDA tensor of shape (slots, 2) on the device of probs.  Returns beam_decode's three values, scores being
+    -(log p + hot_end), the total that ranked the beams, and a host (N, B) float tensor of the acoustic -log p of the same beams."""
+    N, T, Cc = probs.shape
+    B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
+    _hot_checks(Cc, probs.device, blank, int(space), hot_table)
+    if N == 0 or T == 0:
+        return _beam_no_frames(N, B)
+    if probs.dtype != torch.float32:
+        probs = probs.float()
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    dev = probs.device
+    sz = sizes.to(dev, torch.int32) if sizes is not None else None
+    buf, lens, scores = _beam_outputs(N, B, T, dev)
+    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
+    call("ds2_beam_decode_hot", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob),
+         int(space), P(hot_table), hot_table.shape[0], P(buf[0]), P(buf[1]), P(lens), P(scores[0]), P(scores[1]), P(ws), S())
+    return _beam_to_host(buf, lens, scores, N, B)
+
+
+def beam_decode_lm_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, word_table, ngram_table, order, bos,
+                       alpha, beta, lexicon, hot_table, hot_oov_logp):
+    """beam_decode_lm with hot words (ds2_beam_decode_lm_hot): its arguments, the table of hotwords.build_table and the ln P that a
+    covered out-of-vocabulary word event is charged.  Returns beam_decode_lm's four values, scores being -((log p + lm) + hot_end)."""
+    B, top_n = _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos)
+    N, T, Cc = probs.shape
+    _hot_checks(Cc, probs.device, blank, int(space), hot_table, hot_oov_logp)
+    if N == 0 or T == 0:
+        return _beam_no_frames(N, B)
+    if probs.dtype != torch.float32:
+        probs = probs.float()
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    dev = probs.device
+    sz = sizes.to(dev, torch.int32) if sizes is not None else None
+    buf, lens, scores = _beam_outputs(N, B, T, dev)
+    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
+    call("ds2_beam_decode_lm_hot", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n,
+         float(cutoff_prob), int(space), P(word_table), word_table.shape[0], P(ngram_table), ngram_table.shape[0], int(order), int(bos),
+         float(alpha), float(beta), int(bool(lexicon)), P(hot_table), hot_table.shape[0], float(hot_oov_logp), P(buf[0]), P(buf[1]),
+         P(lens), P(scores[0]), P(scores[1]), P(ws), S())
+    return _beam_to_host(buf, lens, scores, N, B)
+
+
 def _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos):
     """The argument checks of beam_decode_lm, for its grid form; returns (B, top_n)."""
     return _beam_lm_checks_for(probs.shape[2], probs.device, beam_width, cutoff_top_n, blank, space, word_table, ngram_table,
@@ -1083,9 +1168,11 @@ class BeamStreamHandle:
         self.__dict__.update(kw)
 
 
-def beam_stream_open(num_streams, max_frames, num_classes, blank, beam_width, cutoff_top_n, cutoff_prob, device="cuda", lm=None):
+def beam_stream_open(num_streams, max_frames, num_classes, blank, beam_width, cutoff_top_n, cutoff_prob, device="cuda", lm=None,
+                     hot=None):
     """Opens N = num_streams resumable CTC prefix beam searches of up to max_frames frames each.  lm: None, or the dict of
-    beam_decode_lm's language-model arguments (space, word_table, ngram_table, order, bos, alpha, beta, lexicon).  The checks and
+    beam_decode_lm's language-model arguments (space, word_table, ngram_table, order, bos, alpha, beta, lexicon).  hot: None, or
+    the dict of the hot-word arguments (space, table, and with an LM oov_logp); the session keeps this table.  The checks and
     messages are beam_decode's / beam_decode_lm's.  The handle owns ds2_beam_stream_bytes(...) bytes of device memory: the
     states and the node pool, 12 * beam_width bytes per frame and stream.  Every stream starts fresh."""
     N, F, Cc = int(num_streams), int(max_frames), int(num_classes)
@@ -1103,12 +1190,19 @@ def beam_stream_open(num_streams, max_frames, num_classes, blank, beam_width, cu
                                        lm["order"], lm["bos"])
         lm = dict(lm, space=int(lm["space"]), order=int(lm["order"]), bos=int(lm["bos"]), alpha=float(lm["alpha"]),
                   beta=float(lm["beta"]), lexicon=bool(lm.get("lexicon", True)))
+    if hot is not None:
+        hot = dict(space=int(hot["space"]), table=hot["table"], oov_logp=float(hot.get("oov_logp", 0.0)))
+        _hot_checks(Cc, dev, blank, hot["space"], hot["table"], hot["oov_logp"])
+        if lm is not None and lm["space"] != hot["space"]:
+            raise ValueError("the language model and the hot words must name one space label, got %d and %d"
+                             % (lm["space"], hot["space"]))
     if (F + 1) * B > 2 ** 31 - 1:
         raise ValueError("max_frames=%d with beam_width=%d passes the node pool's 2^31 - 1 slots per stream" % (F, B))
-    state = torch.empty(query("ds2_beam_stream_bytes", N, B, F, int(lm is not None)), dtype=torch.uint8, device=dev)
+    flags = int(lm is not None) | (2 if hot is not None else 0)      # the flag word of the ds2_beam_stream_* size queries
+    state = torch.empty(query("ds2_beam_stream_bytes", N, B, F, flags), dtype=torch.uint8, device=dev)
     # state_stride: bytes between two streams' states at the front of the buffer; the node pool follows them
     h = BeamStreamHandle(state=state, N=N, B=B, max_frames=F, C=Cc, blank=int(blank), top_n=top_n, cutoff_prob=float(cutoff_prob),
-                         lm=lm, device=dev, state_stride=query("ds2_beam_stream_state_stride", B, int(lm is not None)))
+                         lm=lm, hot=hot, flags=flags, device=dev, state_stride=query("ds2_beam_stream_state_stride", B, flags))
     beam_stream_reset(h)
     return h
 
@@ -1138,7 +1232,7 @@ def beam_stream_reset(h, streams=None):
                 raise ValueError("stream index %d out of range for %d streams" % (int(n), h.N))
             m[int(n)] = 1
         mask = m.to(h.device)
-    call("ds2_beam_stream_reset", P(h.state), h.N, h.B, h.max_frames, int(h.lm is not None), P(mask), S())
+    call("ds2_beam_stream_reset", P(h.state), h.N, h.B, h.max_frames, h.flags, P(mask), S())
 
 
 def _beam_stream_call(h, probs, Tc, sz, row_stride, top_only=False):
@@ -1156,7 +1250,17 @@ def _beam_stream_call(h, probs, Tc, sz, row_stride, top_only=False):
     x = (P(probs), probs.stride(0), probs.stride(1)) if Tc > 0 else (P(None), 0, 0)
     out = (P(buf[0]), P(buf[1]), row_stride, R, P(lens), P(scores[0])) if buf is not None else \
         (P(None), P(None), 0, 0, P(None), P(None))
-    if h.lm is None:
+    acoustic = P(scores[1]) if buf is not None else P(None)
+    if h.hot is not None and h.lm is None:
+        call("ds2_beam_stream_feed_hot", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, h.hot["space"], P(h.hot["table"]),
+             h.hot["table"].shape[0], P(h.state), h.max_frames, *out, acoustic, P(ws), S())
+    elif h.hot is not None:
+        L = h.lm
+        call("ds2_beam_stream_feed_lm_hot", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, L["space"], P(L["word_table"]),
+             L["word_table"].shape[0], P(L["ngram_table"]), L["ngram_table"].shape[0], L["order"], L["bos"], L["alpha"], L["beta"],
+             int(L["lexicon"]), P(h.hot["table"]), h.hot["table"].shape[0], h.hot["oov_logp"], P(h.state), h.max_frames, *out,
+             acoustic, P(ws), S())
+    elif h.lm is None:
         call("ds2_beam_stream_feed", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, P(h.state), h.max_frames, *out,
              P(ws), S())
     else:
@@ -1172,7 +1276,7 @@ def _beam_stream_call(h, probs, Tc, sz, row_stride, top_only=False):
     toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(R)] for n in range(N)]
     offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(R)] for n in range(N)]
     sc = scores.cpu()
-    return (toks, offs, sc[0]) if h.lm is None else (toks, offs, sc[0], sc[1])
+    return (toks, offs, sc[0]) if h.lm is None and h.hot is None else (toks, offs, sc[0], sc[1])
 
 
 def _sizes_to_device(sizes, dev):

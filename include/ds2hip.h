@@ -505,6 +505,25 @@ int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N,
                             const float* betas, int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws,
                             ds2_stream_t stream);
 
+/* ---- hot words (DESIGN.md "ds2_beam", hot words) ---------------------------------------------------------------------------
+ * ds2_beam_decode / ds2_beam_decode_lm with a table of hot phrases: a beam earns a boost while its string ends in a prefix of a
+ * phrase, and keeps the boost of every phrase it has completed.  hot_table: the open-addressing table of hotwords.build_table,
+ * [hot_slots][2] 64-bit words (key = 61-bit string hash of a phrase prefix, value = v bits | c bits << 32 | whole phrase << 63),
+ * hot_slots a power of two >= 2, 16-byte aligned.  space: the label that ends a word (not the blank).  scores = -(log p + hot_end),
+ * with an LM -((log p + lm) + hot_end): the total that ranks the beams; acoustic [N][B] (may be null) = -log p of the same ranks.
+ * hot_oov_logp (finite): ln P charged to a word event whose word is out of vocabulary but covered by a hot phrase.  Everything
+ * else as ds2_beam_decode / ds2_beam_decode_lm, whose results these calls give bit for bit when every weight in the table is 0
+ * (with an LM: and every phrase word is in the vocabulary).  DS2_ERR_ARG: a null table, hot_slots no power of two >= 2, space
+ * out of range or the blank, a hot_oov_logp that is not finite, and all of the siblings'. */
+int ds2_beam_decode_hot(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                        int cutoff_top_n, float cutoff_prob, int space, const void* hot_table, long hot_slots, int* tokens,
+                        int* offsets, int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t stream);
+int ds2_beam_decode_lm_hot(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                           int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                           const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
+                           const void* hot_table, long hot_slots, float hot_oov_logp, int* tokens, int* offsets, int* lens,
+                           float* scores, float* acoustic, void* ws, ds2_stream_t stream);
+
 /* ---- resumable CTC prefix beam search: N streams fed chunk by chunk (DESIGN.md "ds2_beam_stream") --------------------------
  * After feeds that delivered frames [0, t_n) of stream n, the output stage gives what ds2_beam_decode / ds2_beam_decode_lm give on
  * those t_n frames, bit for bit (labels, frames, lengths, scores, acoustic scores).
@@ -528,11 +547,17 @@ int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N,
  * ds2_beam_stream_feed_lm: the same with the language model of ds2_beam_decode_lm; the output stage includes the end-of-utterance
  *   bonus and re-rank, which always look at all the live beams; acoustic [N][out_ranks] may be null.
  *   The consumed count never passes max_frames, so it needs no bound of its own.
+ * flags (the former `lm` argument of the two size queries and of ds2_beam_stream_reset; 0 and 1 mean what they meant): bit 0 a
+ *   language model, bit 1 hot words; any other bit gives size 0 / DS2_ERR_ARG.  Hot words add, from the next multiple of 8 bytes
+ *   after the other fields, 24 * B bytes (match hash, done, v, space value, flags), and 8 * B more (the partial-word hash) when
+ *   there is no LM: a stride of 16 + 64 * B bytes without an LM and 16 + align8(68 * B) + 24 * B with one, rounded up to 256.
+ * ds2_beam_stream_feed_hot / _feed_lm_hot: the same with the hot words of ds2_beam_decode_hot / _lm_hot, on a buffer sized with
+ *   flags 2 / 3; the output stage includes hot_end and the re-rank.
  * DS2_ERR_ARG: as ds2_beam_decode(_lm); outputs given in part, or out_ranks outside [1, B] with them; Tc == 0 without outputs; (max_frames + 1) * B > 2^31 - 1. */
-long ds2_beam_stream_bytes(int N, int B, int max_frames, int lm);
+long ds2_beam_stream_bytes(int N, int B, int max_frames, int flags);
 long ds2_beam_stream_ws_bytes(int N, int Tc);
-long ds2_beam_stream_state_stride(int B, int lm);
-int ds2_beam_stream_reset(void* state, int N, int B, int max_frames, int lm, const int* mask, ds2_stream_t stream);
+long ds2_beam_stream_state_stride(int B, int flags);
+int ds2_beam_stream_reset(void* state, int N, int B, int max_frames, int flags, const int* mask, ds2_stream_t stream);
 int ds2_beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
                          int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets,
                          long row_stride, int out_ranks, int* lens, float* scores, void* ws, ds2_stream_t stream);
@@ -541,6 +566,16 @@ int ds2_beam_stream_feed_lm(const float* x, long stride_n, long stride_t, int N,
                             const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
                             void* state, int max_frames, int* tokens, int* offsets, long row_stride, int out_ranks, int* lens,
                             float* scores, float* acoustic, void* ws, ds2_stream_t stream);
+int ds2_beam_stream_feed_hot(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                             int cutoff_top_n, float cutoff_prob, int space, const void* hot_table, long hot_slots, void* state,
+                             int max_frames, int* tokens, int* offsets, long row_stride, int out_ranks, int* lens, float* scores,
+                             float* acoustic, void* ws, ds2_stream_t stream);
+int ds2_beam_stream_feed_lm_hot(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank,
+                                int B, int cutoff_top_n, float cutoff_prob, int space, const void* word_table, long word_slots,
+                                const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
+                                const void* hot_table, long hot_slots, float hot_oov_logp, void* state, int max_frames, int* tokens,
+                                int* offsets, long row_stride, int out_ranks, int* lens, float* scores, float* acoustic, void* ws,
+                                ds2_stream_t stream);
 
 /* ---- exact chunked inference: conv front-end and lookahead with carried time context -------------
  * For a uni-directional model in eval mode: fed chunk by chunk, the three kernels below give the frames of the one-shot forward.

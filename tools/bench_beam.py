@@ -22,6 +22,12 @@ the one-shot call, the sum of the chunked feeds with one result fetch at the end
 and the first feed of a stream against the feed of its last CHUNK_FRAMES frames: the same chunk length, so the two differ only
 in the frames already consumed (the state is put back before every repetition, outside the timed interval).  The last of the
 chunked feeds is shorter where CHUNK_FRAMES does not divide T'; it is not the "last feed" that is timed on its own.
+
+    python tools/bench_beam.py --hot 100 [--lm tests/golden/lm/toy3.arpa] [--stream 100]
+
+With --hot the same widths are also timed through ops.beam_decode_hot (and, with --lm, ops.beam_decode_lm_hot; with --stream the
+hot streams too) on N synthetic phrases: half of them words cut from the input's own greedy transcripts, so that matches start,
+run on and complete, the other half random letter strings of one or two words.
 """
 import argparse
 import json
@@ -58,15 +64,31 @@ def timed(fn, runs, warmup=3, prep=None):
     return float(np.median(ms)), float(np.min(ms)), float(np.max(ms))
 
 
-def stream_rows(a, probs, lm, oneshot):
-    """the resumable search against the one-shot call oneshot(B), per width; lm: None or ops.beam_stream_open's dict"""
+def hot_phrases(probs, sizes, count, labels, seed=2):
+    """count phrases (weight 2.0 per label): half of them words of the input's greedy transcripts, half random letter strings"""
+    rng = np.random.default_rng(seed)
+    toks, _ = ops.greedy_decode(probs, sizes, 0)
+    words = sorted({w for t in toks for w in ''.join(labels[v] for v in t).split(' ') if 2 <= len(w) <= 8})
+    rng.shuffle(words)
+    letters = [c for c in labels[1:] if c != ' ']
+    out = list(words[:count // 2])
+    while len(out) < count:
+        w = ' '.join(''.join(rng.choice(letters, size=int(rng.integers(3, 9)))) for _ in range(int(rng.integers(1, 3))))
+        # no duplicate, and no phrase that followed by a space starts another (hotwords.py refuses both)
+        if w not in out and not any(o.startswith(w + ' ') or w.startswith(o + ' ') for o in out):
+            out.append(w)
+    return out
+
+
+def stream_rows(a, probs, lm, oneshot, hot=None):
+    """the resumable search against the one-shot call oneshot(B), per width; lm / hot: None or ops.beam_stream_open's dicts"""
     N, T, C = probs.shape
     Tc = a.stream
     assert 1 <= Tc <= T
     chunks = [probs[:, i:i + Tc] for i in range(0, T, Tc)]
     rows = []
     for B in [int(w) for w in a.widths.split(",")]:
-        h = ops.beam_stream_open(N, T, C, 0, B, a.top_n, 1.0, "cuda", lm)
+        h = ops.beam_stream_open(N, T, C, 0, B, a.top_n, 1.0, "cuda", lm, hot)
         states = h.state[:h.N * h.state_stride]          # what a feed reads and writes besides the pool slots of its own frames
 
         def chunked():
@@ -82,7 +104,7 @@ def stream_rows(a, probs, lm, oneshot):
         late = states.clone()
         fresh = lambda: ops.beam_stream_reset(h)
         resume = lambda: states.copy_(late)
-        row = dict(decoder="stream+lm" if lm else "stream", B=B, chunk=Tc, feeds=len(chunks))
+        row = dict(decoder="stream" + ("+lm" if lm else "") + ("+hot" if hot else ""), B=B, chunk=Tc, feeds=len(chunks))
         row["oneshot_ms"], row["oneshot_min"], row["oneshot_max"] = timed(lambda: oneshot(B), a.runs)
         row["chunked_ms"], row["chunked_min"], row["chunked_max"] = timed(chunked, a.runs)
         row["feed_ms"], row["feed_min"], row["feed_max"] = timed(lambda: ops.beam_stream_feed(h, chunks[0]), a.runs, prep=fresh)
@@ -174,6 +196,8 @@ def main():
     ap.add_argument("--open", action="store_true", help="open mode (lexicon=False)")
     ap.add_argument("--space-boost", type=float, default=0.0)
     ap.add_argument("--grid", default=None, help="with --lm: numbers of (alpha, beta) points, e.g. 1,8,64")
+    ap.add_argument("--hot", type=int, default=0, metavar="N", help="also time the hot-word entries on N synthetic phrases")
+    ap.add_argument("--hot-oov-logp", type=float, default=-11.5)
     ap.add_argument("--stream", type=int, default=None, metavar="CHUNK_FRAMES", help="also time the resumable search in chunks")
     a = ap.parse_args()
     assert a.runs >= 10
@@ -192,6 +216,21 @@ def main():
         med, lo, hi = timed(lambda: ops.beam_decode(probs, sizes, 0, B, a.top_n, 1.0), a.runs)
         rows.append(dict(decoder="beam", B=B, ms_per_batch=med, min_ms=lo, max_ms=hi, us_per_step=1e3 * med / T))
     notes = []
+    ht = None
+    if a.hot:
+        from deepspeech.pytorch_amd import hotwords as HW
+        from deepspeech.pytorch_amd.configs import LABELS
+        assert len(LABELS) == C and LABELS[C - 1] == ' '
+        phrases = hot_phrases(probs, sizes, a.hot, LABELS)
+        t0 = time.perf_counter()
+        table = HW.build_table(phrases, LABELS, 0, 2.0)
+        t1 = time.perf_counter()
+        ht = torch.from_numpy(table).cuda()
+        notes.append("# hot words: %d phrases (%d from the input's greedy transcripts), weight 2.0 per label; table build %.3f s, %d "
+                     "slots (%.1f KB)" % (len(phrases), a.hot // 2, t1 - t0, ht.shape[0], ht.numel() * 8 / 1e3))
+        for B in [int(w) for w in a.widths.split(",")]:
+            med, lo, hi = timed(lambda: ops.beam_decode_hot(probs, sizes, 0, B, a.top_n, 1.0, C - 1, ht), a.runs)
+            rows.append(dict(decoder="beam+hot", B=B, ms_per_batch=med, min_ms=lo, max_ms=hi, us_per_step=1e3 * med / T))
     if a.lm:
         from deepspeech.pytorch_amd import lm as LM
         from deepspeech.pytorch_amd.configs import LABELS
@@ -212,21 +251,33 @@ def main():
             med, lo, hi = timed(lambda: ops.beam_decode_lm(probs, sizes, 0, B, a.top_n, 1.0, C - 1, wt, gt, model.order, model.bos,
                                                            a.alpha, a.beta, not a.open), a.runs)
             rows.append(dict(decoder="beam+lm", B=B, ms_per_batch=med, min_ms=lo, max_ms=hi, us_per_step=1e3 * med / T))
+            if ht is not None:
+                med, lo, hi = timed(lambda: ops.beam_decode_lm_hot(probs, sizes, 0, B, a.top_n, 1.0, C - 1, wt, gt, model.order,
+                                                                   model.bos, a.alpha, a.beta, not a.open, ht, a.hot_oov_logp), a.runs)
+                rows.append(dict(decoder="beam+lm+hot", B=B, ms_per_batch=med, min_ms=lo, max_ms=hi, us_per_step=1e3 * med / T))
     if a.lm and a.grid:
         rows += grid_rows(a, probs, sizes, wt, gt, model, C)
     if a.stream:
         rows += stream_rows(a, probs, None, lambda B: ops.beam_decode(probs, sizes, 0, B, a.top_n, 1.0))
+        hot_args = None if ht is None else dict(space=C - 1, table=ht, oov_logp=a.hot_oov_logp)
+        if ht is not None:
+            rows += stream_rows(a, probs, None, lambda B: ops.beam_decode_hot(probs, sizes, 0, B, a.top_n, 1.0, C - 1, ht), hot_args)
         if a.lm:
             lm_args = dict(space=C - 1, word_table=wt, ngram_table=gt, order=model.order, bos=model.bos, alpha=a.alpha, beta=a.beta,
                            lexicon=not a.open)
             rows += stream_rows(a, probs, lm_args,
                                 lambda B: ops.beam_decode_lm(probs, sizes, 0, B, a.top_n, 1.0, C - 1, wt, gt, model.order, model.bos,
                                                              a.alpha, a.beta, not a.open))
+            if ht is not None:
+                rows += stream_rows(a, probs, lm_args,
+                                    lambda B: ops.beam_decode_lm_hot(probs, sizes, 0, B, a.top_n, 1.0, C - 1, wt, gt, model.order,
+                                                                     model.bos, a.alpha, a.beta, not a.open, ht, a.hot_oov_logp),
+                                    hot_args)
     lines = notes + ["# tools/bench_beam.py: N=%d T'=%d C=%d cutoff_top_n=%d softmax(normal * %.1f), median of %d calls after warm-up, %s"
              % (N, T, C, a.top_n, a.scale, a.runs, torch.cuda.get_device_name(0))]
     for r in rows:
         if r["decoder"].startswith("stream"):
-            lines.append("%-9s B=%-4d chunk=%-4d one-shot %8.3f ms (min %.3f, max %.3f) | %d feeds + result %8.3f ms (min %.3f, max %.3f) | "
+            lines.append("%-13s B=%-4d chunk=%-4d one-shot %8.3f ms (min %.3f, max %.3f) | %d feeds + result %8.3f ms (min %.3f, max %.3f) | "
                          "feed of frames 0..chunk %.3f ms, the same + result %.3f ms | feed of the first chunk frames %.3f ms (min %.3f, "
                          "max %.3f), of the last chunk frames (T'-chunk..T') %.3f ms (min %.3f, max %.3f)" % (r["decoder"], r["B"], r["chunk"], r["oneshot_ms"], r["oneshot_min"], r["oneshot_max"], r["feeds"],
                                         r["chunked_ms"], r["chunked_min"], r["chunked_max"], r["feed_ms"], r["feed_result_ms"],
@@ -236,7 +287,7 @@ def main():
             lines.append("%-7s B=%-4d G=%-3d %10.3f ms/call (min %.3f, max %.3f)  kernels %10.3f ms  %8.3f ms/point" %
                          (r["decoder"], r["B"], r["G"], r["ms_per_call"], r["min_ms"], r["max_ms"], r["kernel_ms"], r["ms_per_point"]))
             continue
-        lines.append("%-7s B=%-4s %9.3f ms/batch (min %.3f, max %.3f)  %8.2f us/step" %
+        lines.append("%-11s B=%-4s %9.3f ms/batch (min %.3f, max %.3f)  %8.2f us/step" %
                      (r["decoder"], r["B"] if r["B"] else "-", r["ms_per_batch"], r["min_ms"], r["max_ms"], r["us_per_step"]))
     lines.append(json.dumps(rows))
     text = "\n".join(lines)
