@@ -97,6 +97,13 @@ SIGNATURES = {
     "ds2_wave_ws_bytes": (_l, [_i]),
     "ds2_wave_energy": (_i, [_vp, _l, _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
     "ds2_wave_mix": (_i, [_vp, _l, _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _l, _vp]),
+    "ds2_resample_out_len": (_l, [_l, _i, _i]),
+    "ds2_resample_tile": (_i, [_i, _i, _i]),
+    "ds2_resample_plan": (_i, [_l, _i, _i, _i, _i, _i, _vp]),
+    "ds2_resample": (_i, [_vp, _l, _vp, _i, _vp, _i, _i, _i, _vp, _l, _vp, _vp]),
+    "ds2_resample_stream_state_bytes": (_l, [_i, _i]),
+    "ds2_resample_stream_ws_bytes": (_l, [_i, _i]),
+    "ds2_resample_stream_feed": (_i, [_vp, _l, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _l, _vp, _vp]),
     "ds2_greedy_decode":(_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ds2_beam_ws_bytes": (_l, [_i, _i, _i]),
     "ds2_beam_decode": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -1579,6 +1579,34 @@ def wsola(wav, nsamples, tempo, ldo, Smax, out=None):
     return out, ns_out, offsets
 
 
+def resample(wav, nsamples, taps, up, down, half_width, ldo, out=None):
+    """Every clip of wav (N, Lmax) (clip n = its first nsamples[n] samples) through the polyphase filter taps (up, 2 half_width) f32
+    on the device, `up` outputs per `down` inputs: ds2_resample.  ldo: row length of the output (the largest out_len of the batch).
+    Returns (out (N, ldo), nsamples_out [N] int32), both on the device; entries of out beyond a clip's own outputs are zero."""
+    wav, ns = _wave_batch(wav, nsamples)
+    N = wav.shape[0]
+    if out is None:
+        out = torch.empty((N, int(ldo)), dtype=torch.float32, device=wav.device)
+    if tuple(out.shape) != (N, int(ldo)) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("out must be a contiguous float32 (N, ldo) tensor")
+    ns_out = torch.empty(N, dtype=torch.int32, device=wav.device)
+    call("ds2_resample", P(wav), wav.stride(0), P(ns), N, P(taps), int(up), int(down), int(half_width), P(out), int(ldo), P(ns_out), S())
+    return out, ns_out
+
+
+def resample_stream_feed(wav, rows, n_rows, max_new, max_emit, capacity, taps, up, down, half_width, state):
+    """One feed of n_rows streams through the polyphase filter: ds2_resample_stream_feed.  wav (.., L) f32 chunks (None for
+    max_new = 0), rows = the device table of ds2_resample_stream_row, state = the carries of `capacity` slots.  Returns out
+    (n_rows, max_emit) f32: row r holds its emit outputs, zero beyond them."""
+    dev = state.device
+    out = torch.empty((n_rows, int(max_emit)), dtype=torch.float32, device=dev)
+    ws = torch.empty(query("ds2_resample_stream_ws_bytes", n_rows, int(half_width)), dtype=torch.uint8, device=dev)
+    call("ds2_resample_stream_feed", P(wav) if max_new else P(None), wav.stride(0) if max_new else 0, P(rows), n_rows, int(max_new),
+         int(max_emit), int(capacity), P(taps), int(up), int(down), int(half_width), P(state), P(out) if max_emit else P(None),
+         int(max_emit), P(ws), S())
+    return out
+
+
 def _noise_args(N, dev, level, bank, noise_off, noise_start):
     lv = _per_clip(level, N, dev, torch.float32, "level")
     if lv is None:

@@ -6,7 +6,9 @@ front-end's DFT GEMM is specialised for (the conv kernels take any bin count, ``
 to come from elsewhere); the window type follows ``SpectConfig.window`` (enums.py:8-14).  With ``augment=True`` the reference's
 ``spec_augment`` (loader/spec_augment.py:68-115, see ``augment.SpecAugment``) is folded into the same call.  A front-end built with
 ``wave_augment=augment.WaveAugment(...)`` first runs the loader's waveform augmentations (tempo, gain, noise injection,
-data_loader.py:151-159) on the device, so one call covers everything ``parse_audio`` does.
+data_loader.py:151-159) on the device, so one call covers everything ``parse_audio`` does.  Waveforms at another sample rate
+(``input_rate=44100``, ...) are converted to 16 kHz on the device in front of all that (``resample.Resampler``, DESIGN.md section
+7.2), one-shot and in ``stream()``.
 
 The reference's STFT lives in a third-party dependency that is not vendored and not pinned (``librosa``, requirements.txt:4):
 ``center=True`` padding is zeros in librosa >= 0.10 (``pad_mode="constant"``, the default here) and reflection before
@@ -72,7 +74,7 @@ def plan_wave(samples_before, n_new, final=False):
 
 class SpectrogramFrontEnd:
     def __init__(self, spect_cfg=None, normalize=True, pad_mode="constant", spec_augment=None, rng=None, wave_augment=None,
-                 running_floor=1e-5, running_prior=None):
+                 running_floor=1e-5, running_prior=None, input_rate=None):
         """normalize: True = (x - mean) / std over the whole utterance (the reference's), False = raw log-magnitudes, "running" =
         the causal mode: frame t is normalised with the statistics of frames 0..t, which is what
         ``stream()`` can reproduce bit for bit while the audio arrives.  running_floor: the mode's lower bound of the standard
@@ -80,7 +82,10 @@ class SpectrogramFrontEnd:
         from, None = none.  spec_augment: an ``augment.SpecAugment`` (None = its defaults) used by calls with ``augment=True``; rng: the
         numpy.random.Generator its draws come from (None = a fresh default_rng()).  wave_augment: an ``augment.WaveAugment``
         (None = none) applied to the waveforms of EVERY call, as the reference's loader applies tempo / gain / noise whenever its
-        configuration asks for them; its draws come from rng too, before those of SpecAugment."""
+        configuration asks for them; its draws come from rng too, before those of SpecAugment.  input_rate: the sample rate of
+        the waveforms handed in, in Hz (None or 16000 = they are at 16 kHz already and nothing is added to any call); any other
+        rate is converted to 16 kHz on the device first (``resample.Resampler``), and every count this class reports -- frames,
+        percentages, ``SpectStream.samples`` -- is one of the 16 kHz signal."""
         sr = getattr(spect_cfg, "sample_rate", 16000)
         n_fft = int(sr * getattr(spect_cfg, "window_size", 0.02))
         hop = int(sr * getattr(spect_cfg, "window_stride", 0.01))
@@ -105,6 +110,10 @@ class SpectrogramFrontEnd:
         self.last_coef = None            # device [N][3]: the time-warp flow coefficients of the latest augmented call
         self.wave_augment = wave_augment
         self.last_wave = None            # (WaveDraws, device [N][Smax] WSOLA offsets or None) of the latest call with wave_augment
+        self.resampler = None
+        if input_rate is not None and int(input_rate) != 16000:
+            from .resample import Resampler
+            self.resampler = Resampler(input_rate)
 
     def _basis_on(self, dev):
         b = self._basis.get(dev)
@@ -127,12 +136,17 @@ class SpectrogramFrontEnd:
         Lm = int(ns.max())
         if Lm > Lmax:
             raise ValueError("nsamples exceeds the waveform buffer")
+        ns_dev = None
+        if self.resampler is not None:   # everything below sees the 16 kHz signal and its lengths (known on the host in closed form)
+            wav, ns_dev, ns = self.resampler._run(wav, ns)
+            Lm = int(ns.max())
         if self.wave_augment is not None and self.wave_augment.active:
             return self._call_wave_augmented(wav, ns, augment)
         Tmax = 1 + Lm // HOP
         out = torch.empty((N, 1, N_BIN, Tmax), dtype=torch.float32, device=wav.device)
-        ns_dev = ns.to(wav.device)       # held in a local until the launch is enqueued (a temporary would be freed -- and its block
-        #                                  possibly re-used by the basis upload -- before the kernels read it)
+        if ns_dev is None:
+            ns_dev = ns.to(wav.device)   # held in a local until the launch is enqueued (a temporary would be freed -- and its block
+            #                              possibly re-used by the basis upload -- before the kernels read it)
         frames = 1 + ns.to(torch.int64) // HOP
         if augment:
             sa = self.spec_augment
@@ -169,7 +183,8 @@ class SpectrogramFrontEnd:
         """__call__ with the waveform augmentations in front: tempo (ds2_wsola), then gain / noise (ds2_wave_energy +
         ds2_wave_mix), then the spectrogram call on the new buffer.  Frame counts, percentages and Tmax follow the lengths after
         the tempo change, which the host knows in closed form (augment.wsola_out_len): nothing is read back.  wd: the WaveDraws
-        of these rows when they were drawn already (collate)."""
+        of these rows when they were drawn already (collate).  wav / ns are the 16 kHz signal: a front-end with input_rate has
+        resampled before it comes here."""
         wa, dev, N = self.wave_augment, wav.device, wav.shape[0]
         if wd is None:
             wd = wa.draw(ns.numpy(), self.rng)
@@ -228,7 +243,8 @@ class SpectrogramFrontEnd:
 
     def collate(self, waveforms, transcripts=None, int16_scale=False, augment=False):
         """waveforms: list of 1-D float tensors.  Sorts by length descending (as _collate_fn sorts by frame count,
-        data_loader.py:251; with wave_augment by the length AFTER the tempo change), pads, uploads and runs the front-end.
+        data_loader.py:251; with wave_augment by the length AFTER the tempo change; with input_rate the resampled length is
+        monotone in the given one, so the order is that of the 16 kHz clips), pads, uploads and runs the front-end.
         Returns (inputs, input_percentages, order), or -- with
         `transcripts` (one sequence of label indices per waveform) -- the reference's whole batch tuple
         (inputs, targets, input_percentages, target_sizes) in the sorted order, as _collate_fn builds it (data_loader.py:259-270).
@@ -240,7 +256,9 @@ class SpectrogramFrontEnd:
         if self.wave_augment is not None and self.wave_augment.active:
             # the reference augments every clip as the sampler hands it out and _collate_fn sorts the RESULTS: draw in the given
             # order, sort by the length after the tempo change (known on the host)
-            wd = self.wave_augment.draw([len(w) for w in waveforms], self.rng)
+            # (with input_rate: of the 16 kHz signal, the one the augmentations work on)
+            rs = self.resampler
+            wd = self.wave_augment.draw([len(w) if rs is None else rs.out_len(len(w)) for w in waveforms], self.rng)
             order = sorted(range(len(waveforms)), key=lambda i: -int(wd.nsamples[i]))
             wd = wd.take(order)
         else:
@@ -255,7 +273,10 @@ class SpectrogramFrontEnd:
         if wd is None:
             inputs, pct, _ = self(buf.cuda(), lens, augment=augment)
         else:
-            inputs, pct, _ = self._call_wave_augmented(buf.cuda(), torch.tensor(lens, dtype=torch.int32), augment, wd)
+            wav, ns = buf.cuda(), torch.tensor(lens, dtype=torch.int32)
+            if self.resampler is not None:
+                wav, _, ns = self.resampler._run(wav, ns)
+            inputs, pct, _ = self._call_wave_augmented(wav, ns, augment, wd)
         if transcripts is None:
             return inputs, pct, order
         tg = [torch.as_tensor(transcripts[i], dtype=torch.int64).reshape(-1) for i in order]
@@ -289,6 +310,8 @@ class SpectStream:
         S = self.capacity
         self._state = torch.zeros(query("ds2_spect_stream_state_bytes", S), dtype=torch.uint8, device=self.device)
         self.samples, self.ended, self._fresh = [0] * S, [False] * S, [True] * S
+        # a front-end with input_rate: the chunks arrive at that rate and pass a ResampleStream over the same slots first
+        self._resample = front_end.resampler.stream(S, self.device) if front_end.resampler is not None else None
 
     def reset(self, slots=None):
         """These slots (None = all) start a new stream: their carry and statistics read as empty from the next feed on; nothing
@@ -297,6 +320,8 @@ class SpectStream:
             if not 0 <= s < self.capacity:
                 raise ValueError("slot %d is not a slot of this stream (capacity %d)" % (s, self.capacity))
             self.samples[s], self.ended[s], self._fresh[s] = 0, False, True
+        if self._resample is not None:
+            self._resample.reset(slots)
 
     def frames(self, slot):
         """frames emitted so far for the slot's stream"""
@@ -306,8 +331,12 @@ class SpectStream:
     def feed(self, slots, wav, nsamples, final=()):
         """wav: [len(slots)][L] float32 on the device, row i = the nsamples[i] >= 0 new samples of slots[i]; final: the slots
         whose utterance ends with this feed.  Returns (spect (len(slots), 1, 161, Tc) float32 with Tc the largest count of new
-        frames -- possibly 0 --, frames [len(slots)] ints): row i holds frames[i] new frames, zero beyond them."""
+        frames -- possibly 0 --, frames [len(slots)] ints): row i holds frames[i] new frames, zero beyond them.  With the
+        front-end's input_rate the chunks are at that rate; ``samples`` and ``frames`` go on counting the 16 kHz signal."""
         fe, S = self.front_end, self.capacity
+        if self._resample is not None:        # the same argument checks, on the same slots: it refuses what this feed would refuse
+            slots, final = [int(s) for s in slots], [int(s) for s in final]
+            wav, nsamples = self._resample.feed(slots, wav, nsamples, final)
         sl, fin = [int(s) for s in slots], set(int(s) for s in final)
         if not sl or len(set(sl)) != len(sl) or any(not 0 <= s < S for s in sl):
             raise ValueError("slots must be distinct and lie in [0, %d), got %s" % (S, sl))

@@ -449,6 +449,49 @@ int ds2_wave_mix(const float* wav, long ldw, const int* nsamples, int N, const f
                  long bank_len, const long long* noise_off, const int* noise_start, const void* ws, float* out, long ldo,
                  ds2_stream_t stream);
 
+/* ---- rational polyphase resampling to 16 kHz (the reference converts its corpora with sox `rate` offline).
+ * g = gcd(in_rate, 16000), U = 16000 / g, D = in_rate / g, W = the half-width in input samples, taps [U][2W] f32 on the device,
+ * 8-byte aligned, U * 2W * 4 <= 128 KiB (resample.Resampler builds them on the host in fp64).  Output m of a clip x of n samples:
+ *   n0 = floor(m D / U), p = (m D) mod U (64-bit), y[m] = sum_j taps[p][j] x[n0 - W + 1 + j], x = 0 outside [0, n);  m < ceil(n U / D).
+ * The sum is acc = fma(taps[p][j], x, acc) from acc = 0 in rising j, in every entry: the order depends on the tap index alone.
+ * ds2_resample_out_len(n, U, D) = ceil(n U / D), ds2_resample_tile(U, D, W) = the consecutive outputs one workgroup computes: host
+ *   only.  ds2_resample: wav [N][ldw], nsamples [N] int32 (device) -> out [N][ldo], zero beyond a clip's outputs, and nsamples_out
+ *   [N] int32 (device) = min(out_len, ldo).
+ * Streaming: after G samples of a stream that has not ended, E(G) = 0 for G <= W, else ceil((G - W) U / D) outputs exist (those
+ *   whose last tap n0 + W has arrived); the end of the utterance completes ceil(G U / D).  A slot keeps the input samples from
+ *   max(0, n0(E) - W + 1) on, at most 2W - 1.
+ * ds2_resample_plan (host only): after samples_before samples, a feed of n_new more (final != 0: the utterance ends) -> out[0]
+ *   outputs before, out[1] outputs emitted, out[2] samples taken from the carry, out[3] samples carried on (0 after a final
+ *   feed), out[4] the clip position of the first carried sample.
+ * ds2_resample_stream_state_bytes(S, W): [S][2W] f32; ds2_resample_stream_ws_bytes(n_rows, W): [n_rows][2W] f32.
+ * ds2_resample_stream_feed: row r reads its n_new <= max_new <= ldw new samples from wav[src] and writes its emit <= max_emit <=
+ *   ldo outputs to out[r] (out [n_rows][ldo]), zeros from emit to max_emit; max_emit = 0 moves the carries alone.  A row with
+ *   fresh != 0 reads its slot's carry as empty, whatever the slot holds (carried and out_before must be 0 then); a final row
+ *   leaves its slot as it is.  The table lives on the device (8-byte aligned), so the entry cannot check it: slots distinct
+ *   (a slot outside [0, S) is skipped), src inside wav, the counts those of the plan.
+ * DS2_ERR_ARG: a null buffer that is read or written, wav == out, N or n_rows outside [1, 65535], S < n_rows, U, D or W < 1, a
+ *   table over 128 KiB, ldw < max_new, ldo < max_emit; DS2_ERR_ALIGN: taps or rows not 8-byte aligned.  Nothing is launched then. */
+typedef struct ds2_resample_stream_row {
+  int32_t slot;          /* the stream's state slot, 0 <= slot < S */
+  int32_t src;           /* the stream's row of wav */
+  int32_t carried;       /* samples taken from the slot's carry (0 for a fresh slot) */
+  int32_t n_new;         /* new samples */
+  int64_t out_before;    /* outputs of the stream that exist before this feed */
+  int32_t emit;          /* outputs this feed emits */
+  int32_t final;         /* the utterance ends with this feed */
+  int32_t fresh;         /* the slot's carry reads as that of a new stream */
+  int32_t pad;
+} ds2_resample_stream_row;
+long ds2_resample_out_len(long n, int U, int D);
+int ds2_resample_tile(int U, int D, int W);
+int ds2_resample_plan(long samples_before, int n_new, int final, int U, int D, int W, long* out);
+int ds2_resample(const float* wav, long ldw, const int* nsamples, int N, const float* taps, int U, int D, int W, float* out, long ldo,
+                 int* nsamples_out, ds2_stream_t stream);
+long ds2_resample_stream_state_bytes(int S, int W);
+long ds2_resample_stream_ws_bytes(int n_rows, int W);
+int ds2_resample_stream_feed(const float* wav, long ldw, const ds2_resample_stream_row* rows, int n_rows, int max_new, int max_emit, int S,
+                             const float* taps, int U, int D, int W, void* state, float* out, long ldo, void* ws, ds2_stream_t stream);
+
 /* ---- greedy CTC decoding on the device (validation_step, model.py:256 -> GreedyDecoder.decode, decoder.py:164-181) -------
  * x[n*stride_n + t*stride_t + c] f32 scores (probabilities or logits), C <= 64; sizes [N] int32 on the device (null = T).
  * Per sample: arg-max per frame (first maximum), repeats collapsed, blanks dropped.  tokens / offsets [N][T] int32 (the first

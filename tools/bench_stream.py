@@ -8,7 +8,7 @@ forward sweep takes h0/c0 and returns hn/cn).  Prints one JSON line per model: p
     python tools/bench_stream.py --decode beam [--beam-width 100]
     python tools/bench_stream.py --carry [--decode greedy --chunk 0.2 --streams 1]
     python tools/bench_stream.py --pool 8 [--chunk 0.2 --seconds 10 --pool-modes sessions,pool,session,pool_lockstep --pool-launches]
-    python tools/bench_stream.py --carry --wave      /      --pool 8 --wave
+    python tools/bench_stream.py --carry --wave      /      --pool 8 --wave      [--rate 48000]
 
 With --decode greedy|beam the drop-in class runs inside a streaming.StreamingTranscriber: every chunk's output goes to the decoder
 stream on the device and the best transcript so far comes back per chunk (no output leaves the device, nothing is decoded twice).
@@ -26,6 +26,8 @@ in which all S streams are open and none ends are timed.  --pool-launches adds t
 
 --wave (with --carry or --pool): the exact modes are fed raw audio, feed_wave instead of feed, in the same chunking (chunk seconds
 * 16000 samples a feed): the streaming front-end with running normalisation runs inside the timed feed.
+--rate R (with --wave): the audio arrives at R Hz, chunk seconds * R samples a feed, and the front-end is built with input_rate=R,
+so the resampler runs inside the timed feed as well.
 """
 import argparse
 import json
@@ -140,6 +142,15 @@ def _uni_lstm(dev):
     return m.to(dev).eval()
 
 
+def _front_end(a):
+    """--rate: a causal front-end that takes the audio at that rate; None = the sessions make their own 16 kHz one"""
+    if not a.rate:
+        return None
+    from deepspeech.pytorch_amd import configs
+    from deepspeech.pytorch_amd.spectrogram import SpectrogramFrontEnd
+    return SpectrogramFrontEnd(configs.SpectConfig(), normalize="running", input_rate=a.rate)
+
+
 def run_pool(a):
     """--pool: see the module docstring.  One JSON line per mode."""
     from deepspeech.pytorch_amd import configs, decoder as D, streaming
@@ -147,13 +158,14 @@ def run_pool(a):
     nch = int(a.seconds * 100) // tc
     m = _uni_lstm(dev)
     mk_dec = lambda: D.BeamCTCDecoder(configs.LABELS, beam_width=a.beam_width) if a.decode == "beam" else D.GreedyDecoder(configs.LABELS)
+    spc = int(round(a.chunk * (a.rate or 16000)))           # samples a wave feed brings per stream
     if a.wave:
-        audio = torch.from_numpy(0.1 * np.random.RandomState(0).standard_normal((S, nch * tc * 160)).astype(np.float32)).to(dev)
-        piece = lambda k, j: audio[k:k + 1, j * tc * 160:(j + 1) * tc * 160]
+        audio = torch.from_numpy(0.1 * np.random.RandomState(0).standard_normal((S, nch * spc)).astype(np.float32)).to(dev)
+        piece = lambda k, j: audio[k:k + 1, j * spc:(j + 1) * spc]
     else:
         audio = torch.from_numpy(np.random.RandomState(0).standard_normal((S, 1, 161, nch * tc)).astype(np.float32)).to(dev)
         piece = lambda k, j: audio[k:k + 1, :, :, j * tc:(j + 1) * tc]
-    per = tc * 160 if a.wave else tc                      # what a feed brings per stream: samples or frames
+    per = spc if a.wave else tc                           # what a feed brings per stream: samples or frames
     feed_of = lambda obj: obj.feed_wave if a.wave else obj.feed
     max_frames = nch * tc // 2 + 2
 
@@ -170,12 +182,13 @@ def run_pool(a):
         plan = ticks_of(starts)
         batches = [torch.cat([piece(k, j) for k, j in rows]).contiguous() for rows, _ in plan]      # the caller's batch, not timed
         if mode == "sessions":
-            sess = [streaming.StreamingTranscriber(m, mk_dec(), max_frames=max_frames, carry_context=True) for _ in range(S)]
+            sess = [streaming.StreamingTranscriber(m, mk_dec(), front_end=_front_end(a), max_frames=max_frames, carry_context=True)
+                    for _ in range(S)]
             xs = [[piece(k, j).contiguous() for k, j in rows] for rows, _ in plan]
         elif mode == "session":
-            sess = streaming.StreamingTranscriber(m, mk_dec(), max_frames=max_frames, carry_context=True)
+            sess = streaming.StreamingTranscriber(m, mk_dec(), front_end=_front_end(a), max_frames=max_frames, carry_context=True)
         else:
-            pool = streaming.StreamPool(m, mk_dec(), S, max_frames=max_frames)
+            pool = streaming.StreamPool(m, mk_dec(), S, max_frames=max_frames, front_end=_front_end(a))
         lat, launches = [], None
         for r in range(a.reps + 1 + int(a.pool_launches)):
             if mode == "sessions":
@@ -214,6 +227,7 @@ def run_pool(a):
         lat = np.array(lat)
         print(json.dumps({"metric": "one tick of S exact streams (every open stream advances one chunk)", "mode": mode, "streams": S,
                           "model": "uni-LSTM-1024x5+lookahead", "decode": a.decode or "greedy", "input": "wave" if a.wave else "spectrogram",
+                          "input_rate": (a.rate or 16000) if a.wave else None,
                           "chunk_seconds": a.chunk,
                           "chunks_per_stream": nch, "ticks_timed": int(lat.size), "ms_per_tick_median": round(float(np.median(lat)) * 1e3, 3),
                           "ms_per_tick_p95": round(float(np.percentile(lat, 95)) * 1e3, 3), "device_kernels_per_tick": launches,
@@ -239,9 +253,12 @@ def main():
     ap.add_argument("--pool-modes", default="sessions,pool,session,pool_lockstep")
     ap.add_argument("--pool-launches", action="store_true", help="--pool: also count the device kernels of one tick")
     ap.add_argument("--wave", action="store_true", help="--carry / --pool: feed raw audio (feed_wave) to the exact modes")
+    ap.add_argument("--rate", type=int, default=None, help="--wave: the sample rate of the audio fed (the front-end's input_rate)")
     a = ap.parse_args()
     if a.wave and not (a.pool or a.carry):
         raise SystemExit("--wave goes with --carry or --pool")
+    if a.rate and not a.wave:
+        raise SystemExit("--rate goes with --wave")
     if a.pool:
         return run_pool(a)
     from deepspeech.pytorch_amd import configs
@@ -284,13 +301,15 @@ def main():
                 dec = D.BeamCTCDecoder(configs.LABELS, beam_width=a.beam_width) if a.decode == "beam" else D.GreedyDecoder(configs.LABELS)
                 even = [c.expand(Ns, -1, -1, -1).contiguous() for c in chunks if c.shape[3] == tc]      # equal chunks only
                 if a.wave:
-                    wav = torch.from_numpy(0.1 * rs.standard_normal((Ns, len(even) * tc * 160)).astype(np.float32)).to(dev)
-                    even = [wav[:, i * tc * 160:(i + 1) * tc * 160].contiguous() for i in range(len(even))]
+                    spc = int(round(a.chunk * (a.rate or 16000)))
+                    wav = torch.from_numpy(0.1 * rs.standard_normal((Ns, len(even) * spc)).astype(np.float32)).to(dev)
+                    even = [wav[:, i * spc:(i + 1) * spc].contiguous() for i in range(len(even))]
                 for carry in ((True,) if a.wave else (False, True)):
-                    st = StreamingTranscriber(m, dec, max_frames=T // 2 + len(chunks), carry_context=carry)
+                    st = StreamingTranscriber(m, dec, front_end=_front_end(a), max_frames=T // 2 + len(chunks), carry_context=carry)
                     lat, total, text, emitted, frames = run_carry(st, even, a.reps, Ns, a.wave)
                     print(json.dumps({"metric": "session feed, chunked inference (StreamingTranscriber)", "model": name,
-                                      "carry_context": carry, "input": "wave" if a.wave else "spectrogram", "decode": a.decode or "greedy",
+                                      "carry_context": carry, "input": "wave" if a.wave else "spectrogram",
+                                      "input_rate": (a.rate or 16000) if a.wave else None, "decode": a.decode or "greedy",
                                       "streams": Ns, "audio_seconds": a.seconds,
                                       "chunk_seconds": a.chunk, "chunks": len(even), "latency_frames": st.latency_frames,
                                       "ms_per_feed_median": round(float(np.median(lat)) * 1e3, 3),
