@@ -127,6 +127,13 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp]),
     "ds2_beam_stream_feed_lm_hot": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _f, _f, _i,
                                          _vp, _l, _f, _vp, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_endpoint_state_bytes": (_l, [_i]),
+    "ds2_endpoint_ring_bytes": (_l, [_i, _i, _i, _l]),
+    "ds2_endpoint_reset": (_i, [_vp, _i, _vp, _vp]),
+    "ds2_endpoint_feed": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _f, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_endpoint_close": (_i, [_vp, _i, _vp, _vp, _vp]),
+    "ds2_endpoint_gather": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "ds2_endpoint_commit": (_i, [_vp, _vp, _vp, _l, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
     "ds2_stream_plan": (_i, [_l, _i, _i, _i, _vp]),
     "ds2_stream_state_bytes": (_l, [_i, _i, _i, _i, _i]),
     "ds2_stream_conv1": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

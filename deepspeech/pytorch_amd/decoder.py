@@ -8,6 +8,8 @@ labels travel to the host.  String building and the edit distance are host-side 
 model from an ARPA file when ``lm_path`` is given (ds2_beam_decode_lm, lm.py).
 When the reference's metric classes are importable the model uses THEM (with this decoder inside); the classes below are the
 stand-ins for images without torchmetrics / Levenshtein."""
+import collections
+
 import torch
 
 from . import ops
@@ -53,9 +55,60 @@ class GreedyDecoder:
         strings = [[''.join(' ' if v == self.space_index else self.int_to_char[v] for v in t)] for t in toks]
         return strings, [[o.to(torch.int)] for o in offs]
 
-    def stream(self, num_streams, device="cuda"):
-        """A GreedyStream: decode for num_streams streams that arrive chunk by chunk."""
+    def stream(self, num_streams, device="cuda", endpoint=None):
+        """A GreedyStream: decode for num_streams streams that arrive chunk by chunk.  endpoint: an Endpointer cuts every stream
+        into segments (EndpointedGreedyStream)."""
+        if endpoint is not None:
+            return EndpointedGreedyStream(self, num_streams, device, endpoint)
         return GreedyStream(self, num_streams, device)
+
+
+class Endpointer:
+    """The rule that cuts an endless stream of CTC posteriors into utterances.  Frame t is silent iff
+    its blank probability > blank_threshold (fp32, strict).  A segment ends at the first frame where, in this order, "silence":
+    it has a non-silent frame and min_trailing silent ones at its end; "leading": it has max_leading silent frames and no other;
+    "length": it has max_segment frames.  The counts are output frames (20 ms): the defaults are 1 s, 5 s and 20 s, the
+    conventional values for CTC endpointing, not tuned on any data."""
+
+    def __init__(self, blank_threshold=0.8, min_trailing=50, max_leading=250, max_segment=1000):
+        self.blank_threshold, self.min_trailing, self.max_leading, self.max_segment = ops.endpoint_rule_checks(
+            blank_threshold, min_trailing, max_leading, max_segment)
+
+    @property
+    def sub_feed(self):
+        """the longest chunk that cannot hold two endpoints of one stream: two endpoints lie at least min(min_trailing + 1,
+        max_leading, max_segment) frames apart"""
+        return min(self.min_trailing, self.max_leading, self.max_segment)
+
+    def check_max_frames(self, max_frames):
+        if self.max_segment > int(max_frames):
+            raise ValueError("max_segment=%d passes the stream's max_frames=%d: a segment must fit the node pool"
+                             % (self.max_segment, int(max_frames)))
+
+    def __repr__(self):
+        return "Endpointer(blank_threshold=%r, min_trailing=%d, max_leading=%d, max_segment=%d)" % (
+            self.blank_threshold, self.min_trailing, self.max_leading, self.max_segment)
+
+
+# a finished utterance: its number in the stream, its first and last frame (absolute; end = start - 1 for an empty "final" one),
+# why it ended, and its best beams as decode_beams gives them on probs[start : end + 1], the offsets as absolute stream frames;
+# acoustic: the beams' acoustic -log p; labels: the beams as label indices
+Segment = collections.namedtuple("Segment", "index start end reason strings offsets scores acoustic labels",
+                                 defaults=(None, None))
+
+
+def split_feed(sizes, limit):
+    """Cuts one feed into sub-feeds of at most `limit` frames per stream: [(t0, t1, sub_sizes)], sub-feed k holding the chunk's
+    frames [t0, t1) = [k * limit, ...) and stream n taking its first sub_sizes[n] of them.  Sub-feeds that no stream takes part in
+    are left out; per stream the sub-feeds' frames concatenate to its sizes[n] frames."""
+    limit = int(limit)
+    if limit < 1:
+        raise ValueError("the sub-feed limit must be >= 1, got %d" % limit)
+    out = []
+    for t0 in range(0, max(sizes, default=0), limit):
+        sub = [min(max(v - t0, 0), limit) for v in sizes]
+        out.append((t0, t0 + max(sub), sub))
+    return out
 
 
 def _stream_sizes(sizes, N, Tc):
@@ -107,6 +160,79 @@ class GreedyStream:
             self.offsets[n] = torch.cat([self.offsets[n], offs[n]])
             self.frames[n] += sz[n]
         return strings, offs
+
+
+class EndpointedGreedyStream(GreedyStream):
+    """A GreedyStream that an Endpointer cuts into segments on the device (ds2_endpoint_feed in front of every greedy feed).
+    ``text[n]`` / ``offsets[n]`` are the partial of the OPEN segment, ``segments()`` drains the finished ones; every segment's
+    text and offsets are GreedyDecoder.decode's on its frames alone, the offsets counted from the start of the stream.
+    ``frames[n]`` counts all the frames consumed.  The events ride on the fetch that every greedy feed makes anyway."""
+
+    def __init__(self, decoder, num_streams, device, endpoint):
+        e = self.endpoint = endpoint
+        self._ep = ops.endpoint_open(num_streams, decoder.blank_index, e.blank_threshold, e.min_trailing, e.max_leading,
+                                     e.max_segment, device)
+        self._start, self._labels = [0] * int(num_streams), [[] for _ in range(int(num_streams))]
+        self._done = [[] for _ in range(int(num_streams))]
+        super().__init__(decoder, num_streams, self._ep.device)
+
+    def reset(self, streams=None):
+        """Streams `streams` (None = all) start again at frame 0 and segment 0; their undrained segments are dropped."""
+        super().reset(streams)
+        ops.endpoint_reset(self._ep, streams)
+        for n in (range(self.num_streams) if streams is None else streams):
+            self._start[n], self._labels[n], self._done[n] = 0, [], []
+
+    def _finish(self, n, reason, start, end, index):
+        self._done[n].append(Segment(index, start, end, reason, [self.text[n]], [self.offsets[n]], None, None, [self._labels[n]]))
+        self._carry[n].zero_()
+        self.text[n], self.offsets[n], self._labels[n], self._start[n] = '', torch.zeros(0, dtype=torch.int), [], end + 1
+
+    def feed(self, probs, sizes=None):
+        """GreedyStream.feed; a chunk longer than endpoint.sub_feed frames is fed in pieces.  Returns (strings, offsets) of what
+        the chunk adds per stream, over all the segments it touches."""
+        d = self.decoder
+        if not probs.is_cuda:
+            probs = probs.to(self._carry.device)
+        if probs.dtype != torch.float32:
+            probs = probs.float()
+        if probs.stride(2) != 1:
+            probs = probs.contiguous()
+        sz = _stream_sizes(sizes, self.num_streams, probs.shape[1])
+        added = [''] * self.num_streams
+        added_offs = [[] for _ in range(self.num_streams)]
+        for t0, t1, take in split_feed(sz, self.endpoint.sub_feed):
+            x = probs[:, t0:t1]
+            while any(take):
+                cut, rest, ev = ops.endpoint_feed(self._ep, x, torch.tensor(take, dtype=torch.int32))
+                toks, offs = ops.greedy_stream_feed(x, cut, d.blank_index, self._carry)
+                take, reason, start, end, index = torch.cat([rest[None], ev]).cpu().tolist()
+                for n in range(self.num_streams):
+                    s = ''.join(' ' if v == d.space_index else d.int_to_char[v] for v in toks[n])
+                    o = offs[n].to(torch.int) + self._start[n]
+                    self.text[n] += s
+                    self.offsets[n] = torch.cat([self.offsets[n], o])
+                    self._labels[n] = self._labels[n] + toks[n]
+                    added[n] += s
+                    added_offs[n].append(o)
+                    if reason[n]:
+                        self._finish(n, ops.ENDPOINT_REASONS[reason[n]], start[n], end[n], index[n])
+                if any(take):
+                    x = ops.endpoint_gather(x, cut, rest)         # the frames after the cut: the next segment's first
+        self.frames = [f + v for f, v in zip(self.frames, sz)]
+        return added, [torch.cat(o) if o else torch.zeros(0, dtype=torch.int) for o in added_offs]
+
+    def end(self, streams=None):
+        """The open segment of streams `streams` (None = all) ends with reason "final"; it may be empty."""
+        streams = list(range(self.num_streams)) if streams is None else [int(n) for n in streams]
+        reason, start, end, index = ops.endpoint_close(self._ep, streams).cpu().tolist()
+        for n in streams:
+            self._finish(n, ops.ENDPOINT_REASONS[reason[n]], start[n], end[n], index[n])
+
+    def segments(self):
+        """Per stream the list of Segments finished since the last call."""
+        out, self._done = self._done, [[] for _ in range(self.num_streams)]
+        return out
 
 
 class BeamCTCDecoder:
@@ -241,9 +367,13 @@ class BeamCTCDecoder:
         strings, offsets, _ = self.decode_beams(probs, sizes)
         return strings, offsets
 
-    def stream(self, num_streams, max_frames, device="cuda"):
+    def stream(self, num_streams, max_frames, device="cuda", endpoint=None, nbest=1):
         """A BeamStream: this decoder's search for num_streams streams that arrive chunk by chunk, up to max_frames frames each
-        (the node pool costs 12 * beam_width bytes per frame and stream)."""
+        (the node pool costs 12 * beam_width bytes per frame and stream).  endpoint: an Endpointer cuts every stream into segments
+        of at most endpoint.max_segment <= max_frames frames (EndpointedBeamStream), so the stream itself has no bound; every
+        finished segment keeps its best `nbest` beams."""
+        if endpoint is not None:
+            return EndpointedBeamStream(self, num_streams, max_frames, device, endpoint, nbest)
         return BeamStream(self, num_streams, max_frames, device)
 
 
@@ -302,6 +432,94 @@ class BeamStream:
         ops.beam_stream_reset(self._h, streams)
         for n in streams:
             self.frames[n] = 0
+
+
+class EndpointedBeamStream(BeamStream):
+    """A BeamStream that an Endpointer cuts into segments on the device (ops.endpoint_beam_feed): when a
+    stream's segment ends, its best ``nbest`` beams -- what ``decode_beams`` gives on the segment's frames alone, bit for bit,
+    the end-of-utterance terms of a language model or of hot words included -- are kept on the device and the search starts again,
+    so a stream runs for any length on a node pool of max_frames >= endpoint.max_segment frames and ``feed`` never refuses for
+    length.  A feed waits for nothing; ``best()`` / ``result()`` give the OPEN segment's beams, ``segments()`` drains the finished
+    ones, and both fetch what has ended in between.  The device keeps at most RING_SLOTS finished segments per stream: after that
+    many device feeds without a fetch, the feed fetches (the one host wait that feeding can take; a chunk longer than
+    endpoint.sub_feed frames is several device feeds).  Offsets are absolute stream frames; ``frames[n]`` counts all frames."""
+
+    RING_SLOTS = 8
+
+    def __init__(self, decoder, num_streams, max_frames, device, endpoint, nbest=1):
+        endpoint.check_max_frames(max_frames)
+        super().__init__(decoder, num_streams, max_frames, device)
+        e = self.endpoint = endpoint
+        self.nbest = int(nbest)
+        self._ep = ops.endpoint_open(self.num_streams, decoder.blank_index, e.blank_threshold, e.min_trailing, e.max_leading,
+                                     e.max_segment, self._h.device)
+        self._sink = ops.endpoint_sink_open(self._h, self.nbest, e.max_segment, self.RING_SLOTS)
+        self._done, self._since = [[] for _ in range(self.num_streams)], 0
+
+    def feed(self, probs, sizes=None):
+        """BeamStream.feed without the bound: a chunk longer than endpoint.sub_feed frames is fed in pieces, each of which can
+        end at most one segment per stream."""
+        sz = _stream_sizes(sizes, self.num_streams, probs.shape[1])
+        if not probs.is_cuda:
+            probs = probs.to(self._h.device)
+        if probs.dtype != torch.float32:
+            probs = probs.float()
+        for t0, t1, sub in split_feed(sz, self.endpoint.sub_feed):
+            ops.endpoint_beam_feed(self._ep, self._h, self._sink, probs[:, t0:t1], torch.tensor(sub, dtype=torch.int32))
+            self._fed_once()
+        self.frames = [f + v for f, v in zip(self.frames, sz)]
+
+    def _fed_once(self):
+        self._since += 1
+        if self._since >= self.RING_SLOTS:       # a ring may be full: fetch before the next segment can end
+            self._fetch()
+
+    def _fetch(self):
+        d = self.decoder
+        for n, segs in enumerate(ops.endpoint_sink_fetch(self._sink)):
+            for s in segs:
+                self._done[n].append(Segment(s["index"], s["start"], s["end"], s["reason"],
+                                             [''.join(d.int_to_char[v] for v in t) for t in s["labels"]],
+                                             [o.to(torch.int) + s["start"] for o in s["offsets"]], s["scores"], s["acoustic"],
+                                             s["labels"]))
+        self._since = 0
+
+    def _open_beams(self, top_only):
+        res = ops.beam_stream_result(self._h, min(max(self.frames), self.endpoint.max_segment), top_only=top_only)
+        start = ops.endpoint_state(self._ep)[:, 0].tolist()
+        self._fetch()
+        strings, offsets, scores = self._strings(res)
+        return strings, [[o + start[n] for o in beams] for n, beams in enumerate(offsets)], scores
+
+    def result(self):
+        """(strings, offsets, scores) in decode_beams' shapes for the open segment of every stream."""
+        return self._open_beams(False)
+
+    def best(self):
+        """The top beam of every stream's open segment (the partial): (strings[n], offsets[n])."""
+        strings, offsets, _ = self._open_beams(True)
+        return [s[0] for s in strings], [o[0] for o in offsets]
+
+    def end(self, streams=None):
+        """The open segment of streams `streams` (None = all) ends with reason "final"; it may be empty.  Feeding may go on:
+        the next frame starts the next segment."""
+        ops.endpoint_beam_close(self._ep, self._h, self._sink, None if streams is None else [int(n) for n in streams])
+        self._fed_once()
+
+    def segments(self):
+        """Per stream the list of Segments finished since the last call, in the order they ended."""
+        self._fetch()
+        out, self._done = self._done, [[] for _ in range(self.num_streams)]
+        return out
+
+    def reset(self, streams=None):
+        """Streams `streams` (None = all) start again: frame 0, segment 0, the empty beam; their undrained segments are dropped."""
+        self._fetch()
+        streams = list(range(self.num_streams)) if streams is None else [int(n) for n in streams]
+        super().reset(streams)
+        ops.endpoint_reset(self._ep, streams)
+        for n in streams:
+            self._done[n] = []
 
 
 def _edit_distance(a, b):

@@ -1246,6 +1246,22 @@ def _beam_stream_call(h, probs, Tc, sz, row_stride, top_only=False):
         buf = torch.empty((2, N, R, row_stride), dtype=torch.int32, device=dev)
         lens = torch.empty((N, R), dtype=torch.int32, device=dev)
         scores = torch.empty((2, N, R), dtype=torch.float32, device=dev)
+    _beam_stream_launch(h, probs, Tc, sz, buf, lens, scores, row_stride, R)
+    if buf is None:
+        return None
+    ln = lens.cpu().numpy()
+    width = min(max(int(ln.max()), 1), row_stride)
+    host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
+    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(R)] for n in range(N)]
+    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(R)] for n in range(N)]
+    sc = scores.cpu()
+    return (toks, offs, sc[0]) if h.lm is None and h.hot is None else (toks, offs, sc[0], sc[1])
+
+
+def _beam_stream_launch(h, probs, Tc, sz, buf, lens, scores, row_stride, R):
+    """the launches of _beam_stream_call on the caller's output tensors (buf (2, N, R, row_stride) int32, lens (N, R) int32, scores
+    (2, N, R) f32: ranking and acoustic), or without the output stage (buf None); nothing is fetched"""
+    dev, N, B = h.device, h.N, h.B
     ws = torch.empty(query("ds2_beam_stream_ws_bytes", N, Tc), dtype=torch.uint8, device=dev) if Tc > 0 else None
     x = (P(probs), probs.stride(0), probs.stride(1)) if Tc > 0 else (P(None), 0, 0)
     out = (P(buf[0]), P(buf[1]), row_stride, R, P(lens), P(scores[0])) if buf is not None else \
@@ -1268,15 +1284,6 @@ def _beam_stream_call(h, probs, Tc, sz, row_stride, top_only=False):
         call("ds2_beam_stream_feed_lm", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, L["space"], P(L["word_table"]),
              L["word_table"].shape[0], P(L["ngram_table"]), L["ngram_table"].shape[0], L["order"], L["bos"], L["alpha"], L["beta"],
              int(L["lexicon"]), P(h.state), h.max_frames, *out, P(scores[1]) if buf is not None else P(None), P(ws), S())
-    if buf is None:
-        return None
-    ln = lens.cpu().numpy()
-    width = min(max(int(ln.max()), 1), row_stride)
-    host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
-    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(R)] for n in range(N)]
-    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(R)] for n in range(N)]
-    sc = scores.cpu()
-    return (toks, offs, sc[0]) if h.lm is None and h.hot is None else (toks, offs, sc[0], sc[1])
 
 
 def _sizes_to_device(sizes, dev):
@@ -1326,6 +1333,198 @@ def beam_stream_header(h):
     """Host (N, 3) int32 tensor: per stream the frames consumed, the live beams and the overflow flag (waits for the device)."""
     hdr = h.state[:h.state_stride * h.N].view(h.N, h.state_stride)[:, :16].contiguous().view(torch.int32)
     return hdr[:, :3].cpu()
+
+
+ENDPOINT_REASONS = (None, "silence", "leading", "length", "final")     # the reason codes of ds2_endpoint_feed / _close
+ENDPOINT_STATE_WORDS = 8      # int32 per stream: segment start, trailing, spoken, frames consumed, segments finished, 3 reserved
+
+
+class EndpointHandle:
+    """The device state of N endpointers (ds2_endpoint_*) and their rule.  Made by endpoint_open."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def endpoint_rule_checks(blank_threshold, min_trailing, max_leading, max_segment):
+    """The checks of the endpointing rule's parameters; returns them as (float, int, int, int)."""
+    thr = float(blank_threshold)
+    if not 0.0 < thr < 1.0:
+        raise ValueError("blank_threshold must lie in (0, 1), got %r" % (blank_threshold,))
+    counts = []
+    for name, v in (("min_trailing", min_trailing), ("max_leading", max_leading), ("max_segment", max_segment)):
+        if int(v) != v or int(v) < 1:
+            raise ValueError("%s must be a frame count >= 1, got %r" % (name, v))
+        counts.append(int(v))
+    return (thr,) + tuple(counts)
+
+
+def endpoint_open(num_streams, blank, blank_threshold, min_trailing, max_leading, max_segment, device="cuda"):
+    """Opens N = num_streams endpointers with one rule; `blank` is the class whose probability says
+    silence.  The handle owns ds2_endpoint_state_bytes(N) bytes of device memory.  Every stream starts at frame 0, segment 0."""
+    N = int(num_streams)
+    dev = torch.device(device)
+    if N < 1:
+        raise ValueError("an endpointer needs num_streams >= 1, got %d" % N)
+    if dev.type != "cuda":
+        raise ValueError("an endpointer lives on a HIP device, not on %s" % dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if int(blank) < 0:
+        raise ValueError("blank index %d must not be negative" % blank)
+    thr, mt, ml, ms = endpoint_rule_checks(blank_threshold, min_trailing, max_leading, max_segment)
+    state = torch.empty(query("ds2_endpoint_state_bytes", N) // 4, dtype=torch.int32, device=dev).view(N, ENDPOINT_STATE_WORDS)
+    h = EndpointHandle(state=state, N=N, blank=int(blank), blank_threshold=thr, min_trailing=mt, max_leading=ml, max_segment=ms,
+                       device=dev)
+    endpoint_reset(h)
+    return h
+
+
+def _stream_mask(streams, N, dev):
+    """a device int32 mask of the stream indices `streams` (None stays None = all)"""
+    if streams is None:
+        return None
+    m = torch.zeros(N, dtype=torch.int32)
+    for n in streams:
+        if not 0 <= int(n) < N:
+            raise ValueError("stream index %d out of range for %d streams" % (int(n), N))
+        m[int(n)] = 1
+    return m.pin_memory().to(dev, non_blocking=True)
+
+
+def endpoint_reset(h, streams=None):
+    """Streams `streams` (indices; None = all) start again at frame 0 and segment 0; the others are untouched."""
+    call("ds2_endpoint_reset", P(h.state), h.N, P(_stream_mask(streams, h.N, h.device)), S())
+
+
+def endpoint_feed(h, probs, sizes=None):
+    """Advances the endpointers of h over one chunk (ds2_endpoint_feed).  probs: (N, Tc, C) CUDA tensor of probabilities with a
+    contiguous class dimension; sizes: [N] ints (tensor or sequence; None = Tc), frames at and beyond them are never read.  Per
+    stream the state stops at the first endpoint.  Returns three DEVICE int32 tensors and does not wait for them: cut [N] (the
+    chunk's frames that belong to the open segment), rest [N] = sizes - cut, events (4, N) = rows (reason, start, end, index), zero
+    where no endpoint fell; reason indexes ENDPOINT_REASONS."""
+    if not (torch.is_tensor(probs) and probs.dim() == 3 and probs.shape[0] == h.N and probs.shape[1] >= 1
+            and probs.shape[2] > h.blank):
+        raise ValueError("a chunk for this endpointer has shape (%d, Tc >= 1, C > %d), got %s"
+                         % (h.N, h.blank, tuple(probs.shape) if torch.is_tensor(probs) else type(probs).__name__))
+    if probs.dtype != torch.float32:
+        probs = probs.float()
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    sz = _sizes_to_device(sizes, h.device)
+    if sz is not None and sz.shape != (h.N,):
+        raise ValueError("sizes must have one entry per stream (%d), got shape %s" % (h.N, tuple(sz.shape)))
+    out = torch.empty((6, h.N), dtype=torch.int32, device=h.device)
+    call("ds2_endpoint_feed", P(probs), probs.stride(0), probs.stride(1), h.N, probs.shape[1], probs.shape[2], P(sz), h.blank,
+         h.blank_threshold, h.min_trailing, h.max_leading, h.max_segment, P(h.state), P(out[0]), P(out[1]), P(out[2:]), S())
+    return out[0], out[1], out[2:]
+
+
+def endpoint_close(h, streams=None):
+    """The open segment of streams `streams` (None = all) ends with reason "final" (ds2_endpoint_close); returns the device
+    events (4, N) as endpoint_feed does."""
+    ev = torch.empty((4, h.N), dtype=torch.int32, device=h.device)
+    call("ds2_endpoint_close", P(h.state), h.N, P(_stream_mask(streams, h.N, h.device)), P(ev), S())
+    return ev
+
+
+def endpoint_state(h):
+    """Host (N, 5) int32 tensor: per stream the open segment's start, trailing, spoken, the frames consumed and the segments
+    finished (waits for the device)."""
+    return h.state[:, :5].cpu()
+
+
+def endpoint_gather(probs, cut, rest):
+    """The frames after the cut at the front of a new contiguous (N, Tc, C) chunk: y[n, :rest[n]] = probs[n, cut[n] : cut[n] +
+    rest[n]] (ds2_endpoint_gather); cut, rest: device int32 [N].  The other frames of y are uninitialised."""
+    N, Tc, Cc = probs.shape
+    y = torch.empty((N, Tc, Cc), dtype=torch.float32, device=probs.device)
+    call("ds2_endpoint_gather", P(probs), probs.stride(0), probs.stride(1), N, Tc, Cc, P(cut), P(rest), P(y), S())
+    return y
+
+
+class EndpointSink:
+    """Where finished segments wait on the device (endpoint_sink_open): the output stage's tensors of one beam feed and the ring."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def endpoint_sink_open(bh, ranks, row_stride, slots):
+    """For the beam streams of handle bh: the stage that a feed's output stage writes (`ranks` best beams per stream, rows of
+    row_stride labels) and a ring of `slots` finished segments per stream, ds2_endpoint_ring_bytes(...) bytes."""
+    N, R, rs, K = bh.N, int(ranks), int(row_stride), int(slots)
+    if not 1 <= R <= bh.B:
+        raise ValueError("nbest must be in [1, beam_width = %d], got %d" % (bh.B, R))
+    if rs < 1 or K < 1:
+        raise ValueError("a segment sink needs row_stride >= 1 and slots >= 1, got %d and %d" % (rs, K))
+    dev = bh.device
+    words = 4 + 3 * R + 2 * R * rs
+    ring = torch.empty(query("ds2_endpoint_ring_bytes", N, K, R, rs) // 4, dtype=torch.int32, device=dev).view(N, K, words)
+    return EndpointSink(N=N, ranks=R, row_stride=rs, slots=K, words=words, ring=ring,
+                        pending=torch.zeros(N, dtype=torch.int32, device=dev),
+                        buf=torch.empty((2, N, R, rs), dtype=torch.int32, device=dev),
+                        lens=torch.empty((N, R), dtype=torch.int32, device=dev),
+                        scores=torch.empty((2, N, R), dtype=torch.float32, device=dev),
+                        acoustic=bh.lm is not None or bh.hot is not None)
+
+
+def endpoint_beam_feed(eh, bh, sink, probs, sizes=None):
+    """One chunk through the endpointers eh and the beam streams bh, at most one endpoint per stream (the caller keeps chunks to
+    min(min_trailing, max_leading, max_segment) frames).  Launch sequence, nothing waits for the device: ds2_endpoint_feed;
+    the beam feed of the frames up to the cut with the output stage into the sink's stage; ds2_endpoint_commit, which moves the
+    ended streams' rows into their ring; ds2_beam_stream_reset with the events' reason row as its mask; and, for chunks of more
+    than one frame, ds2_endpoint_gather, ds2_endpoint_feed and the beam feed again on the frames after the cut."""
+    if probs.dtype != torch.float32:
+        probs = probs.float()
+    if probs.stride(2) != 1:
+        probs = probs.contiguous()
+    cut, rest, ev = endpoint_feed(eh, probs, sizes)
+    _beam_stream_launch(bh, probs, probs.shape[1], cut, sink.buf, sink.lens, sink.scores, sink.row_stride, sink.ranks)
+    _endpoint_commit(ev, sink)
+    call("ds2_beam_stream_reset", P(bh.state), bh.N, bh.B, bh.max_frames, bh.flags, P(ev[0]), S())
+    if probs.shape[1] > 1:                       # a chunk of one frame has no frames after a cut
+        y = endpoint_gather(probs, cut, rest)
+        endpoint_feed(eh, y, rest)               # no second endpoint can fall here: the chunk is too short for two
+        _beam_stream_launch(bh, y, y.shape[1], rest, None, None, None, None, 0)
+
+
+def endpoint_beam_close(eh, bh, sink, streams=None):
+    """The open segments of `streams` (None = all) end with reason "final": their beams, with the end-of-utterance terms of the
+    output stage, go to the ring and their searches start again.  Nothing waits for the device."""
+    ev = endpoint_close(eh, streams)
+    _beam_stream_launch(bh, None, 0, None, sink.buf, sink.lens, sink.scores, sink.row_stride, sink.ranks)
+    _endpoint_commit(ev, sink)
+    call("ds2_beam_stream_reset", P(bh.state), bh.N, bh.B, bh.max_frames, bh.flags, P(ev[0]), S())
+
+
+def _endpoint_commit(ev, k):
+    call("ds2_endpoint_commit", P(ev), P(k.buf[0]), P(k.buf[1]), k.row_stride, k.ranks, P(k.lens), P(k.scores[0]),
+         P(k.scores[1]) if k.acoustic else P(None), k.N, P(k.ring), P(k.pending), k.slots, S())
+
+
+def endpoint_sink_fetch(k):
+    """Fetches and empties the ring (waits for the device).  Returns per stream a list of finished segments in the order they
+    ended, each a dict: reason (a string of ENDPOINT_REASONS), start, end, index, labels (ranks lists of ints), offsets (ranks
+    int32 tensors, frames counted from the segment's start), scores and acoustic (f32 tensors [ranks])."""
+    pend = k.pending.cpu().tolist()
+    out = [[] for _ in range(k.N)]
+    top = max(pend)
+    if top == 0:
+        return out
+    R, rs = k.ranks, k.row_stride
+    host = k.ring[:, :min(top, k.slots)].cpu()
+    k.pending.zero_()
+    for n in range(k.N):
+        for s in range(min(pend[n], k.slots)):
+            w = host[n, s]
+            lens = w[4:4 + R].tolist()
+            sc = w[4 + R:4 + 3 * R].view(torch.float32).clone()
+            tok, off = w[4 + 3 * R:4 + 3 * R + R * rs].view(R, rs), w[4 + 3 * R + R * rs:].view(R, rs)
+            out[n].append(dict(reason=ENDPOINT_REASONS[int(w[0])], start=int(w[1]), end=int(w[2]), index=int(w[3]),
+                               labels=[tok[r, :lens[r]].tolist() for r in range(R)],
+                               offsets=[off[r, :lens[r]].clone() for r in range(R)], scores=sc[:R], acoustic=sc[R:]))
+    return out
 
 
 def greedy_stream_feed(scores, sizes, blank, carry):

@@ -61,12 +61,18 @@ def plan_feed(frames, chunk, ctx, final=False):
 
 
 class StreamingTranscriber:
-    def __init__(self, model, decoder, front_end=None, max_frames=6000, carry_context=False):
+    def __init__(self, model, decoder, front_end=None, max_frames=6000, carry_context=False, endpoint=None):
         """model: a DeepSpeech on a HIP device; decoder: a BeamCTCDecoder or GreedyDecoder over the model's labels; front_end: a
         SpectrogramFrontEnd for feed_wave (None = one with the model's spect_cfg, made on first use).  max_frames bounds the output
         frames per stream of a beam decoder (its node pool is allocated at the first feed).  carry_context: exact chunked
-        inference (module docstring); uni-directional models only -- a reverse direction cannot be streamed exactly."""
+        inference (module docstring); uni-directional models only -- a reverse direction cannot be streamed exactly.
+        endpoint: a decoder.Endpointer cuts every stream into utterances on the device: feeds return
+        the partial of the open segment, ``segments()`` drains the finished ones, max_frames bounds a segment and not the stream,
+        and only the decoder starts again at an endpoint -- the acoustic state runs on."""
         self.model, self.decoder, self.front_end, self.max_frames = model, decoder, front_end, int(max_frames)
+        self.endpoint = endpoint
+        if endpoint is not None and isinstance(decoder, BeamCTCDecoder):
+            endpoint.check_max_frames(self.max_frames)
         self.hs, self.stream = None, None
         self.carry_context = bool(carry_context)
         if self.carry_context and model.bidirectional:
@@ -78,9 +84,15 @@ class StreamingTranscriber:
 
     def _open(self, N, device):
         if isinstance(self.decoder, BeamCTCDecoder):
-            self.stream = self.decoder.stream(N, self.max_frames, device)
+            self.stream = self.decoder.stream(N, self.max_frames, device, endpoint=self.endpoint)
         else:
-            self.stream = self.decoder.stream(N, device)
+            self.stream = self.decoder.stream(N, device, endpoint=self.endpoint)
+
+    def segments(self):
+        """endpoint: per stream the list of decoder.Segments finished since the last call"""
+        if self.endpoint is None:
+            raise ValueError("segments() belongs to a session with an endpoint")
+        return self.stream.segments() if self.stream is not None else []
 
     @property
     def frames(self):
@@ -283,6 +295,9 @@ class StreamingTranscriber:
                     self.last_output = (probs, sizes)
                     self.stream.feed(probs, torch.tensor(sizes, dtype=torch.int))
                     self._text = self.best()
+        if final and self.endpoint is not None:
+            self.stream.end()                      # the last segment closes; the open one is empty from here on
+            self._text = [''] * N
         self._fed += chunk
         self._ended = final
         return list(self._text)
@@ -316,16 +331,23 @@ class StreamPool:
     one recurrent stack over the rows that retire an RNN frame, one lookahead, one head, one decoder feed -- and per stream the
     probabilities emitted over its feeds, concatenated, are the one-shot eval ``forward`` of that utterance alone."""
 
-    def __init__(self, model, decoder, capacity, max_frames=6000, front_end=None):
+    def __init__(self, model, decoder, capacity, max_frames=6000, front_end=None, endpoint=None):
         """model: a uni-directional DeepSpeech on a HIP device (run in eval mode, no autograd); decoder: a BeamCTCDecoder or
         GreedyDecoder over its labels; max_frames bounds the output frames per stream of a beam decoder; front_end: a causal
-        SpectrogramFrontEnd for feed_wave (None = one with the model's spect_cfg and normalize="running", made on first use)."""
+        SpectrogramFrontEnd for feed_wave (None = one with the model's spect_cfg and normalize="running", made on first use).
+        endpoint: a decoder.Endpointer cuts every slot's stream into utterances on the device: feeds
+        return the partial of the open segment, ``segments(slot)`` drains the finished ones, a final feed or ``end`` closes the
+        last one, max_frames bounds a segment and not the stream, and the acoustic state is not reset at an endpoint."""
         if model.bidirectional:
             raise ValueError("a StreamPool needs a uni-directional model: a reverse direction cannot be streamed exactly")
         if int(capacity) < 1:
             raise ValueError("capacity must be >= 1, got %s" % (capacity,))
         self.model, self.decoder, self.capacity, self.max_frames = model, decoder, int(capacity), int(max_frames)
+        self.endpoint = endpoint
+        if endpoint is not None and isinstance(decoder, BeamCTCDecoder):
+            endpoint.check_max_frames(self.max_frames)
         S = self.capacity
+        self._segs = [[] for _ in range(S)]                # endpoint: per slot the finished segments not yet handed out
         self.stream, self._state, self._h = None, None, None
         self._open = [False] * S
         self._fed, self._ended, self._text = [0] * S, [False] * S, [''] * S
@@ -348,7 +370,10 @@ class StreamPool:
             self._wave.reset([s])
         self.last_output.pop(s, None)
         if self.stream is not None:
+            if self.endpoint is not None:
+                self._pull_segments()
             self.stream.reset([s])
+        self._segs[s] = []
         if self._h is not None and not self._h_zero[s]:
             self._h[:, :, s].zero_()
         self._h_zero[s] = True
@@ -358,6 +383,20 @@ class StreamPool:
         """Frees the slot for the next ``open``."""
         self._check_slots([slot])
         self._open[int(slot)] = False
+
+    def _pull_segments(self):
+        for n, segs in enumerate(self.stream.segments()):
+            self._segs[n] += segs
+
+    def segments(self, slot):
+        """endpoint: the decoder.Segments of the slot's stream finished since the last call"""
+        s = self._check_slots([slot])[0]
+        if self.endpoint is None:
+            raise ValueError("segments() belongs to a pool with an endpoint")
+        if self.stream is not None:
+            self._pull_segments()
+        out, self._segs[s] = self._segs[s], []
+        return out
 
     def frames(self, slot):
         """output frames emitted so far for the slot's stream"""
@@ -464,13 +503,14 @@ class StreamPool:
         ctx, H, dev = int(m.lookahead[0].context), m._Hp, spect.device
         rp = plan_rows([self._fed[s] for s in sl], lens, [s in fin for s in sl], ctx)
         beam = isinstance(self.decoder, BeamCTCDecoder)
-        if beam:
+        if beam and self.endpoint is None:
             for i, s in enumerate(sl):
                 have = self.stream.frames[s] if self.stream is not None else 0
                 if have + rp.cnt3[i] > self.max_frames:
                     raise ValueError("slot %d: %d frames emitted + %d more pass max_frames=%d" % (s, have, rp.cnt3[i], self.max_frames))
         if self.stream is None:
-            self.stream = self.decoder.stream(S, self.max_frames, dev) if beam else self.decoder.stream(S, dev)
+            self.stream = self.decoder.stream(S, self.max_frames, dev, endpoint=self.endpoint) if beam else \
+                self.decoder.stream(S, dev, endpoint=self.endpoint)
         dtype = m._stream_begin()
         st = self._state
         if st is None or st["dtype"] != dtype:
@@ -522,6 +562,10 @@ class StreamPool:
             text = self.stream.best()[0] if beam else self.stream.text
             for s in sl:
                 self._text[s] = text[s]
+        if fin and self.endpoint is not None:
+            self.stream.end(sorted(fin))           # the last segment closes; the open one is empty from here on
+            for s in fin:
+                self._text[s] = ''
         return [self._text[s] for s in sl]
 
     def _advance(self, slots, bit):

@@ -620,6 +620,43 @@ int ds2_beam_stream_feed_lm_hot(const float* x, long stride_n, long stride_t, in
                                 int* offsets, long row_stride, int out_ranks, int* lens, float* scores, float* acoustic, void* ws,
                                 ds2_stream_t stream);
 
+/* ---- endpointing: endless streams cut into utterances on the device ------------------------------
+ * Frame t of a stream is silent iff x[t][blank] > blank_threshold (fp32, strict; a NaN is not silent).  A segment starts at frame
+ * s (0, or one past the previous endpoint) and ends at the first t where, in this order, 1 "silence": a non-silent frame in
+ * [s, t] and at least min_trailing silent frames ending at t; 2 "leading": no non-silent frame and at least max_leading silent
+ * ones; 3 "length": t - s + 1 == max_segment.  Reason 4 "final" is ds2_endpoint_close's.
+ * state: ds2_endpoint_state_bytes(N) bytes, 16-byte aligned: per stream eight int32 (segment start as an absolute frame,
+ *   trailing, spoken, frames consumed, segments finished, three reserved).  The counters are int32: 2^31 frames per stream.
+ * ds2_endpoint_reset: the streams with mask[n] != 0 (mask [N] int32 on the device, null = all) start again at frame 0, segment 0.
+ * ds2_endpoint_feed: x is the chunk (N, Tc, C) with ds2_beam_stream_feed's strides; sizes [N] int32 on the device (null = Tc).
+ *   Frames at and beyond sizes[n] are never read; sizes[n] == 0 leaves the state of stream n bitwise as it is.  The state
+ *   advances to the first endpoint and stops: cut[n] = the frames of the chunk that belong to the open segment (sizes[n] without
+ *   an endpoint), rest[n] = sizes[n] - cut[n]; events [4][N] int32 = rows (reason, start, end, index), all 0 without an endpoint,
+ *   so the first row is a mask for ds2_beam_stream_reset.  One wave per stream, 64 frames per step.
+ * ds2_endpoint_close: the open segment of the masked streams ends with reason 4 at the last frame consumed (end = start - 1 for
+ *   an empty one); events as above.
+ * ds2_endpoint_gather: y (N, Tc, C) contiguous, y[n][i] = x[n][cut[n] + i] for i < rest[n]: the frames after the endpoint at the
+ *   front of a second chunk, for a second feed with sizes = rest.  Nothing else of y is written, nothing beyond cut + rest read.
+ * ds2_endpoint_commit: for the streams with a non-zero reason, the event and the rows that a beam feed's output stage wrote
+ *   (its tokens / offsets / row_stride / out_ranks / lens / scores / acoustic arguments; acoustic null = scores) are copied to
+ *   slot pending[n] of the stream's ring and pending[n] grows by one; a stream whose `slots` slots are full is skipped.  ring:
+ *   ds2_endpoint_ring_bytes(N, slots, ranks, row_stride) bytes of [N][slots] slots, each 4 + 3 * ranks + 2 * ranks * row_stride
+ *   int32 words: event, lens, scores, acoustic, tokens, offsets.  pending [N] int32 on the device; the caller zeroes it when it
+ *   has fetched the ring.
+ * DS2_ERR_ARG: a null pointer other than sizes / mask / acoustic, N, C, slots, ranks or row_stride < 1, Tc < 1, a blank outside
+ *   [0, C), a threshold outside (0, 1), a count < 1.  DS2_ERR_ALIGN: a state that is not 16-byte aligned.  Size queries: 0. */
+long ds2_endpoint_state_bytes(int N);
+long ds2_endpoint_ring_bytes(int N, int slots, int ranks, long row_stride);
+int ds2_endpoint_reset(void* state, int N, const int* mask, ds2_stream_t stream);
+int ds2_endpoint_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank,
+                      float blank_threshold, int min_trailing, int max_leading, int max_segment, void* state, int* cut, int* rest,
+                      int* events, ds2_stream_t stream);
+int ds2_endpoint_close(void* state, int N, const int* mask, int* events, ds2_stream_t stream);
+int ds2_endpoint_gather(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* cut, const int* rest, float* y,
+                        ds2_stream_t stream);
+int ds2_endpoint_commit(const int* events, const int* tokens, const int* offsets, long row_stride, int ranks, const int* lens,
+                        const float* scores, const float* acoustic, int N, void* ring, int* pending, int slots, ds2_stream_t stream);
+
 /* ---- exact chunked inference: conv front-end and lookahead with carried time context -------------
  * For a uni-directional model in eval mode: fed chunk by chunk, the three kernels below give the frames of the one-shot forward.
  * Each reads, per stream n, a VIRTUAL WINDOW over time: position i < K comes from `carry` (the K positions in front of the

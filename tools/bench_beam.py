@@ -113,8 +113,52 @@ def stream_rows(a, probs, lm, oneshot, hot=None):
         row["first_ms"], row["first_min"], row["first_max"] = row["feed_ms"], row["feed_min"], row["feed_max"]
         row["last_ms"], row["last_min"], row["last_max"] = \
             timed(lambda: ops.beam_stream_feed(h, probs[:, T - Tc:]), a.runs, prep=resume)
+        if a.endpoint:
+            row.update(endpoint_fields(a, h, chunks[0]))
         rows.append(row)
     return rows
+
+
+def endpoint_fields(a, h, chunk):
+    """--endpoint: the feed of frames 0..chunk through the endpointers (decoder.Endpointer's default rule; the chunk goes in
+    sub-feeds of min_trailing frames as EndpointedBeamStream feeds it), and its launches timed apart for one sub-feed: the
+    endpoint kernel, the search with and without the output stage, and the second pass over the frames after a cut"""
+    mt, ml, ms = 50, 250, min(1000, h.max_frames)
+    eh = ops.endpoint_open(h.N, 0, 0.8, mt, ml, ms)
+    sink = ops.endpoint_sink_open(h, 1, ms, 8)
+    L = min(mt, ml, ms)
+    sub = chunk[:, :L]
+    zero = torch.zeros(h.N, dtype=torch.int32, device=chunk.device)
+
+    def fresh():
+        ops.beam_stream_reset(h)
+        ops.endpoint_reset(eh)
+        sink.pending.zero_()
+
+    def feed():
+        for i in range(0, chunk.shape[1], L):
+            ops.endpoint_beam_feed(eh, h, sink, chunk[:, i:i + L])
+
+    def second_pass():
+        y = ops.endpoint_gather(sub, zero, zero)
+        ops.endpoint_feed(eh, y, zero)
+        ops.beam_stream_feed(h, y, zero)
+
+    none = torch.zeros((4, h.N), dtype=torch.int32, device=chunk.device)       # an event block in which no stream ended
+
+    def commit_reset():
+        ops._endpoint_commit(none, sink)
+        ops.call("ds2_beam_stream_reset", ops.P(h.state), h.N, h.B, h.max_frames, h.flags, ops.P(none[0]), ops.S())
+
+    out = {}
+    for key, fn in (("ep_feed", feed), ("ep_detect", lambda: ops.endpoint_feed(eh, sub)), ("ep_search", lambda: ops.beam_stream_feed(h, sub)),
+                    ("ep_search_out", lambda: ops._beam_stream_launch(h, sub, L, None, sink.buf, sink.lens, sink.scores, ms, 1)),
+                    ("ep_commit_reset", commit_reset),
+                    ("ep_second_pass", second_pass)):
+        out[key + "_ms"], out[key + "_min"], out[key + "_max"] = timed(fn, a.runs, prep=fresh)
+    out["ep_sub_feeds"], out["ep_sub_frames"] = -(-chunk.shape[1] // L), L
+    out["ep_bytes_per_stream"] = (h.state.numel() + sink.ring.numel() * 4 + sink.buf.numel() * 4) // h.N
+    return out
 
 
 def grid_rows(a, probs, sizes, wt, gt, model, C):
@@ -199,6 +243,7 @@ def main():
     ap.add_argument("--hot", type=int, default=0, metavar="N", help="also time the hot-word entries on N synthetic phrases")
     ap.add_argument("--hot-oov-logp", type=float, default=-11.5)
     ap.add_argument("--stream", type=int, default=None, metavar="CHUNK_FRAMES", help="also time the resumable search in chunks")
+    ap.add_argument("--endpoint", action="store_true", help="with --stream: also time the feed with endpointing (DESIGN.md 3.6.5)")
     a = ap.parse_args()
     assert a.runs >= 10
     assert torch.cuda.is_available(), "bench_beam needs a HIP device"
@@ -282,6 +327,14 @@ def main():
                          "max %.3f), of the last chunk frames (T'-chunk..T') %.3f ms (min %.3f, max %.3f)" % (r["decoder"], r["B"], r["chunk"], r["oneshot_ms"], r["oneshot_min"], r["oneshot_max"], r["feeds"],
                                         r["chunked_ms"], r["chunked_min"], r["chunked_max"], r["feed_ms"], r["feed_result_ms"],
                                         r["first_ms"], r["first_min"], r["first_max"], r["last_ms"], r["last_min"], r["last_max"]))
+            if "ep_feed_ms" in r:
+                lines.append("%-13s B=%-4d chunk=%-4d endpointed feed of frames 0..chunk (%d sub-feeds of <= %d frames) %.3f ms (min %.3f, "
+                             "max %.3f) | one sub-feed's launches apart: endpoint kernel %.3f ms, search %.3f ms, search + output stage "
+                             "%.3f ms, commit + masked reset %.3f ms, second pass (gather, endpoint kernel, search; nothing after the "
+                             "cut) %.3f ms | %d bytes per stream" % (r["decoder"], r["B"], r["chunk"], r["ep_sub_feeds"], r["ep_sub_frames"],
+                                                                     r["ep_feed_ms"], r["ep_feed_min"], r["ep_feed_max"], r["ep_detect_ms"],
+                                                                     r["ep_search_ms"], r["ep_search_out_ms"], r["ep_commit_reset_ms"],
+                                                                     r["ep_second_pass_ms"], r["ep_bytes_per_stream"]))
             continue
         if r["decoder"] in ("grid", "loop"):
             lines.append("%-7s B=%-4d G=%-3d %10.3f ms/call (min %.3f, max %.3f)  kernels %10.3f ms  %8.3f ms/point" %

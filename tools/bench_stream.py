@@ -168,6 +168,8 @@ def run_pool(a):
     per = spc if a.wave else tc                           # what a feed brings per stream: samples or frames
     feed_of = lambda obj: obj.feed_wave if a.wave else obj.feed
     max_frames = nch * tc // 2 + 2
+    # --endpoint: decoder.Endpointer's default rule (a segment no longer than the pool that the other runs get)
+    ep = D.Endpointer(max_segment=min(1000, max_frames)) if a.endpoint else None
 
     def ticks_of(starts):
         """per tick the streams that are open, (stream, its chunk index), and whether the tick is timed"""
@@ -182,13 +184,14 @@ def run_pool(a):
         plan = ticks_of(starts)
         batches = [torch.cat([piece(k, j) for k, j in rows]).contiguous() for rows, _ in plan]      # the caller's batch, not timed
         if mode == "sessions":
-            sess = [streaming.StreamingTranscriber(m, mk_dec(), front_end=_front_end(a), max_frames=max_frames, carry_context=True)
-                    for _ in range(S)]
+            sess = [streaming.StreamingTranscriber(m, mk_dec(), front_end=_front_end(a), max_frames=max_frames, carry_context=True,
+                                                     endpoint=ep) for _ in range(S)]
             xs = [[piece(k, j).contiguous() for k, j in rows] for rows, _ in plan]
         elif mode == "session":
-            sess = streaming.StreamingTranscriber(m, mk_dec(), front_end=_front_end(a), max_frames=max_frames, carry_context=True)
+            sess = streaming.StreamingTranscriber(m, mk_dec(), front_end=_front_end(a), max_frames=max_frames, carry_context=True,
+                                                  endpoint=ep)
         else:
-            pool = streaming.StreamPool(m, mk_dec(), S, max_frames=max_frames, front_end=_front_end(a))
+            pool = streaming.StreamPool(m, mk_dec(), S, max_frames=max_frames, front_end=_front_end(a), endpoint=ep)
         lat, launches = [], None
         for r in range(a.reps + 1 + int(a.pool_launches)):
             if mode == "sessions":
@@ -228,7 +231,7 @@ def run_pool(a):
         print(json.dumps({"metric": "one tick of S exact streams (every open stream advances one chunk)", "mode": mode, "streams": S,
                           "model": "uni-LSTM-1024x5+lookahead", "decode": a.decode or "greedy", "input": "wave" if a.wave else "spectrogram",
                           "input_rate": (a.rate or 16000) if a.wave else None,
-                          "chunk_seconds": a.chunk,
+                          "chunk_seconds": a.chunk, "endpoint": repr(ep) if ep is not None else None,
                           "chunks_per_stream": nch, "ticks_timed": int(lat.size), "ms_per_tick_median": round(float(np.median(lat)) * 1e3, 3),
                           "ms_per_tick_p95": round(float(np.percentile(lat, 95)) * 1e3, 3), "device_kernels_per_tick": launches,
                           "dtype": "bf16"}), flush=True)
@@ -253,10 +256,13 @@ def main():
     ap.add_argument("--pool-modes", default="sessions,pool,session,pool_lockstep")
     ap.add_argument("--pool-launches", action="store_true", help="--pool: also count the device kernels of one tick")
     ap.add_argument("--wave", action="store_true", help="--carry / --pool: feed raw audio (feed_wave) to the exact modes")
+    ap.add_argument("--endpoint", action="store_true", help="--pool: the sessions and the pool cut their streams into utterances")
     ap.add_argument("--rate", type=int, default=None, help="--wave: the sample rate of the audio fed (the front-end's input_rate)")
     a = ap.parse_args()
     if a.wave and not (a.pool or a.carry):
         raise SystemExit("--wave goes with --carry or --pool")
+    if a.endpoint and not a.pool:
+        raise SystemExit("--endpoint goes with --pool")
     if a.rate and not a.wave:
         raise SystemExit("--rate goes with --wave")
     if a.pool:
