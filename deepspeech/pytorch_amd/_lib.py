@@ -147,6 +147,10 @@ SIGNATURES = {
     "ds2_ctc_loss_grad": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _l, _vp, _i, _vp]),
     "ds2_ctc_align_ws_bytes": (_l, [_i, _i, _i]),
     "ds2_ctc_align": (_i, [_vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_confidence_ws_bytes": (_l, [_i, _i]),
+    "ds2_confidence": (_i, [_vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _d, _i, _i,
+                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_frame_store_append": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _vp, _vp, _i, _vp]),
 }
 
 

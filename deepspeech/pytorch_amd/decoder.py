@@ -55,12 +55,36 @@ class GreedyDecoder:
         strings = [[''.join(' ' if v == self.space_index else self.int_to_char[v] for v in t)] for t in toks]
         return strings, [[o.to(torch.int)] for o in offs]
 
-    def stream(self, num_streams, device="cuda", endpoint=None):
+    def decode_words(self, probs, sizes=None, confidence=None, frame_seconds=None, kind="probs"):
+        """decode with word and character timings and confidences: [Hypothesis] per clip (confidence.py; score and acoustic are
+        None).  A character's span is the arg-max run it was collapsed from.  kind: what probs holds, as ForcedAligner.align's;
+        confidence: a Confidence (None = Confidence()); frame_seconds: the duration of a frame, for start_s / end_s."""
+        from . import align, confidence as _conf
+        conf = _conf.Confidence() if confidence is None else confidence
+        if not isinstance(conf, _conf.Confidence):
+            raise ValueError("confidence must be a Confidence, got %r" % (confidence,))
+        if kind not in align.KINDS:
+            raise ValueError("kind must be one of %s, got %r" % (sorted(align.KINDS), kind))
+        conf.check_classes(probs.shape[2])
+        if probs.shape[0] == 0 or probs.shape[1] == 0:
+            return [_conf.Hypothesis('', None, None, None, [], [], []) for _ in range(probs.shape[0])]
+        if not probs.is_cuda:
+            probs = probs.to("cuda")
+        words = dict(space=self.space_index, measure=conf.measure, alpha=conf.alpha, aggregate=conf.aggregate,
+                     word_aggregate=conf.word_aggregate, nbest=1, kind=kind)
+        labels, _, res = ops.greedy_decode(probs, sizes, self.blank_index, _words=words)
+        return [_conf.make_hypothesis(labels[n][0], self.int_to_char, self.space_index, res[n][0], None, None, frame_seconds)
+                for n in range(len(labels))]
+
+    def stream(self, num_streams, device="cuda", endpoint=None, confidence=None, max_frames=None):
         """A GreedyStream: decode for num_streams streams that arrive chunk by chunk.  endpoint: an Endpointer cuts every stream
-        into segments (EndpointedGreedyStream)."""
+        into segments (EndpointedGreedyStream).  confidence: a Confidence makes the stream keep its frames on the device, up to
+        max_frames per stream (required then; 4 * len(labels) bytes per frame and stream), and gives it ``words()``; with an
+        endpoint the frames live in a ring of ring_capacity(endpoint) frames instead, max_frames plays no part, the finished
+        segments carry ``.hypotheses`` and ``best_words()`` gives the open segment's partial."""
         if endpoint is not None:
-            return EndpointedGreedyStream(self, num_streams, device, endpoint)
-        return GreedyStream(self, num_streams, device)
+            return EndpointedGreedyStream(self, num_streams, device, endpoint, confidence)
+        return GreedyStream(self, num_streams, device, confidence, max_frames)
 
 
 class Endpointer:
@@ -97,6 +121,29 @@ Segment = collections.namedtuple("Segment", "index start end reason strings offs
                                  defaults=(None, None))
 
 
+class WordSegment(Segment):
+    """A Segment of a stream opened with confidence=: the same fields, equal to the plain tuple, and two attributes:
+    ``hypotheses``, the confidence.Hypothesis of every kept beam (word and character frames are absolute stream frames, like the
+    offsets), and ``confidence``, the top beam's (None without words)."""
+
+    def __new__(cls, segment, hypotheses):
+        self = super().__new__(cls, *segment)
+        self.hypotheses = hypotheses
+        self.confidence = hypotheses[0].confidence if hypotheses else None
+        return self
+
+
+RING_SLOTS = 8      # finished segments the device keeps per endpointed beam stream; a fetch happens at least every RING_SLOTS device feeds
+
+
+def ring_capacity(endpoint, slots=RING_SLOTS):
+    """Frames an endpointed stream keeps for the confidence pass.  At a fetch the frames still needed run from the start of the
+    oldest segment not yet fetched (or of the open one) to the newest frame.  A segment has at most max_segment frames; one that
+    is not yet fetched ended after the last fetch, and since then at most `slots` device feeds of at most sub_feed frames each
+    were consumed: max_segment + slots * sub_feed (tests/test_confidence_host.py simulates feed and fetch schedules against it)."""
+    return endpoint.max_segment + int(slots) * endpoint.sub_feed
+
+
 def split_feed(sizes, limit):
     """Cuts one feed into sub-feeds of at most `limit` frames per stream: [(t0, t1, sub_sizes)], sub-feed k holding the chunk's
     frames [t0, t1) = [k * limit, ...) and stream n taking its first sub_sizes[n] of them.  Sub-feeds that no stream takes part in
@@ -121,18 +168,65 @@ def _stream_sizes(sizes, N, Tc):
     return sz
 
 
+def _conf_settings(decoder, confidence, nbest=1, kind="probs"):
+    """(Confidence, the settings dict of ops' confidence pass) for a stream opened with confidence= (None: (None, None))"""
+    if confidence is None:
+        return None, None
+    from . import confidence as _conf
+    if not isinstance(confidence, _conf.Confidence):
+        raise ValueError("confidence must be a Confidence, got %r" % (confidence,))
+    confidence.check_classes(len(decoder.labels))
+    return confidence, dict(space=decoder.space_index, measure=confidence.measure, alpha=confidence.alpha,
+                            aggregate=confidence.aggregate, word_aggregate=confidence.word_aggregate, nbest=int(nbest), kind=kind)
+
+
+def _hypotheses(decoder, labels, res, scores=None, acoustic=None, frame_seconds=None, shifts=None):
+    """[[Hypothesis] per rank] per stream from ops._words_to_host's values; shifts[n]: added to stream n's frames"""
+    from . import confidence as _conf
+    with _conf.building_tuples():
+        return [[_conf.make_hypothesis(labels[n][r], decoder.int_to_char, decoder.space_index, res[n][r],
+                                       None if scores is None else float(scores[n, r]),
+                                       None if acoustic is None else float(acoustic[n, r]), frame_seconds,
+                                       0 if shifts is None else int(shifts[n]))
+                 for r in range(len(labels[n]))] for n in range(len(labels))]
+
+
 class GreedyStream:
     """GreedyDecoder.decode on streams that arrive in chunks (ds2_greedy_stream_feed): the previous frame's arg-max and the frame
     count of every stream stay on the device, so a repeated label or a run of blanks across a chunk boundary is collapsed as in the
     whole utterance.  ``text[n]`` is the transcript so far, ``offsets[n]`` its frames, ``frames[n]`` the frames consumed."""
 
-    def __init__(self, decoder, num_streams, device="cuda"):
+    def __init__(self, decoder, num_streams, device="cuda", confidence=None, max_frames=None):
         self.decoder, self.num_streams = decoder, int(num_streams)
         self._carry = torch.zeros((self.num_streams, 2), dtype=torch.int32, device=device)
+        self.confidence, self._wc = _conf_settings(decoder, confidence)
+        self._store, self._toks, self.max_frames = None, None, None
+        if confidence is not None:
+            if max_frames is None:
+                raise ValueError("a greedy stream with confidence= keeps its frames: it needs max_frames")
+            self.max_frames = int(max_frames)
+            self._store = ops.frame_store_open(self.num_streams, self.max_frames, len(decoder.labels), self._carry.device)
         self.reset()
+
+    def words(self, frame_seconds=None):
+        """Per stream the Hypothesis (confidence.py) of the whole stream so far: GreedyDecoder.decode_words on the frames consumed.
+        The transcript so far is uploaded in one copy."""
+        if self._store is None:
+            raise ValueError("words() needs a stream opened with confidence=")
+        hyps = [[(self._toks[n], self.offsets[n].tolist())] for n in range(self.num_streams)]
+        labels, _, res = ops.host_hypotheses_words(self._store.rows, self._store.count, hyps, self.decoder.blank_index, self._wc,
+                                                   self._wc["kind"])
+        return [h[0] for h in _hypotheses(self.decoder, labels, res, frame_seconds=frame_seconds)]
 
     def reset(self, streams=None):
         """Streams `streams` (None = all) start again."""
+        if self._store is not None:
+            ops.frame_store_reset(self._store, streams)
+            if streams is None:
+                self._toks = [[] for _ in range(self.num_streams)]
+            else:
+                for n in streams:
+                    self._toks[n] = []
         if streams is None:
             self._carry.zero_()
             self.text = [''] * self.num_streams
@@ -151,8 +245,20 @@ class GreedyStream:
         if not probs.is_cuda:
             probs = probs.to(self._carry.device)
         sz = _stream_sizes(sizes, self.num_streams, probs.shape[1])
+        if self._store is not None:
+            for n, v in enumerate(sz):
+                if self.frames[n] + v > self.max_frames:
+                    raise ValueError("stream %d: %d frames consumed + %d fed pass max_frames=%d"
+                                     % (n, self.frames[n], v, self.max_frames))
+            if probs.shape[1]:
+                x = probs if probs.dtype == torch.float32 else probs.float()
+                ops.frame_store_append(self._store, x if x.stride(2) == 1 else x.contiguous(),
+                                       None if sizes is None else ops._sizes_to_device(sz, x.device))
         toks, offs = ops.greedy_stream_feed(probs, None if sizes is None else torch.tensor(sz, dtype=torch.int32), d.blank_index,
                                             self._carry)
+        if self._store is not None:
+            for n in range(self.num_streams):
+                self._toks[n] = self._toks[n] + toks[n]
         strings = [''.join(' ' if v == d.space_index else d.int_to_char[v] for v in t) for t in toks]
         offs = [o.to(torch.int) for o in offs]
         for n in range(self.num_streams):
@@ -168,13 +274,48 @@ class EndpointedGreedyStream(GreedyStream):
     text and offsets are GreedyDecoder.decode's on its frames alone, the offsets counted from the start of the stream.
     ``frames[n]`` counts all the frames consumed.  The events ride on the fetch that every greedy feed makes anyway."""
 
-    def __init__(self, decoder, num_streams, device, endpoint):
+    def __init__(self, decoder, num_streams, device, endpoint, confidence=None):
         e = self.endpoint = endpoint
         self._ep = ops.endpoint_open(num_streams, decoder.blank_index, e.blank_threshold, e.min_trailing, e.max_leading,
                                      e.max_segment, device)
         self._start, self._labels = [0] * int(num_streams), [[] for _ in range(int(num_streams))]
         self._done = [[] for _ in range(int(num_streams))]
         super().__init__(decoder, num_streams, self._ep.device)
+        self.confidence, self._wc = _conf_settings(decoder, confidence)
+        self._fresh = []                   # (stream, position in _done) of the segments that still wait for their hypotheses
+        if confidence is not None:
+            self._toks = [[] for _ in range(self.num_streams)]
+            self._store = ops.frame_store_open(self.num_streams, ring_capacity(e), len(decoder.labels), self._ep.device)
+
+    def _attach(self):
+        """the hypotheses of the segments finished in the last device feed (at most one per stream): one upload, one pass"""
+        if self._store is None or not self._fresh:
+            self._fresh = []
+            return
+        N = self.num_streams
+        sizes, starts, hyps = [0] * N, [0] * N, [[([], [])] for _ in range(N)]
+        for n, i in self._fresh:
+            s = self._done[n][i]
+            sizes[n], starts[n] = s.end - s.start + 1, s.start
+            hyps[n] = [(s.labels[0], (s.offsets[0] - s.start).tolist())]
+        labels, _, res = ops.ring_segments_words(self._store, [(sizes, starts, hyps)], self.decoder.blank_index, self._wc)[0]
+        hy = _hypotheses(self.decoder, labels, res, shifts=starts)
+        for n, i in self._fresh:
+            self._done[n][i] = WordSegment(self._done[n][i], hy[n])
+        self._fresh = []
+
+    def words(self, frame_seconds=None):
+        """Per stream the Hypothesis of the OPEN segment's partial (frames absolute); finished segments carry theirs."""
+        if self._store is None:
+            raise ValueError("words() needs a stream opened with confidence=")
+        st = ops.endpoint_state(self._ep).tolist()
+        starts = [r[0] for r in st]
+        hyps = [[(self._labels[n], (self.offsets[n] - starts[n]).tolist())] for n in range(self.num_streams)]
+        labels, _, res = ops.ring_segments_words(self._store, [([r[3] - r[0] for r in st], starts, hyps)],
+                                                 self.decoder.blank_index, self._wc)[0]
+        return [h[0] for h in _hypotheses(self.decoder, labels, res, frame_seconds=frame_seconds, shifts=starts)]
+
+    best_words = words
 
     def reset(self, streams=None):
         """Streams `streams` (None = all) start again at frame 0 and segment 0; their undrained segments are dropped."""
@@ -185,6 +326,7 @@ class EndpointedGreedyStream(GreedyStream):
 
     def _finish(self, n, reason, start, end, index):
         self._done[n].append(Segment(index, start, end, reason, [self.text[n]], [self.offsets[n]], None, None, [self._labels[n]]))
+        self._fresh.append((n, len(self._done[n]) - 1))
         self._carry[n].zero_()
         self.text[n], self.offsets[n], self._labels[n], self._start[n] = '', torch.zeros(0, dtype=torch.int), [], end + 1
 
@@ -205,6 +347,8 @@ class EndpointedGreedyStream(GreedyStream):
             x = probs[:, t0:t1]
             while any(take):
                 cut, rest, ev = ops.endpoint_feed(self._ep, x, torch.tensor(take, dtype=torch.int32))
+                if self._store is not None:
+                    ops.frame_store_append(self._store, x, cut)
                 toks, offs = ops.greedy_stream_feed(x, cut, d.blank_index, self._carry)
                 take, reason, start, end, index = torch.cat([rest[None], ev]).cpu().tolist()
                 for n in range(self.num_streams):
@@ -217,6 +361,7 @@ class EndpointedGreedyStream(GreedyStream):
                     added_offs[n].append(o)
                     if reason[n]:
                         self._finish(n, ops.ENDPOINT_REASONS[reason[n]], start[n], end[n], index[n])
+                self._attach()
                 if any(take):
                     x = ops.endpoint_gather(x, cut, rest)         # the frames after the cut: the next segment's first
         self.frames = [f + v for f, v in zip(self.frames, sz)]
@@ -228,6 +373,7 @@ class EndpointedGreedyStream(GreedyStream):
         reason, start, end, index = ops.endpoint_close(self._ep, streams).cpu().tolist()
         for n in streams:
             self._finish(n, ops.ENDPOINT_REASONS[reason[n]], start[n], end[n], index[n])
+        self._attach()
 
     def segments(self):
         """Per stream the list of Segments finished since the last call."""
@@ -303,33 +449,63 @@ class BeamCTCDecoder:
             self._tables[device] = (torch.from_numpy(wt).to(device), torch.from_numpy(gt).to(device))
         return self._tables[device]
 
+    def _search(self, probs, sizes, words=None):
+        """The one-shot search in the form this decoder is set up for (plain, hot words, LM, LM with hot words); words: the
+        settings of ops' confidence pass for decode_words, None for the plain results."""
+        ht = self._hot_table(probs.device)
+        if self.lm is None and ht is not None:
+            return ops.beam_decode_hot(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
+                                       self.space_index, ht, _words=words)
+        if self.lm is None:
+            res = ops.beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
+                                  _words=words)
+            return res if words is not None else res + (res[2],)
+        wt, gt = self._lm_tables(probs.device)
+        if ht is not None:
+            return ops.beam_decode_lm_hot(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
+                                          self.space_index, wt, gt, self.lm.order, self.lm.bos, self.alpha, self.beta, self.lexicon,
+                                          ht, self.hot_oov_logp, _words=words)
+        return ops.beam_decode_lm(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
+                                  self.space_index, wt, gt, self.lm.order, self.lm.bos, self.alpha, self.beta, self.lexicon,
+                                  _words=words)
+
     def decode_beams_detailed(self, probs, sizes=None):
         """(strings, offsets, scores, acoustic): decode_beams' three values and the acoustic -log p of the same beams.  With an
         LM, scores = acoustic - lm (the total that ranked the beams); without one the two are equal."""
         if not probs.is_cuda:
             probs = probs.to("cuda")
-        ht = self._hot_table(probs.device)
-        if self.lm is None and ht is not None:
-            toks, offs, scores, acoustic = ops.beam_decode_hot(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
-                                                               self.cutoff_prob, self.space_index, ht)
-        elif self.lm is None:
-            toks, offs, scores = ops.beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
-                                                 self.cutoff_prob)
-            acoustic = scores
-        elif ht is not None:
-            wt, gt = self._lm_tables(probs.device)
-            toks, offs, scores, acoustic = ops.beam_decode_lm_hot(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
-                                                                  self.cutoff_prob, self.space_index, wt, gt, self.lm.order,
-                                                                  self.lm.bos, self.alpha, self.beta, self.lexicon, ht,
-                                                                  self.hot_oov_logp)
-        else:
-            wt, gt = self._lm_tables(probs.device)
-            toks, offs, scores, acoustic = ops.beam_decode_lm(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n,
-                                                              self.cutoff_prob, self.space_index, wt, gt, self.lm.order,
-                                                              self.lm.bos, self.alpha, self.beta, self.lexicon)
+        toks, offs, scores, acoustic = self._search(probs, sizes)
         strings = [[''.join(self.int_to_char[v] for v in t) for t in beams] for beams in toks]
         offsets = [[o.to(torch.int) for o in beams] for beams in offs]
         return strings, offsets, scores, acoustic
+
+    def decode_words(self, probs, sizes=None, confidence=None, nbest=1, frame_seconds=None):
+        """The best `nbest` beams of every clip with word and character timings and confidences: [[Hypothesis] * nbest] per clip
+        (confidence.py).  text, score and acoustic are decode_beams_detailed's of the same rank; the spans and confidences come
+        from one device pass over the search's own buffers (ds2_confidence), so only the top nbest ranks travel to the host.
+        confidence: a Confidence (None = Confidence()); frame_seconds: the duration of a frame, for start_s / end_s."""
+        from . import confidence as _conf
+        conf = _conf.Confidence() if confidence is None else confidence
+        if not isinstance(conf, _conf.Confidence):
+            raise ValueError("confidence must be a Confidence, got %r" % (confidence,))
+        if not 1 <= int(nbest) <= self.beam_width:
+            raise ValueError("nbest must be in [1, beam_width=%d], got %r" % (self.beam_width, nbest))
+        conf.check_classes(probs.shape[2])
+        if not probs.is_cuda:
+            probs = probs.to("cuda")
+        if probs.shape[0] == 0 or probs.shape[1] == 0:       # no frames: the empty string alone
+            _, _, scores, acoustic = self.decode_beams_detailed(probs, sizes)
+            return [[_conf.Hypothesis('', float(scores[n, r]), float(acoustic[n, r]), None, [], [], [])
+                     for r in range(int(nbest))] for n in range(probs.shape[0])]
+        if probs.dtype != torch.float32:
+            probs = probs.float()
+        words = dict(space=self.space_index, measure=conf.measure, alpha=conf.alpha, aggregate=conf.aggregate,
+                     word_aggregate=conf.word_aggregate, nbest=int(nbest))
+        labels, _, res, scores, acoustic = self._search(probs, sizes, words)
+        with _conf.building_tuples():
+            return [[_conf.make_hypothesis(labels[n][r], self.int_to_char, self.space_index, res[n][r], float(scores[n, r]),
+                                           float(acoustic[n, r]), frame_seconds)
+                     for r in range(len(labels[n]))] for n in range(len(labels))]
 
     def decode_grid_device(self, probs, sizes, points, max_ws_bytes=1 << 30):
         """The top beam at every (alpha, beta) of `points`, left on the device: ops.beam_decode_lm_grid's five tensors
@@ -367,14 +543,18 @@ class BeamCTCDecoder:
         strings, offsets, _ = self.decode_beams(probs, sizes)
         return strings, offsets
 
-    def stream(self, num_streams, max_frames, device="cuda", endpoint=None, nbest=1):
+    def stream(self, num_streams, max_frames, device="cuda", endpoint=None, nbest=1, confidence=None):
         """A BeamStream: this decoder's search for num_streams streams that arrive chunk by chunk, up to max_frames frames each
         (the node pool costs 12 * beam_width bytes per frame and stream).  endpoint: an Endpointer cuts every stream into segments
         of at most endpoint.max_segment <= max_frames frames (EndpointedBeamStream), so the stream itself has no bound; every
-        finished segment keeps its best `nbest` beams."""
+        finished segment keeps its best `nbest` beams.  confidence: a Confidence makes the stream keep its frames on the device
+        ((num_streams, max_frames, len(labels)) fp32: 4 * len(labels) bytes per frame and stream) and gives it ``words()`` and
+        ``best_words()``; without it no store exists and no kernel is added to a feed.  With an endpoint the store is a ring of
+        ring_capacity(endpoint) frames per stream, every finished segment comes back with ``.hypotheses`` (its kept beams'
+        words, frames absolute) and ``.confidence``, and ``words()`` / ``best_words()`` give the open segment's partial."""
         if endpoint is not None:
-            return EndpointedBeamStream(self, num_streams, max_frames, device, endpoint, nbest)
-        return BeamStream(self, num_streams, max_frames, device)
+            return EndpointedBeamStream(self, num_streams, max_frames, device, endpoint, nbest, confidence)
+        return BeamStream(self, num_streams, max_frames, device, confidence)
 
 
 class BeamStream:
@@ -383,9 +563,10 @@ class BeamStream:
     sizes reach the device through pinned memory in a queued copy; a host ``probs`` is copied first, which does wait).
     ``frames[n]`` counts the frames that stream n has consumed."""
 
-    def __init__(self, decoder, num_streams, max_frames, device="cuda"):
+    def __init__(self, decoder, num_streams, max_frames, device="cuda", confidence=None):
         d = self.decoder = decoder
         self.num_streams, self.max_frames = int(num_streams), int(max_frames)
+        self.confidence, self._wc = _conf_settings(decoder, confidence)
         dev = torch.empty(0, device=device).device
         lm = None
         if d.lm is not None:
@@ -398,6 +579,9 @@ class BeamStream:
         self._h = ops.beam_stream_open(self.num_streams, self.max_frames, len(d.labels), d.blank_index, d.beam_width,
                                        d.cutoff_top_n, d.cutoff_prob, dev, lm, hot)
         self.frames = [0] * self.num_streams
+        self._store = None
+        if confidence is not None:
+            self._store = ops.frame_store_open(self.num_streams, self.max_frames, len(d.labels), self._h.device)
 
     def feed(self, probs, sizes=None):
         """probs: (N, Tc, C) probabilities of the next chunk (device or host tensor); sizes: host ints per stream (None = Tc), 0
@@ -409,8 +593,29 @@ class BeamStream:
                                  % (n, self.frames[n], v, self.max_frames))
         if not probs.is_cuda:
             probs = probs.to(self._h.device)
-        ops.beam_stream_feed(self._h, probs, None if sizes is None else torch.tensor(sz, dtype=torch.int32))
+        if self._store is not None and probs.shape[1]:
+            x = probs if probs.dtype == torch.float32 else probs.float()
+            szd = None if sizes is None else ops._sizes_to_device(sz, self._h.device)
+            ops.frame_store_append(self._store, x if x.stride(2) == 1 else x.contiguous(), szd)
+            ops.beam_stream_feed(self._h, x, szd)
+        else:
+            ops.beam_stream_feed(self._h, probs, None if sizes is None else torch.tensor(sz, dtype=torch.int32))
         self.frames = [f + v for f, v in zip(self.frames, sz)]
+
+    def words(self, nbest=1, frame_seconds=None):
+        """[[Hypothesis] * nbest] per stream (confidence.py): BeamCTCDecoder.decode_words on the frames consumed so far, bit for
+        bit.  Needs a stream opened with confidence=; feeding can go on afterwards."""
+        if self._store is None:
+            raise ValueError("words() needs a stream opened with confidence=")
+        if not 1 <= int(nbest) <= self.decoder.beam_width:
+            raise ValueError("nbest must be in [1, beam_width=%d], got %r" % (self.decoder.beam_width, nbest))
+        labels, _, res, scores, acoustic = ops.beam_stream_words(self._h, self._store, max(self.frames),
+                                                                 dict(self._wc, nbest=int(nbest)))
+        return _hypotheses(self.decoder, labels, res, scores, acoustic, frame_seconds)
+
+    def best_words(self, frame_seconds=None):
+        """The top beam's Hypothesis of every stream; only rank 0 travels to the host."""
+        return [h[0] for h in self.words(1, frame_seconds)]
 
     def _strings(self, res):
         d = self.decoder
@@ -430,6 +635,8 @@ class BeamStream:
         """Streams `streams` (None = all) start again from the empty beam."""
         streams = list(range(self.num_streams)) if streams is None else [int(n) for n in streams]
         ops.beam_stream_reset(self._h, streams)
+        if self._store is not None:
+            ops.frame_store_reset(self._store, streams)
         for n in streams:
             self.frames[n] = 0
 
@@ -444,11 +651,15 @@ class EndpointedBeamStream(BeamStream):
     many device feeds without a fetch, the feed fetches (the one host wait that feeding can take; a chunk longer than
     endpoint.sub_feed frames is several device feeds).  Offsets are absolute stream frames; ``frames[n]`` counts all frames."""
 
-    RING_SLOTS = 8
+    RING_SLOTS = RING_SLOTS
 
-    def __init__(self, decoder, num_streams, max_frames, device, endpoint, nbest=1):
+    def __init__(self, decoder, num_streams, max_frames, device, endpoint, nbest=1, confidence=None):
         endpoint.check_max_frames(max_frames)
         super().__init__(decoder, num_streams, max_frames, device)
+        self.confidence, self._wc = _conf_settings(decoder, confidence)
+        if confidence is not None:
+            self._store = ops.frame_store_open(self.num_streams, ring_capacity(endpoint, self.RING_SLOTS), len(decoder.labels),
+                                               self._h.device)
         e = self.endpoint = endpoint
         self.nbest = int(nbest)
         self._ep = ops.endpoint_open(self.num_streams, decoder.blank_index, e.blank_threshold, e.min_trailing, e.max_leading,
@@ -464,8 +675,15 @@ class EndpointedBeamStream(BeamStream):
             probs = probs.to(self._h.device)
         if probs.dtype != torch.float32:
             probs = probs.float()
+        if self._store is not None and probs.stride(2) != 1:
+            probs = probs.contiguous()
         for t0, t1, sub in split_feed(sz, self.endpoint.sub_feed):
-            ops.endpoint_beam_feed(self._ep, self._h, self._sink, probs[:, t0:t1], torch.tensor(sub, dtype=torch.int32))
+            if self._store is not None:
+                szd = ops._sizes_to_device(sub, self._h.device)
+                ops.frame_store_append(self._store, probs[:, t0:t1], szd)
+                ops.endpoint_beam_feed(self._ep, self._h, self._sink, probs[:, t0:t1], szd)
+            else:
+                ops.endpoint_beam_feed(self._ep, self._h, self._sink, probs[:, t0:t1], torch.tensor(sub, dtype=torch.int32))
             self._fed_once()
         self.frames = [f + v for f, v in zip(self.frames, sz)]
 
@@ -476,13 +694,53 @@ class EndpointedBeamStream(BeamStream):
 
     def _fetch(self):
         d = self.decoder
-        for n, segs in enumerate(ops.endpoint_sink_fetch(self._sink)):
-            for s in segs:
-                self._done[n].append(Segment(s["index"], s["start"], s["end"], s["reason"],
-                                             [''.join(d.int_to_char[v] for v in t) for t in s["labels"]],
-                                             [o.to(torch.int) + s["start"] for o in s["offsets"]], s["scores"], s["acoustic"],
-                                             s["labels"]))
+        fetched = ops.endpoint_sink_fetch(self._sink)
+        hyp = self._segment_hypotheses(fetched) if self._store is not None else None
+        for n, segs in enumerate(fetched):
+            for k, s in enumerate(segs):
+                seg = Segment(s["index"], s["start"], s["end"], s["reason"],
+                              [''.join(d.int_to_char[v] for v in t) for t in s["labels"]],
+                              [o.to(torch.int) + s["start"] for o in s["offsets"]], s["scores"], s["acoustic"], s["labels"])
+                self._done[n].append(seg if hyp is None else WordSegment(seg, hyp[n][k]))
         self._since = 0
+
+    def _segment_hypotheses(self, fetched):
+        """[n][k]: the Hypothesis list of stream n's k-th fetched segment.  All of them go up in one copy; the k-th segments of
+        all streams share one pass over the ring."""
+        N, R = self.num_streams, self.nbest
+        out = [[None] * len(segs) for segs in fetched]
+        groups = []
+        for k in range(max(len(segs) for segs in fetched)):
+            sizes, starts, hyps = [0] * N, [0] * N, [[([], [])] * R for _ in range(N)]
+            for n, segs in enumerate(fetched):
+                if k < len(segs):
+                    s = segs[k]
+                    sizes[n], starts[n] = s["end"] - s["start"] + 1, s["start"]
+                    hyps[n] = [(t, o.tolist()) for t, o in zip(s["labels"], s["offsets"])]
+            groups.append((sizes, starts, hyps))
+        if not groups:
+            return out
+        for k, (labels, _, res) in enumerate(ops.ring_segments_words(self._store, groups, self.decoder.blank_index, self._wc)):
+            sc = [None if k >= len(segs) else (segs[k]["scores"], segs[k]["acoustic"]) for segs in fetched]
+            hy = _hypotheses(self.decoder, labels, res, shifts=groups[k][1])
+            for n, segs in enumerate(fetched):
+                if k < len(segs):
+                    out[n][k] = [h._replace(score=float(sc[n][0][r]), acoustic=float(sc[n][1][r])) for r, h in enumerate(hy[n])]
+        return out
+
+    def words(self, nbest=1, frame_seconds=None):
+        """[[Hypothesis] * nbest] per stream for the OPEN segment's beams (frames absolute): BeamCTCDecoder.decode_words on the
+        open segment's frames.  Finished segments carry theirs (``Segment.hypotheses``)."""
+        if self._store is None:
+            raise ValueError("words() needs a stream opened with confidence=")
+        if not 1 <= int(nbest) <= self.decoder.beam_width:
+            raise ValueError("nbest must be in [1, beam_width=%d], got %r" % (self.decoder.beam_width, nbest))
+        st = self._ep.state
+        labels, _, res, scores, acoustic = ops.beam_stream_words(
+            self._h, self._store, min(max(self.frames), self.endpoint.max_segment), dict(self._wc, nbest=int(nbest)),
+            st[:, 3] - st[:, 0], st[:, 0] % self._store.cap)
+        starts = ops.endpoint_state(self._ep)[:, 0].tolist()
+        return _hypotheses(self.decoder, labels, res, scores, acoustic, frame_seconds, starts)
 
     def _open_beams(self, top_only):
         res = ops.beam_stream_result(self._h, min(max(self.frames), self.endpoint.max_segment), top_only=top_only)

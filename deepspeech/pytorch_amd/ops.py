@@ -894,7 +894,7 @@ def softmax_rows(logits, Cc):
     return out
 
 
-def greedy_decode(scores, sizes, blank):
+def greedy_decode(scores, sizes, blank, _words=None):
     """scores: (N, T', C) f32 CUDA tensor (any strides with a contiguous class dimension); sizes: [N] int tensor.
     Returns host lists (tokens per sample, frame offsets per sample) -- reference decoder.py:164-181."""
     if scores.dtype != torch.float32:
@@ -908,6 +908,8 @@ def greedy_decode(scores, sizes, blank):
     counts = torch.empty(N, dtype=torch.int32, device=dev)
     call("ds2_greedy_decode", P(scores), scores.stride(0), scores.stride(1), N, T, Cc, P(sz), blank, P(buf[0]), P(buf[1]), P(counts),
          S())
+    if _words is not None:       # decode_words: the confidence pass reads the device buffers before anything travels
+        return _words_to_host(scores, sz, buf[0][:, None], buf[1][:, None], counts[:, None], blank, _words, _words["kind"])
     cnt = counts.cpu()
     width = int(cnt.max().item()) if N > 0 else 0
     host = buf[:, :, :max(width, 1)].cpu()           # only the surviving labels + offsets travel
@@ -919,7 +921,7 @@ def greedy_decode(scores, sizes, blank):
 BEAM_MAX_WIDTH, BEAM_MAX_TOP_N, BEAM_MAX_CLASSES = 256, 64, 8192     # ds2_beam_decode's limits
 
 
-def beam_decode(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob):
+def beam_decode(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, _words=None):
     """CTC prefix beam search without a language model (ds2_beam_decode).  probs: (N, T', C) CUDA tensor of probabilities (any
     strides with a contiguous class dimension); sizes: [N] int tensor or None (= T').  Returns host lists: tokens[n][b] (labels
     of beam b, best first), offsets[n][b] (int tensor of their frames) and a host (N, B) float tensor of scores (-log p, ctcdecode's
@@ -943,6 +945,9 @@ def beam_decode(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob):
     ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
     call("ds2_beam_decode", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob),
          P(buf[0]), P(buf[1]), P(lens), P(scores), P(ws), S())
+    if _words is not None:
+        sc = scores.cpu()
+        return _words_to_host(probs, sz, buf[0], buf[1], lens, blank, _words) + (sc, sc)
     ln = lens.cpu().numpy()
     width = max(int(ln.max()), 1)
     host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
@@ -955,7 +960,7 @@ BEAM_LM_MAX_ORDER = 5
 
 
 def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, word_table, ngram_table, order, bos,
-                   alpha, beta, lexicon=True):
+                   alpha, beta, lexicon=True, _words=None):
     """CTC prefix beam search with a word n-gram language model (ds2_beam_decode_lm).  Arguments as beam_decode, plus the space
     label, the two tables of lm.build_tables as int64 CUDA tensors of shape (slots, 2) on the device of probs, the LM's order,
     the id of <s>, alpha, beta and the lexicon flag.  Returns beam_decode's three values, scores being -(log p + lm), and a host
@@ -980,6 +985,9 @@ def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, s
     call("ds2_beam_decode_lm", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob),
          int(space), P(word_table), word_table.shape[0], P(ngram_table), ngram_table.shape[0], int(order), int(bos), float(alpha),
          float(beta), int(bool(lexicon)), P(buf[0]), P(buf[1]), P(lens), P(scores[0]), P(scores[1]), P(ws), S())
+    if _words is not None:
+        sc = scores.cpu()
+        return _words_to_host(probs, sz, buf[0], buf[1], lens, blank, _words) + (sc[0], sc[1])
     ln = lens.cpu().numpy()
     width = max(int(ln.max()), 1)
     host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
@@ -1028,7 +1036,7 @@ def _beam_no_frames(N, B):
         [[torch.zeros(0, dtype=torch.int32) for _ in range(B)] for _ in range(N)], scores, scores.clone()
 
 
-def beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, hot_table):
+def beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, hot_table, _words=None):
     """beam_decode with hot words (ds2_beam_decode_hot).  space: the space label; hot_table: the table of hotwords.build_table
     as an int64 CUDA tensor of shape (slots, 2) on the device of probs.  Returns beam_decode's three values, scores being
     -(log p + hot_end), the total that ranked the beams, and a host (N, B) float tensor of the acoustic -log p of the same beams."""
@@ -1047,11 +1055,14 @@ def beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, 
     ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
     call("ds2_beam_decode_hot", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob),
          int(space), P(hot_table), hot_table.shape[0], P(buf[0]), P(buf[1]), P(lens), P(scores[0]), P(scores[1]), P(ws), S())
+    if _words is not None:
+        sc = scores.cpu()
+        return _words_to_host(probs, sz, buf[0], buf[1], lens, blank, _words) + (sc[0], sc[1])
     return _beam_to_host(buf, lens, scores, N, B)
 
 
 def beam_decode_lm_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, word_table, ngram_table, order, bos,
-                       alpha, beta, lexicon, hot_table, hot_oov_logp):
+                       alpha, beta, lexicon, hot_table, hot_oov_logp, _words=None):
     """beam_decode_lm with hot words (ds2_beam_decode_lm_hot): its arguments, the table of hotwords.build_table and the ln P that a
     covered out-of-vocabulary word event is charged.  Returns beam_decode_lm's four values, scores being -((log p + lm) + hot_end)."""
     B, top_n = _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos)
@@ -1071,6 +1082,9 @@ def beam_decode_lm_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_pro
          float(cutoff_prob), int(space), P(word_table), word_table.shape[0], P(ngram_table), ngram_table.shape[0], int(order), int(bos),
          float(alpha), float(beta), int(bool(lexicon)), P(hot_table), hot_table.shape[0], float(hot_oov_logp), P(buf[0]), P(buf[1]),
          P(lens), P(scores[0]), P(scores[1]), P(ws), S())
+    if _words is not None:
+        sc = scores.cpu()
+        return _words_to_host(probs, sz, buf[0], buf[1], lens, blank, _words) + (sc[0], sc[1])
     return _beam_to_host(buf, lens, scores, N, B)
 
 
@@ -1739,6 +1753,217 @@ def ctc_align(x, sizes, targets, target_lengths, blank=0, mode="probs", max_targ
     call("ds2_ctc_align", P(x), x.stride(0), x.stride(1), N, Tp, Cc, m, P(sz), P(tg), P(offs), P(tl), max_target_len, int(blank),
          P(frame_state), P(tok[0]), P(tok[1]), P(tok_logp), P(score), P(ws), S())
     return frame_state, tok[0, :total], tok[1, :total], tok_logp[:total], score
+
+
+# ---- word timings and confidence (csrc/ds2_confidence.hip) --------------------------------------------------------------------
+CONFIDENCE_MAX_CLASSES, CONFIDENCE_MAX_BEAMS = 8192, 256     # ds2_confidence's limits (the decoders')
+CONFIDENCE_MEASURES = {"label_prob": 0, "max_prob": 1, "entropy": 2, "tsallis": 3, "renyi": 4}
+CONFIDENCE_AGGREGATES = {"mean": 0, "min": 1, "prod": 2}
+
+
+def confidence(x, sizes, tokens, offsets, lens, blank, space, measure="label_prob", alpha=1 / 3, aggregate="mean",
+               word_aggregate="min", kind="probs", t0=None, cap=None):
+    """Spans, word tables and confidences of hypotheses that live on the device (ds2_confidence; the rules are in
+    include/ds2hip.h).  x: (N, T', C) float32 CUDA tensor as the decoders take it, `kind` as ctc_align's mode; sizes: [N] or None.
+    tokens, offsets: (N, B, ld) int32 CUDA tensors, lens (N, B): the hypotheses as a decoder's device buffers hold them.  space:
+    the space label (>= C: none).  t0 / cap: frame t of row n is row (t0[n] + t) % cap of x, a stream's ring; then T' = cap
+    frames at most are addressed and sizes is required.  Returns ten device tensors: tok_start, tok_end, tok_conf (N, B, ld);
+    word_first, word_last, word_start, word_end, word_conf (N, B, (ld + 1) // 2); word_count, utt_conf (N, B).  No host
+    synchronisation."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32):
+        raise ValueError("confidence takes a float32 HIP device tensor of shape (N, T', C)")
+    N, Tp, Cc = x.shape
+    if Cc > CONFIDENCE_MAX_CLASSES:
+        raise ValueError("at most %d classes, got %d" % (CONFIDENCE_MAX_CLASSES, Cc))
+    if N < 1 or Tp < 1 or Cc < 1:
+        raise ValueError("confidence needs at least one clip, one frame and one class; got shape %s" % (tuple(x.shape),))
+    k = CTC_ALIGN_MODES.get(kind, kind)
+    if k not in (0, 1, 2):
+        raise ValueError("kind must be one of %s, got %r" % (sorted(CTC_ALIGN_MODES), kind))
+    m = CONFIDENCE_MEASURES.get(measure, measure)
+    ag, wag = CONFIDENCE_AGGREGATES.get(aggregate, aggregate), CONFIDENCE_AGGREGATES.get(word_aggregate, word_aggregate)
+    if m not in range(5) or ag not in range(3) or wag not in range(3):
+        raise ValueError("measure must be one of %s and the aggregates of %s, got %r, %r, %r"
+                         % (sorted(CONFIDENCE_MEASURES), sorted(CONFIDENCE_AGGREGATES), measure, aggregate, word_aggregate))
+    alpha = float(alpha)
+    if not alpha > 0:
+        raise ValueError("alpha must be > 0, got %r" % (alpha,))
+    if m >= 3 and alpha == 1:
+        raise ValueError("alpha == 1 is not an order of the tsallis or renyi entropy")
+    if m >= 2 and Cc < 2:
+        raise ValueError("at least 2 classes for an entropy measure, got %d" % Cc)
+    if not 0 <= int(blank) < Cc:
+        raise ValueError("blank index %d out of range for %d classes" % (blank, Cc))
+    if int(space) < 0:
+        raise ValueError("space label %d must be >= 0 (the number of classes or more: no space label)" % space)
+    for name, t in (("tokens", tokens), ("offsets", offsets)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and t.dim() == 3 and t.shape[0] == N):
+            raise ValueError("%s must be an int32 HIP device tensor of shape (N, B, ld)" % name)
+    B, ld = tokens.shape[1], tokens.shape[2]
+    if B > CONFIDENCE_MAX_BEAMS:
+        raise ValueError("at most %d hypotheses per clip, got %d" % (CONFIDENCE_MAX_BEAMS, B))
+    if B < 1 or ld < 1 or offsets.shape != tokens.shape or tuple(lens.shape) != (N, B):
+        raise ValueError("tokens %s, offsets %s and lens %s do not describe (N, B, ld >= 1) hypotheses"
+                         % (tuple(tokens.shape), tuple(offsets.shape), tuple(lens.shape)))
+    if (t0 is None) != (cap is None) or (t0 is not None and sizes is None):
+        raise ValueError("a ring is addressed with t0, cap and sizes together")
+    if x.stride(2) != 1:
+        x = x.contiguous()
+    dev = x.device
+    if t0 is not None:
+        if int(cap) != Tp:
+            raise ValueError("cap=%d must be the rows of the store, %d" % (cap, Tp))
+        t0 = t0.to(dev, torch.int32).contiguous()
+    sz = sizes.to(dev, torch.int32).contiguous() if sizes is not None else None
+    tokens, offsets, lens = tokens.contiguous(), offsets.contiguous(), lens.to(dev, torch.int32).contiguous()
+    lw = (ld + 1) // 2
+    tok_i = torch.empty((2, N, B, ld), dtype=torch.int32, device=dev)
+    tok_c = torch.empty((N, B, ld), dtype=torch.float32, device=dev)
+    word_i = torch.empty((4, N, B, lw), dtype=torch.int32, device=dev)
+    word_c = torch.empty((N, B, lw), dtype=torch.float32, device=dev)
+    count = torch.empty((N, B), dtype=torch.int32, device=dev)
+    utt = torch.empty((N, B), dtype=torch.float32, device=dev)
+    ws = torch.empty(query("ds2_confidence_ws_bytes", N, Tp), dtype=torch.uint8, device=dev)
+    call("ds2_confidence", P(x), x.stride(0), x.stride(1), N, Tp, Cc, k, P(sz), P(t0), Tp, P(tokens), P(offsets), P(lens), B, ld, lw,
+         int(blank), int(space), m, alpha, ag, wag, P(tok_i[0]), P(tok_i[1]), P(tok_c), P(word_i[0]), P(word_i[1]), P(word_i[2]),
+         P(word_i[3]), P(word_c), P(count), P(utt), P(ws), S())
+    return tok_i[0], tok_i[1], tok_c, word_i[0], word_i[1], word_i[2], word_i[3], word_c, count, utt
+
+
+def _words_to_host(x, sz, tokens, offsets, lens, blank, wc, kind="probs", t0=None, cap=None):
+    """The confidence pass on a decode's own device buffers, then the one trip to the host: tokens, offsets (N, B, ld) and lens
+    (N, B) on the device; wc = dict(space, measure, alpha, aggregate, word_aggregate, nbest).  Only the top nbest ranks are passed
+    and come back.  Returns (labels[n][r], offsets[n][r] as lists, res[n][r] = the hypothesis' rows of confidence's ten outputs as
+    host lists / numbers, cut to its length and word count)."""
+    N, B = lens.shape
+    R = max(1, min(int(wc["nbest"]), B))
+    tk, of, ln = tokens[:, :R], offsets[:, :R], lens[:, :R]
+    out = confidence(x, sz, tk, of, ln, blank, wc["space"], wc["measure"], wc["alpha"], wc["aggregate"], wc["word_aggregate"], kind,
+                     t0, cap)
+    lnh, cnt = ln.cpu().numpy(), out[8].cpu().numpy()
+    width, wwidth = max(int(lnh.max()), 1), max(int(cnt.max()), 1)
+    ih = torch.stack([tk[:, :, :width], of[:, :, :width], out[0][:, :, :width], out[1][:, :, :width]]).cpu().numpy()
+    tch = out[2][:, :, :width].cpu().numpy()
+    wih = torch.stack([o[:, :, :wwidth] for o in out[3:7]]).cpu().numpy()
+    wch, utt = out[7][:, :, :wwidth].cpu().numpy(), out[9].cpu().numpy()
+    labels, offs, res = [], [], []
+    for n in range(N):
+        labels.append([ih[0, n, r, :max(lnh[n, r], 0)].tolist() for r in range(R)])
+        offs.append([ih[1, n, r, :max(lnh[n, r], 0)].tolist() for r in range(R)])
+        res.append([(ih[2, n, r, :max(lnh[n, r], 0)].tolist(), ih[3, n, r, :max(lnh[n, r], 0)].tolist(),
+                     tch[n, r, :max(lnh[n, r], 0)].tolist(), wih[0, n, r, :cnt[n, r]].tolist(), wih[1, n, r, :cnt[n, r]].tolist(),
+                     wih[2, n, r, :cnt[n, r]].tolist(), wih[3, n, r, :cnt[n, r]].tolist(), wch[n, r, :cnt[n, r]].tolist(),
+                     int(cnt[n, r]), float(utt[n, r])) for r in range(R)])
+    return labels, offs, res
+
+
+class FrameStore:
+    """The frames a stream keeps for the confidence pass: rows (N, cap, C) float32 and the frames stored so far, count [N] int32,
+    both on the device.  Made by frame_store_open."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def frame_store_open(num_streams, cap, num_classes, device="cuda"):
+    """A store of cap frames of num_classes classes for each of num_streams streams (4 * num_classes bytes per frame and stream);
+    frame f of a stream lives at row f % cap."""
+    N, cap, Cc = int(num_streams), int(cap), int(num_classes)
+    if N < 1 or cap < 1 or not 1 <= Cc <= CONFIDENCE_MAX_CLASSES:
+        raise ValueError("a frame store needs num_streams >= 1, cap >= 1 and 1 to %d classes, got %d, %d and %d"
+                         % (CONFIDENCE_MAX_CLASSES, N, cap, Cc))
+    return FrameStore(rows=torch.zeros((N, cap, Cc), dtype=torch.float32, device=device),
+                      count=torch.zeros(N, dtype=torch.int32, device=device), N=N, cap=cap, C=Cc)
+
+
+def frame_store_append(store, x, sizes=None):
+    """Appends the first sizes[n] (device int32 tensor; None = all) frames of chunk x (N, Tc, C) to every stream's rows
+    (ds2_frame_store_append).  No host synchronisation.  A chunk longer than cap goes in pieces."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32 and x.shape[0] == store.N
+            and x.shape[2] == store.C and x.stride(2) == 1):
+        raise ValueError("a chunk for this store is a float32 HIP device tensor of shape (%d, Tc, %d)" % (store.N, store.C))
+    for t0 in range(0, x.shape[1], store.cap):
+        part = x[:, t0:t0 + store.cap]
+        sz = None if sizes is None else (sizes - t0).clamp_(0, part.shape[1])
+        call("ds2_frame_store_append", P(part), part.stride(0), part.stride(1), store.N, part.shape[1], store.C, P(sz), P(store.count),
+             P(store.rows), store.cap, S())
+
+
+def frame_store_reset(store, streams=None):
+    """Streams `streams` (None = all) start again at frame 0."""
+    if streams is None:
+        store.count.zero_()
+    else:
+        store.count[torch.tensor([int(n) for n in streams], dtype=torch.long, device=store.count.device)] = 0
+
+
+def beam_stream_words(h, store, row_stride, wc, sizes=None, t0=None):
+    """_words_to_host on the beams of every stream of h for the frames consumed so far, read from `store`; returns its three
+    values and the host scores and acoustic (N, nbest).  The state is left unchanged.  sizes, t0 (device int32 [N]): the frames
+    are an endpointed stream's open segment, sizes[n] frames from row t0[n] of the ring; default: the store from its row 0."""
+    N, B = h.N, h.B
+    R = 1 if int(wc["nbest"]) == 1 else B
+    row_stride = max(int(row_stride), 1)
+    buf = torch.empty((2, N, R, row_stride), dtype=torch.int32, device=h.device)
+    lens = torch.empty((N, R), dtype=torch.int32, device=h.device)
+    scores = torch.empty((2, N, R), dtype=torch.float32, device=h.device)
+    _beam_stream_launch(h, None, 0, None, buf, lens, scores, row_stride, R)
+    sc = scores.cpu()
+    plain = h.lm is None and h.hot is None
+    if t0 is None:
+        res = _words_to_host(store.rows, store.count, buf[0], buf[1], lens, h.blank, wc)
+    else:
+        res = _words_to_host(store.rows, sizes, buf[0], buf[1], lens, h.blank, wc, "probs", t0, store.cap)
+    return res + (sc[0], sc[0] if plain else sc[1])
+
+
+def ring_segments_words(store, groups, blank, wc, kind="probs"):
+    """The confidence pass for segments of streams whose frames live in the ring `store`, their hypotheses on the host.  groups:
+    a list of (sizes, starts, hyps): for every stream n one segment of sizes[n] frames (0: none) that began at absolute frame
+    starts[n], with hyps[n] = [(labels, offsets from the segment's start)] * B; several groups when a stream has several
+    segments.  Everything is uploaded in ONE copy (a pinned int32 buffer), then one ds2_confidence call per group.  Returns
+    _words_to_host's value per group."""
+    N, G = store.N, len(groups)
+    B = len(groups[0][2][0])
+    ld = max(1, max(len(t) for _, _, hyps in groups for hs in hyps for t, _ in hs))
+    per = 2 * N + N * B * (2 * ld + 1)
+    pack = torch.zeros(G * per, dtype=torch.int32).pin_memory()
+    for g, (sizes, starts, hyps) in enumerate(groups):
+        p = pack[g * per:(g + 1) * per]
+        p[:N] = torch.as_tensor(sizes, dtype=torch.int32)
+        p[N:2 * N] = torch.as_tensor([int(s) % store.cap for s in starts], dtype=torch.int32)
+        tk, of = p[2 * N:2 * N + N * B * ld].view(N, B, ld), p[2 * N + N * B * ld:2 * N + 2 * N * B * ld].view(N, B, ld)
+        ln = p[2 * N + 2 * N * B * ld:].view(N, B)
+        for n, hs in enumerate(hyps):
+            for b, (t, o) in enumerate(hs):
+                tk[n, b, :len(t)] = torch.as_tensor(t, dtype=torch.int32)
+                of[n, b, :len(t)] = torch.as_tensor(o, dtype=torch.int32)
+                ln[n, b] = len(t)
+    dev = pack.to(store.rows.device, non_blocking=True)
+    out = []
+    for g in range(G):
+        p = dev[g * per:(g + 1) * per]
+        tk, of = p[2 * N:2 * N + N * B * ld].view(N, B, ld), p[2 * N + N * B * ld:2 * N + 2 * N * B * ld].view(N, B, ld)
+        out.append(_words_to_host(store.rows, p[:N], tk, of, p[2 * N + 2 * N * B * ld:].view(N, B), blank, dict(wc, nbest=B), kind,
+                                  p[N:2 * N], store.cap))
+    return out
+
+
+def host_hypotheses_words(x, sizes, hyps, blank, wc, kind="probs", t0=None, cap=None):
+    """_words_to_host for hypotheses that live on the host: hyps[n] = [(labels, offsets)] * B as lists.  They are uploaded in ONE
+    copy (tokens, offsets and lengths packed in one pinned int32 buffer)."""
+    N, B = len(hyps), len(hyps[0])
+    ld = max(1, max(len(t) for hs in hyps for t, _ in hs))
+    pack = torch.zeros(N * B * (2 * ld + 1), dtype=torch.int32).pin_memory()
+    tk, of, ln = pack[:N * B * ld].view(N, B, ld), pack[N * B * ld:2 * N * B * ld].view(N, B, ld), pack[2 * N * B * ld:].view(N, B)
+    for n, hs in enumerate(hyps):
+        for b, (t, o) in enumerate(hs):
+            tk[n, b, :len(t)] = torch.as_tensor(t, dtype=torch.int32)
+            of[n, b, :len(t)] = torch.as_tensor(o, dtype=torch.int32)
+            ln[n, b] = len(t)
+    dev = pack.to(x.device, non_blocking=True)
+    tk, of, ln = dev[:N * B * ld].view(N, B, ld), dev[N * B * ld:2 * N * B * ld].view(N, B, ld), dev[2 * N * B * ld:].view(N, B)
+    return _words_to_host(x, sizes, tk, of, ln, blank, dict(wc, nbest=B), kind, t0, cap)
 
 
 # ---- waveform augmentation (csrc/ds2_waveaug.hip) ---------------------------------------------------------------------------

@@ -61,16 +61,19 @@ def plan_feed(frames, chunk, ctx, final=False):
 
 
 class StreamingTranscriber:
-    def __init__(self, model, decoder, front_end=None, max_frames=6000, carry_context=False, endpoint=None):
+    def __init__(self, model, decoder, front_end=None, max_frames=6000, carry_context=False, endpoint=None, confidence=None):
         """model: a DeepSpeech on a HIP device; decoder: a BeamCTCDecoder or GreedyDecoder over the model's labels; front_end: a
         SpectrogramFrontEnd for feed_wave (None = one with the model's spect_cfg, made on first use).  max_frames bounds the output
         frames per stream of a beam decoder (its node pool is allocated at the first feed).  carry_context: exact chunked
         inference (module docstring); uni-directional models only -- a reverse direction cannot be streamed exactly.
         endpoint: a decoder.Endpointer cuts every stream into utterances on the device: feeds return
         the partial of the open segment, ``segments()`` drains the finished ones, max_frames bounds a segment and not the stream,
-        and only the decoder starts again at an endpoint -- the acoustic state runs on."""
+        and only the decoder starts again at an endpoint -- the acoustic state runs on.
+        confidence: a confidence.Confidence makes the decoder stream keep max_frames frames of probabilities per stream on the
+        device and gives the session ``words()`` / ``best_words()``; with an endpoint the frames live in a ring, ``segments()``
+        returns decoder.WordSegments that carry ``.hypotheses``, and ``words()`` is the open segment's partial."""
         self.model, self.decoder, self.front_end, self.max_frames = model, decoder, front_end, int(max_frames)
-        self.endpoint = endpoint
+        self.endpoint, self.confidence = endpoint, confidence
         if endpoint is not None and isinstance(decoder, BeamCTCDecoder):
             endpoint.check_max_frames(self.max_frames)
         self.hs, self.stream = None, None
@@ -84,9 +87,25 @@ class StreamingTranscriber:
 
     def _open(self, N, device):
         if isinstance(self.decoder, BeamCTCDecoder):
-            self.stream = self.decoder.stream(N, self.max_frames, device, endpoint=self.endpoint)
+            self.stream = self.decoder.stream(N, self.max_frames, device, endpoint=self.endpoint, confidence=self.confidence)
         else:
-            self.stream = self.decoder.stream(N, device, endpoint=self.endpoint)
+            self.stream = self.decoder.stream(N, device, endpoint=self.endpoint, confidence=self.confidence,
+                                              max_frames=self.max_frames if self.confidence is not None else None)
+
+    def words(self, nbest=1, frame_seconds=None):
+        """Per stream the confidence.Hypothesis list of everything fed so far, as ``decoder.decode_words`` gives it on the
+        concatenation of the chunks' outputs: [[Hypothesis] * nbest] with a beam decoder, [[Hypothesis]] with a greedy one."""
+        if self.confidence is None:
+            raise ValueError("words() belongs to a session opened with confidence=")
+        if self.stream is None:
+            return []
+        if isinstance(self.decoder, BeamCTCDecoder):
+            return self.stream.words(nbest, frame_seconds)
+        return [[h] for h in self.stream.words(frame_seconds)]
+
+    def best_words(self, frame_seconds=None):
+        """The top Hypothesis of every stream."""
+        return [h[0] for h in self.words(1, frame_seconds)]
 
     def segments(self):
         """endpoint: per stream the list of decoder.Segments finished since the last call"""
@@ -331,19 +350,22 @@ class StreamPool:
     one recurrent stack over the rows that retire an RNN frame, one lookahead, one head, one decoder feed -- and per stream the
     probabilities emitted over its feeds, concatenated, are the one-shot eval ``forward`` of that utterance alone."""
 
-    def __init__(self, model, decoder, capacity, max_frames=6000, front_end=None, endpoint=None):
+    def __init__(self, model, decoder, capacity, max_frames=6000, front_end=None, endpoint=None, confidence=None):
         """model: a uni-directional DeepSpeech on a HIP device (run in eval mode, no autograd); decoder: a BeamCTCDecoder or
         GreedyDecoder over its labels; max_frames bounds the output frames per stream of a beam decoder; front_end: a causal
         SpectrogramFrontEnd for feed_wave (None = one with the model's spect_cfg and normalize="running", made on first use).
         endpoint: a decoder.Endpointer cuts every slot's stream into utterances on the device: feeds
         return the partial of the open segment, ``segments(slot)`` drains the finished ones, a final feed or ``end`` closes the
-        last one, max_frames bounds a segment and not the stream, and the acoustic state is not reset at an endpoint."""
+        last one, max_frames bounds a segment and not the stream, and the acoustic state is not reset at an endpoint.
+        confidence: a confidence.Confidence makes the decoder stream keep max_frames frames of probabilities per slot on the
+        device and gives the pool ``words(slot)``; with an endpoint the frames live in a ring, ``segments(slot)`` returns
+        decoder.WordSegments that carry ``.hypotheses``, and ``words(slot)`` is the open segment's partial."""
         if model.bidirectional:
             raise ValueError("a StreamPool needs a uni-directional model: a reverse direction cannot be streamed exactly")
         if int(capacity) < 1:
             raise ValueError("capacity must be >= 1, got %s" % (capacity,))
         self.model, self.decoder, self.capacity, self.max_frames = model, decoder, int(capacity), int(max_frames)
-        self.endpoint = endpoint
+        self.endpoint, self.confidence = endpoint, confidence
         if endpoint is not None and isinstance(decoder, BeamCTCDecoder):
             endpoint.check_max_frames(self.max_frames)
         S = self.capacity
@@ -427,6 +449,24 @@ class StreamPool:
             return strings[s], offsets[s]
         return [self.stream.text[s]], [self.stream.offsets[s]]
 
+    def words(self, slot, nbest=1, frame_seconds=None):
+        """[Hypothesis] * nbest (confidence.py) of the slot's stream for everything emitted so far, as ``decoder.decode_words``
+        gives it on the probabilities the slot's stream produced (one Hypothesis with a greedy decoder)."""
+        s = self._check_slots([slot])[0]
+        if self.confidence is None:
+            raise ValueError("words() belongs to a pool opened with confidence=")
+        if self.stream is None:                            # nothing fed yet: decode_words on no frames
+            from .confidence import Hypothesis
+            if not isinstance(self.decoder, BeamCTCDecoder):
+                return [Hypothesis('', None, None, None, [], [], [])]
+            if not 1 <= int(nbest) <= self.decoder.beam_width:
+                raise ValueError("nbest must be in [1, beam_width=%d], got %r" % (self.decoder.beam_width, nbest))
+            return [Hypothesis('', 0.0 if r == 0 else float("inf"), 0.0 if r == 0 else float("inf"), None, [], [], [])
+                    for r in range(int(nbest))]
+        if isinstance(self.decoder, BeamCTCDecoder):
+            return self.stream.words(nbest, frame_seconds)[s]
+        return [self.stream.words(frame_seconds)[s]]
+
     def end(self, slots):
         """The end of these streams' utterances as a final feed of nothing: every frame still held back is emitted (for a slot
         fed with ``feed_wave``: the front-end's last frame first)."""
@@ -509,8 +549,9 @@ class StreamPool:
                 if have + rp.cnt3[i] > self.max_frames:
                     raise ValueError("slot %d: %d frames emitted + %d more pass max_frames=%d" % (s, have, rp.cnt3[i], self.max_frames))
         if self.stream is None:
-            self.stream = self.decoder.stream(S, self.max_frames, dev, endpoint=self.endpoint) if beam else \
-                self.decoder.stream(S, dev, endpoint=self.endpoint)
+            self.stream = self.decoder.stream(S, self.max_frames, dev, endpoint=self.endpoint, confidence=self.confidence) if beam else \
+                self.decoder.stream(S, dev, endpoint=self.endpoint, confidence=self.confidence,
+                                    max_frames=self.max_frames if self.confidence is not None else None)
         dtype = m._stream_begin()
         st = self._state
         if st is None or st["dtype"] != dtype:

@@ -778,6 +778,48 @@ int ds2_ctc_align(const float* x, long stride_n, long stride_t, int N, int Tp, i
                   const int* target_offsets, const int* target_lengths, int max_target_len, int blank, int* frame_state,
                   int* tok_start, int* tok_end, float* tok_logp, float* score, void* ws, ds2_stream_t stream);
 
+/* ---- word timings and confidence of hypotheses a CTC decoder returned ---------------------------------
+ * x, stride_n, stride_t, sizes as for ds2_ctc_align; kind 0: logits, 1: probabilities, 2: log-probabilities.  Frame t of row n is
+ * read at row (t0[n] + t) mod cap of x (t0 [N] int32 on the device, null = 0; cap >= Tp; a one-shot call passes null and Tp).
+ * Hypothesis (n, b), b < B: lens[n*B + b] labels tokens[(n*B + b)*ld + i] at frames offsets[...], as the decoders return them.
+ * A hypothesis with a length outside [0, ld], a label outside [0, C) or a frame outside [0, sizes[n]) is used as no index and
+ * comes back INVALID: every confidence NaN, every span and word entry -1, 0 words.
+ * Frame pass, for every valid frame: p_t(c), an fp32 number: the value as given (probabilities, not renormalised),
+ * exp(x - lz) (logits) or exp(x) (log-probabilities), evaluated in fp64 and rounded once; lz = m + log(sum exp(x - m)), m the
+ * frame's maximum, in fp64 rounded once to fp32.  a_t: the first maximal class by the greedy decoder's scan (class 0 wins when it
+ * is NaN, a NaN elsewhere never wins).  m_t, the frame value of `measure`, V = C:
+ *   0 label_prob  none: a token uses p_t(l) of its own label l        1 max_prob  p_t(a_t)
+ *   2 entropy     1 - H / ln V, H = -sum p ln p (a zero term is 0)
+ *   3 tsallis     1 - H / Hmax, H = (1 - sum p^alpha) / (alpha - 1), Hmax = (1 - V^(1 - alpha)) / (alpha - 1)
+ *   4 renyi       1 - H / ln V, H = ln(sum p^alpha) / (1 - alpha)
+ * 2 to 4 in fp64, clamped to [0, 1], rounded once.  SUMMATION ORDER of every sum over the classes (lz's too): 64 partial sums, the
+ * j-th over the classes j, j + 64, ... in increasing order, then v[j] += v[j ^ o] for o = 32, 16, 8, 4, 2, 1.
+ * Token i (label l, frame o): forward end e_i: from o, t = o + 1, ... while t < sizes[n], a_t == l and t < offsets[i + 1] (if
+ * there is a next token); start s_i: t = o - 1, ... while t >= 0, a_t == l and t > e_(i-1) (if there is a previous token).  The
+ * span [s_i, e_i] always holds o.  tok_conf = aggregate (0 mean, 1 min, 2 prod) of m_t, or p_t(l), over the span in increasing
+ * frame order: fp64 sum / count or product, rounded once; min is exact.  The space label is a token like any other.
+ * Words: maximal runs of tokens other than `space` (space = any value >= C: one word).  word_first / word_last: token indices;
+ * word_start = s_first, word_end = e_last; word_conf = word_aggregate over the tokens' fp32 confidences in order; utt_conf =
+ * word_aggregate over the word confidences, NaN without words.
+ * Outputs (device; EVERY element is written on every call; entries past a length or a count are -1 / NaN):
+ *   tok_start, tok_end int32 and tok_conf f32 [N][B][ld]; word_first, word_last, word_start, word_end int32 and word_conf f32
+ *   [N][B][lw], 2 lw >= ld; word_count int32 and utt_conf f32 [N][B].
+ * ws: ds2_confidence_ws_bytes(N, Tp) bytes, 4-byte aligned (a_t, m_t, lz: 12 bytes per frame); -1 for N or Tp < 1.
+ * No atomics; the same bits on every launch.  DS2_ERR_ARG: N outside [1, 65535], Tp, ld < 1, N * Tp > 2^31 - 1, C outside [1, 8192] (entropy
+ * measures: [2, 8192]), B outside [1, 256], 2 lw < ld, cap < Tp, blank outside [0, C), space < 0, kind, measure or an aggregate
+ * out of range, alpha <= 0 or == 1 for measures 3 and 4, a null pointer other than sizes and t0. */
+long ds2_confidence_ws_bytes(int N, int Tp);
+int ds2_confidence(const float* x, long stride_n, long stride_t, int N, int Tp, int C, int kind, const int* sizes, const int* t0,
+                   int cap, const int* tokens, const int* offsets, const int* lens, int B, int ld, int lw, int blank, int space,
+                   int measure, double alpha, int aggregate, int word_aggregate, int* tok_start, int* tok_end, float* tok_conf,
+                   int* word_first, int* word_last, int* word_start, int* word_end, float* word_conf, int* word_count,
+                   float* utt_conf, void* ws, ds2_stream_t stream);
+/* A stream keeps its frames for ds2_confidence: row j < sizes[n] of chunk x [N][Tc][C] goes to row (count[n] + j) mod cap of
+ * store [N][cap][C] f32, then count[n] += sizes[n]; sizes (null = Tc) and count [N] int32 are read on the device, so a feed waits
+ * for nothing.  DS2_ERR_ARG: N outside [1, 65535], Tc < 1, C outside [1, 8192], cap < Tc, a null pointer other than sizes. */
+int ds2_frame_store_append(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int* count,
+                           float* store, int cap, ds2_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

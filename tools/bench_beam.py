@@ -28,6 +28,13 @@ chunked feeds is shorter where CHUNK_FRAMES does not divide T'; it is not the "l
 With --hot the same widths are also timed through ops.beam_decode_hot (and, with --lm, ops.beam_decode_lm_hot; with --stream the
 hot streams too) on N synthetic phrases: half of them words cut from the input's own greedy transcripts, so that matches start,
 run on and complete, the other half random letter strings of one or two words.
+
+    python tools/bench_beam.py --words [--widths 1,10,128]
+
+With --words the word timings and confidences are timed per width: decoder.decode_words at nbest = 1 and nbest = B against
+decode_beams on the same input, the confidence pass alone on hypotheses that are already on the device (ops.confidence: both
+kernels, and the same call on hypotheses of length 0, which leaves the frame kernel), and a BeamStream's best_words() against
+its best() after the whole input was fed.
 """
 import argparse
 import json
@@ -227,6 +234,51 @@ def grid_rows(a, probs, sizes, wt, gt, model, C):
     return rows
 
 
+def words_rows(a, probs, sizes):
+    """decode_words against decode_beams, the confidence pass alone, and the streamed best_words() against best(), per width"""
+    from deepspeech.pytorch_amd.configs import LABELS
+    from deepspeech.pytorch_amd.confidence import Confidence
+    from deepspeech.pytorch_amd.decoder import BeamCTCDecoder, GreedyDecoder
+    N, T, C = probs.shape
+    conf, rows = Confidence(), []
+    g = GreedyDecoder(LABELS)
+    row = dict(decoder="words", B=0)
+    row["beams_ms"], _, _ = timed(lambda: g.decode(probs, sizes), a.runs)
+    row["words1_ms"], _, _ = timed(lambda: g.decode_words(probs, sizes, conf), a.runs)
+    rows.append(row)
+    for B in [int(w) for w in a.widths.split(",")]:
+        d = BeamCTCDecoder(LABELS, beam_width=B, cutoff_top_n=a.top_n)
+        row = dict(decoder="words", B=B)
+        row["beams_ms"], _, _ = timed(lambda: d.decode_beams(probs, sizes), a.runs)
+        row["words1_ms"], _, _ = timed(lambda: d.decode_words(probs, sizes, conf, nbest=1), a.runs)
+        row["wordsB_ms"], _, _ = timed(lambda: d.decode_words(probs, sizes, conf, nbest=B), a.runs)
+        toks, offs, _ = ops.beam_decode(probs, sizes, 0, B, a.top_n, 1.0)
+        tk = torch.zeros((N, B, T), dtype=torch.int32)
+        of, ln = torch.zeros_like(tk), torch.zeros((N, B), dtype=torch.int32)
+        for n in range(N):
+            for b in range(B):
+                L = len(toks[n][b])
+                tk[n, b, :L], of[n, b, :L], ln[n, b] = torch.tensor(toks[n][b], dtype=torch.int32), offs[n][b], L
+        tk, of, ln = tk.cuda(), of.cuda(), ln.cuda()
+        for name, measure in (("pass", "label_prob"), ("pass_entropy", "entropy")):
+            row[name + "_ms"], _, _ = timed(lambda: ops.confidence(probs, sizes, tk, of, ln, 0, C - 1, measure), a.runs)
+            row[name + "_frames_ms"], _, _ = timed(lambda: ops.confidence(probs, sizes, tk, of, torch.zeros_like(ln), 0, C - 1, measure),
+                                                   a.runs)
+        row["pass1_ms"], _, _ = timed(lambda: ops.confidence(probs, sizes, tk[:, :1], of[:, :1], ln[:, :1], 0, C - 1), a.runs)
+        row["mean_len"] = float(ln.float().mean())
+        for name, c in (("stream", None), ("stream_conf", conf)):
+            st = d.stream(N, T, "cuda", confidence=c)
+            st.feed(probs, sizes.tolist())
+            row[name + "_best_ms"], _, _ = timed(st.best, a.runs)
+            if c is not None:
+                row["stream_best_words_ms"], _, _ = timed(st.best_words, a.runs)
+                row["stream_feed_conf_ms"], _, _ = timed(lambda: st.feed(probs, sizes.tolist()), a.runs, prep=st.reset)
+            else:
+                row["stream_feed_ms"], _, _ = timed(lambda: st.feed(probs, sizes.tolist()), a.runs, prep=st.reset)
+        rows.append(row)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=20)
@@ -244,6 +296,7 @@ def main():
     ap.add_argument("--hot-oov-logp", type=float, default=-11.5)
     ap.add_argument("--stream", type=int, default=None, metavar="CHUNK_FRAMES", help="also time the resumable search in chunks")
     ap.add_argument("--endpoint", action="store_true", help="with --stream: also time the feed with endpointing (DESIGN.md 3.6.5)")
+    ap.add_argument("--words", action="store_true", help="also time decode_words and the confidence pass (DESIGN.md 3.8)")
     a = ap.parse_args()
     assert a.runs >= 10
     assert torch.cuda.is_available(), "bench_beam needs a HIP device"
@@ -318,6 +371,8 @@ def main():
                                     lambda B: ops.beam_decode_lm_hot(probs, sizes, 0, B, a.top_n, 1.0, C - 1, wt, gt, model.order,
                                                                      model.bos, a.alpha, a.beta, not a.open, ht, a.hot_oov_logp),
                                     hot_args)
+    if a.words:
+        rows += words_rows(a, probs, sizes)
     lines = notes + ["# tools/bench_beam.py: N=%d T'=%d C=%d cutoff_top_n=%d softmax(normal * %.1f), median of %d calls after warm-up, %s"
              % (N, T, C, a.top_n, a.scale, a.runs, torch.cuda.get_device_name(0))]
     for r in rows:
@@ -335,6 +390,18 @@ def main():
                                                                      r["ep_feed_ms"], r["ep_feed_min"], r["ep_feed_max"], r["ep_detect_ms"],
                                                                      r["ep_search_ms"], r["ep_search_out_ms"], r["ep_commit_reset_ms"],
                                                                      r["ep_second_pass_ms"], r["ep_bytes_per_stream"]))
+            continue
+        if r["decoder"] == "words" and r["B"] == 0:
+            lines.append("words greedy   decode %8.3f ms | decode_words %8.3f ms" % (r["beams_ms"], r["words1_ms"]))
+            continue
+        if r["decoder"] == "words":
+            lines.append("words B=%-4d    decode_beams %8.3f ms | decode_words nbest=1 %8.3f ms, nbest=B %8.3f ms | the pass alone on B "
+                         "hypotheses of %.0f labels on average: label_prob %.3f ms (frame kernel alone %.3f), entropy %.3f ms (frame "
+                         "kernel alone %.3f); on rank 0 alone %.3f ms | stream: best() %.3f ms, best_words() %.3f ms; feed of all frames "
+                         "%.3f ms, with the frame store %.3f ms"
+                         % (r["B"], r["beams_ms"], r["words1_ms"], r["wordsB_ms"], r["mean_len"], r["pass_ms"], r["pass_frames_ms"],
+                            r["pass_entropy_ms"], r["pass_entropy_frames_ms"], r["pass1_ms"], r["stream_best_ms"],
+                            r["stream_best_words_ms"], r["stream_feed_ms"], r["stream_feed_conf_ms"]))
             continue
         if r["decoder"] in ("grid", "loop"):
             lines.append("%-7s B=%-4d G=%-3d %10.3f ms/call (min %.3f, max %.3f)  kernels %10.3f ms  %8.3f ms/point" %
