@@ -524,10 +524,25 @@ int ds2_opt_multi(int mode, int count, float* const* p, const float* const* g, f
   return 0;
 }
 
-static bool opt_matrix_vec_ok(int mode, const float* p, const float* g, const float* m, const float* v, int C, int perm_c, int Cout,
-                              const void* dst, long ldd) {
-  return perm_c == 0 && Cout == C && C % 4 == 0 && (dst == nullptr || ldd % 4 == 0) &&
-         (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)(mode == 0 ? v : p) | (uintptr_t)dst) & 15) == 0;
+// The kernel ds2_opt_matrix takes for these arguments -- the ONE place that decides it (ds2_opt_matrix launches by this value,
+// ds2_opt_matrices gathers the matrices of route 0 into k_opt_matrix4_multi and hands the others to ds2_opt_matrix): 0 k_opt_matrix4,
+// 1 k_opt_matrix_perm_rows, 2 k_opt_matrix_perm, 3 k_opt_matrix; arguments ds2_opt_matrix rejects: minus its error code.  Host only: the
+// pointers are looked at for null and alignment and never dereferenced.
+enum { OPT_ROUTE_MATRIX4 = 0, OPT_ROUTE_PERM_ROWS = 1, OPT_ROUTE_PERM = 2, OPT_ROUTE_GENERIC = 3 };
+int ds2_opt_matrix_route(int mode, const void* p, const void* g, const void* m, const void* v, int R, int C, int perm_c, int perm_f,
+                         int Cout, const void* dst, long ldd, const void* dstT, long lddT) {
+  if (!((mode == 0 || mode == 1) && p && g && m && (mode == 1 || v))) return -DS2_ERR_ARG;
+  if (!(R > 0 && C > 0 && R % 16 == 0 && Cout >= C)) return -DS2_ERR_ARG;
+  if (!(perm_c == 0 || perm_c * perm_f == C)) return -DS2_ERR_ARG;
+  if (!(dstT == nullptr || (lddT % 8 == 0 && (((uintptr_t)dstT) & 15) == 0))) return -DS2_ERR_ALIGN;
+  const bool fp32_aligned = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)(mode == 0 ? v : p)) & 15) == 0;   // SGD never reads v
+  if (perm_c == 0 && Cout == C && C % 4 == 0 && fp32_aligned && (dst == nullptr || (ldd % 4 == 0 && (((uintptr_t)dst) & 15) == 0)))
+    return OPT_ROUTE_MATRIX4;
+  const int cw = perm_rows_cw(C, perm_c, perm_f);
+  if (cw > 0 && PR_ROWS * cw * perm_f * 2 <= PR_MAX_LDS && fp32_aligned && (dst == nullptr || (ldd % 8 == 0 && (((uintptr_t)dst) & 15) == 0)))
+    return OPT_ROUTE_PERM_ROWS;
+  if (perm_c > 0 && C % 4 == 0 && fp32_aligned) return OPT_ROUTE_PERM;
+  return OPT_ROUTE_GENERIC;
 }
 
 // `count` weight matrices of ONE parameter group (same hp / first): ds2_opt_matrix for each of them, with every matrix the
@@ -552,11 +567,9 @@ int ds2_opt_matrices(int mode, int count, float* const* p, const float* const* g
   };
   for (int i = 0; i < count; ++i) {
     float* vi = mode == 0 ? v[i] : nullptr;
-    DS2_REQUIRE(p[i] && g[i] && m[i] && (mode == 1 || vi), DS2_ERR_ARG);
-    DS2_REQUIRE(R[i] > 0 && C[i] > 0 && R[i] % 16 == 0 && Cout[i] >= C[i], DS2_ERR_ARG);
-    DS2_REQUIRE(perm_c[i] == 0 || perm_c[i] * perm_f[i] == C[i], DS2_ERR_ARG);
-    DS2_REQUIRE(dstT[i] == nullptr || (lddT[i] % 8 == 0 && (((uintptr_t)dstT[i]) & 15) == 0), DS2_ERR_ALIGN);
-    if (!opt_matrix_vec_ok(mode, p[i], g[i], m[i], vi, C[i], perm_c[i], Cout[i], dst[i], ldd[i])) {
+    const int route = ds2_opt_matrix_route(mode, p[i], g[i], m[i], vi, R[i], C[i], perm_c[i], perm_f[i], Cout[i], dst[i], ldd[i], dstT[i], lddT[i]);
+    if (route < 0) return -route;
+    if (route != OPT_ROUTE_MATRIX4) {
       const int rc = ds2_opt_matrix(mode, p[i], g[i], m[i], vi, R[i], C[i], perm_c[i], perm_f[i], Cout[i], dst[i], ldd[i], dstT[i], lddT[i], hp,
                                     first, clip, st_);
       if (rc != 0) return rc;
@@ -579,23 +592,19 @@ int ds2_opt_matrices(int mode, int count, float* const* p, const float* const* g
 int ds2_opt_matrix(int mode, float* p, const float* g, float* m, float* v, int R, int C, int perm_c, int perm_f, int Cout,
                    void* dst, long ldd, void* dstT, long lddT, const float* hp, int first, const float* clip, ds2_stream_t st_) {
   hipStream_t st = (hipStream_t)st_;
-  DS2_REQUIRE((mode == 0 || mode == 1) && p && g && m && hp && (mode == 1 || v), DS2_ERR_ARG);
-  DS2_REQUIRE(R > 0 && C > 0 && R % 16 == 0 && Cout >= C, DS2_ERR_ARG);
-  DS2_REQUIRE(perm_c == 0 || perm_c * perm_f == C, DS2_ERR_ARG);
-  DS2_REQUIRE(dstT == nullptr || (lddT % 8 == 0 && (((uintptr_t)dstT) & 15) == 0), DS2_ERR_ALIGN);
+  DS2_REQUIRE(hp, DS2_ERR_ARG);
+  const int route = ds2_opt_matrix_route(mode, p, g, m, v, R, C, perm_c, perm_f, Cout, dst, ldd, dstT, lddT);
+  if (route < 0) return -route;
   const Hyper h = make_hyper(mode, hp, first, clip);
-  const bool vec = opt_matrix_vec_ok(mode, p, g, m, v, C, perm_c, Cout, dst, ldd);
-  if (vec)
+  if (route == OPT_ROUTE_MATRIX4)
     hipLaunchKernelGGL(k_opt_matrix4, dim3(ds2_cdiv(C, 64), ds2_cdiv(R, 64)), dim3(256), 0, st, p, g, m, v, R, C, (uint16_t*)dst, ldd,
                        (uint16_t*)dstT, lddT, h);
-  else if (perm_rows_cw(C, perm_c, perm_f) > 0 && PR_ROWS * perm_rows_cw(C, perm_c, perm_f) * perm_f * 2 <= PR_MAX_LDS &&
-           (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)(mode == 0 ? v : p)) & 15) == 0 &&
-           (dst == nullptr || (ldd % 8 == 0 && (((uintptr_t)dst) & 15) == 0))) {
+  else if (route == OPT_ROUTE_PERM_ROWS) {
     const int cw = perm_rows_cw(C, perm_c, perm_f);
     hipLaunchKernelGGL(k_opt_matrix_perm_rows, dim3(R / PR_ROWS, perm_c / cw), dim3(256), PR_ROWS * cw * perm_f * 2, st, p, g, m, v, C,
                        perm_c, perm_f, cw, Cout, (uint16_t*)dst, ldd, (uint16_t*)dstT, lddT, h);
   }
-  else if (perm_c > 0 && C % 4 == 0 && (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)(mode == 0 ? v : p)) & 15) == 0)
+  else if (route == OPT_ROUTE_PERM)
     hipLaunchKernelGGL(k_opt_matrix_perm, dim3(ds2_cdiv(C, 64), ds2_cdiv(R, 64)), dim3(256), 0, st, p, g, m, v, R, C, perm_c, perm_f,
                        Cout, (uint16_t*)dst, ldd, (uint16_t*)dstT, lddT, h);
   else

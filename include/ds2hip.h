@@ -327,8 +327,15 @@ int ds2_opt_multi(int mode, int count, float* const* p, const float* const* g, f
                   const float* hp, int first, const float* clip, ds2_stream_t stream);
 int ds2_opt_matrix(int mode, float* p, const float* g, float* m, float* v, int R, int C, int perm_c, int perm_f, int Cout,
                    void* dst, long ldd, void* dstT, long lddT, const float* hp, int first, const float* clip, ds2_stream_t stream);
-/* ds2_opt_matrix for `count` matrices of ONE parameter group (arrays of the per-matrix arguments): every matrix without a column
- * permutation (perm_c == 0, Cout == C, C % 4 == 0, 16-byte aligned) is updated in one launch per 36 of them, the others one by one. */
+/* The kernel ds2_opt_matrix takes for these arguments, host only (the pointers are looked at for null and alignment, never
+ * dereferenced): 0 the vectorised k_opt_matrix4 (no permutation, Cout == C, C % 4 == 0, 16-byte aligned operands, ldd % 4 == 0),
+ * 1 k_opt_matrix_perm_rows (permutation with perm_c % 8 == 0 and C % 8 == 0, an LDS image of at most 64 KB, aligned operands,
+ * ldd % 8 == 0), 2 k_opt_matrix_perm (any other permutation with C % 4 == 0 and aligned fp32 operands), 3 the general k_opt_matrix;
+ * arguments ds2_opt_matrix rejects: minus its error code.  ds2_opt_matrix and ds2_opt_matrices both decide through it. */
+int ds2_opt_matrix_route(int mode, const void* p, const void* g, const void* m, const void* v, int R, int C, int perm_c, int perm_f,
+                         int Cout, const void* dst, long ldd, const void* dstT, long lddT);
+/* ds2_opt_matrix for `count` matrices of ONE parameter group (arrays of the per-matrix arguments): every matrix of route 0 (no
+ * column permutation, Cout == C, C % 4 == 0, 16-byte aligned) is updated in one launch per 36 of them, the others one by one. */
 int ds2_opt_matrices(int mode, int count, float* const* p, const float* const* g, float* const* m, float* const* v, const int* R,
                      const int* C, const int* perm_c, const int* perm_f, const int* Cout, void* const* dst, const long* ldd,
                      void* const* dstT, const long* lddT, const float* hp, int first, const float* clip, ds2_stream_t stream);
