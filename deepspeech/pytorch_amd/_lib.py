@@ -135,6 +135,11 @@ SIGNATURES = {
     "ds2_endpoint_close": (_i, [_vp, _i, _vp, _vp, _vp]),
     "ds2_endpoint_gather": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ds2_endpoint_commit": (_i, [_vp, _vp, _vp, _l, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp]),
+    "ds2_kws_state_bytes": (_l, [_i, _i, _i]),
+    "ds2_kws_ws_bytes": (_l, [_i, _i, _i, _i]),
+    "ds2_kws_out_stride": (_l, [_i, _i]),
+    "ds2_kws_reset": (_i, [_vp, _i, _i, _i, _vp, _vp]),
+    "ds2_kws_feed": (_i, [_vp, _l, _l, _i, _i, _i, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ds2_stream_plan": (_i, [_l, _i, _i, _i, _vp]),
     "ds2_stream_state_bytes": (_l, [_i, _i, _i, _i, _i]),
     "ds2_stream_conv1": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -1755,6 +1755,114 @@ def ctc_align(x, sizes, targets, target_lengths, blank=0, mode="probs", max_targ
     return frame_state, tok[0, :total], tok[1, :total], tok_logp[:total], score
 
 
+# ---- keyword spotting (csrc/ds2_kws.hip) ----------------------------------------------------------------------------------------
+KWS_MAX_LABELS, KWS_MAX_HITS, KWS_MAX_STREAMS = 64, 4096, 65535     # ds2_kws_feed's limits
+KWS_FIRST_FETCH = 32          # hits per stream that travel with the headers; a feed with more costs a second copy
+
+
+class KwsHandle:
+    """The device state of N keyword spotters (ds2_kws_*) over one packed keyword list.  Made by kws_open."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def kws_open(num_streams, lanes, num_keywords, hold, max_hits, blank, device="cuda"):
+    """Opens N = num_streams spotters.  lanes: the packing of the K = num_keywords keywords, an int32 array
+    (waves * 64, 4) of (label, flags, keyword, thr_abs bits) per lane (keywords.pack).  The handle owns
+    ds2_kws_state_bytes(N, waves, K) bytes of state and the output rows (N, ds2_kws_out_stride(K, max_hits)) int32.  Every
+    stream starts at frame 0 with no path."""
+    N, K, hold, max_hits = int(num_streams), int(num_keywords), int(hold), int(max_hits)
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise ValueError("a keyword spotter lives on a HIP device, not on %s" % dev)
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    if not 1 <= N <= KWS_MAX_STREAMS:
+        raise ValueError("a keyword stream takes 1 to %d streams, got %d" % (KWS_MAX_STREAMS, N))
+    if hold < 1 or not 1 <= max_hits <= KWS_MAX_HITS or K < 1 or int(blank) < 0:
+        raise ValueError("kws_open needs hold >= 1, max_hits in [1, %d], keywords and a blank >= 0; got %d, %d, %d, %d"
+                         % (KWS_MAX_HITS, hold, max_hits, K, blank))
+    ln = torch.as_tensor(np.ascontiguousarray(lanes, dtype=np.int32))
+    if ln.dim() != 2 or ln.shape[1] != 4 or ln.shape[0] == 0 or ln.shape[0] % 64:
+        raise ValueError("lanes is an int32 array of shape (waves * 64, 4), got %s" % (tuple(ln.shape),))
+    W = ln.shape[0] // 64
+    with torch.cuda.device(dev):
+        state = torch.empty(query("ds2_kws_state_bytes", N, W, K) // 4, dtype=torch.int32, device=dev)
+        stride = query("ds2_kws_out_stride", K, max_hits)
+        h = KwsHandle(state=state, key=state[N * W * 256:N * W * 256 + N * K * 8].view(N, K, 8),
+                      frm=state[N * W * 256 + N * K * 8:N * W * 256 + N * K * 8 + N * W].view(N, W), lanes=ln.to(dev), N=N, W=W, K=K,
+                      hold=hold, max_hits=max_hits, blank=int(blank), device=dev,
+                      out=torch.empty((N, stride), dtype=torch.int32, device=dev))
+        kws_reset(h)
+    return h
+
+
+def kws_reset(h, streams=None):
+    """Streams `streams` (indices; None = all) start again: no path, no candidate, no best, frame 0; the others are untouched."""
+    call("ds2_kws_reset", P(h.state), h.N, h.W, h.K, P(_stream_mask(streams, h.N, h.device)), S())
+
+
+def kws_feed(h, x, sizes=None, mode="probs", end=None):
+    """Advances the spotters of h over one chunk and fetches the hits that THIS feed emits (ds2_kws_feed; waits for the device).
+    x: (N, Tc, C) float32 CUDA tensor, any strides with a contiguous class dimension (the transposed view DeepSpeech.forward
+    returns is read in place), or None for an end alone; mode: what x holds, "logits", "probs" or "log_probs"; sizes: [N] ints
+    (tensor or sequence; None = Tc), frames at and beyond them are never read and 0 leaves a stream as it is.  end: None, True
+    (every stream ends after its frames: an open candidate is emitted) or the indices of the streams that end.
+    Returns (hits, dropped): per stream the list of (keyword, start_frame, end_frame, score) in (keyword, time) order with
+    absolute frames, and the hits of this feed beyond max_hits per keyword, which are counted and not returned."""
+    N, K = h.N, h.K
+    m = CTC_ALIGN_MODES.get(mode, mode)
+    if m not in (0, 1, 2):
+        raise ValueError("mode must be one of %s, got %r" % (sorted(CTC_ALIGN_MODES), mode))
+    if x is None:
+        Tc, Cc, xs = 0, 2 ** 31 - 1, (P(None), 0, 0)       # no column is read; every label counts as a class
+    else:
+        if not (torch.is_tensor(x) and x.is_cuda and x.dim() == 3 and x.dtype == torch.float32 and x.shape[0] == N
+                and x.shape[2] > h.blank):
+            raise ValueError("a chunk for this keyword stream is a float32 HIP device tensor of shape (%d, Tc, C > %d), got %s"
+                             % (N, h.blank, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+        if x.stride(2) != 1:
+            x = x.contiguous()
+        Tc, Cc = x.shape[1], x.shape[2]
+        xs = (P(x), x.stride(0), x.stride(1)) if Tc > 0 else (P(None), 0, 0)
+    sz = _sizes_to_device(sizes, h.device) if Tc > 0 else None
+    if sz is not None and sz.shape != (N,):
+        raise ValueError("sizes must have one entry per stream (%d), got shape %s" % (N, tuple(sz.shape)))
+    end_all = end is True
+    mask = None if end is None or end_all else _stream_mask(end, N, h.device)
+    if Tc == 0 and not end_all and mask is None:
+        return [[] for _ in range(N)], [0] * N
+    ws = torch.empty(query("ds2_kws_ws_bytes", N, Tc, K, h.max_hits), dtype=torch.uint8, device=h.device)
+    call("ds2_kws_feed", *xs, N, Tc, Cc, m, P(sz), h.blank, P(h.lanes), h.W, K, h.hold, h.max_hits, P(mask), int(end_all),
+         P(h.state), P(h.out), P(ws), S())
+    first = min(K * h.max_hits, KWS_FIRST_FETCH)
+    host = h.out[:, :4 + 4 * first].cpu()
+    counts = host[:, 0].tolist()
+    top = max(counts)
+    rows = host[:, 4:]
+    if top > first:
+        rows = torch.cat([rows, h.out[:, 4 + 4 * first:4 + 4 * top].cpu()], 1)
+    hits = []
+    for n in range(N):
+        r = rows[n, :4 * counts[n]].view(counts[n], 4)
+        sc = r[:, 3].contiguous().view(torch.float32).tolist()
+        hits.append([(k, b, e, s) for (k, b, e, _), s in zip(r.tolist(), sc)])
+    return hits, host[:, 1].tolist()
+
+
+def kws_best(h):
+    """Host tensors (scores (N, K) float32, spans (N, K, 2) int32): per stream and keyword the largest end score so far and its
+    (start, end) frames; -inf, -1, -1 before any path exists (waits for the device)."""
+    key = h.key.cpu()
+    return key[:, :, 3].contiguous().view(torch.float32), key[:, :, 4:6].contiguous()
+
+
+def kws_frames(h):
+    """Frames consumed per stream (host ints; waits for the device)."""
+    return h.frm[:, 0].cpu().tolist()
+
+
 # ---- word timings and confidence (csrc/ds2_confidence.hip) --------------------------------------------------------------------
 CONFIDENCE_MAX_CLASSES, CONFIDENCE_MAX_BEAMS = 8192, 256     # ds2_confidence's limits (the decoders')
 CONFIDENCE_MEASURES = {"label_prob": 0, "max_prob": 1, "entropy": 2, "tsallis": 3, "renyi": 4}

@@ -61,7 +61,8 @@ def plan_feed(frames, chunk, ctx, final=False):
 
 
 class StreamingTranscriber:
-    def __init__(self, model, decoder, front_end=None, max_frames=6000, carry_context=False, endpoint=None, confidence=None):
+    def __init__(self, model, decoder, front_end=None, max_frames=6000, carry_context=False, endpoint=None, confidence=None,
+                 keywords=None):
         """model: a DeepSpeech on a HIP device; decoder: a BeamCTCDecoder or GreedyDecoder over the model's labels; front_end: a
         SpectrogramFrontEnd for feed_wave (None = one with the model's spect_cfg, made on first use).  max_frames bounds the output
         frames per stream of a beam decoder (its node pool is allocated at the first feed).  carry_context: exact chunked
@@ -71,9 +72,12 @@ class StreamingTranscriber:
         and only the decoder starts again at an endpoint -- the acoustic state runs on.
         confidence: a confidence.Confidence makes the decoder stream keep max_frames frames of probabilities per stream on the
         device and gives the session ``words()`` / ``best_words()``; with an endpoint the frames live in a ring, ``segments()``
-        returns decoder.WordSegments that carry ``.hypotheses``, and ``words()`` is the open segment's partial."""
+        returns decoder.WordSegments that carry ``.hypotheses``, and ``words()`` is the open segment's partial.
+        keywords: a keywords.KeywordSpotter gets every chunk's probabilities and sizes as the decoder stream does (DESIGN.md
+        section 3.9); ``detections()`` drains what it found, a final feed or ``end`` emits its open candidates."""
         self.model, self.decoder, self.front_end, self.max_frames = model, decoder, front_end, int(max_frames)
         self.endpoint, self.confidence = endpoint, confidence
+        self.keywords, self._kws, self._dets = keywords, None, []
         if endpoint is not None and isinstance(decoder, BeamCTCDecoder):
             endpoint.check_max_frames(self.max_frames)
         self.hs, self.stream = None, None
@@ -91,6 +95,19 @@ class StreamingTranscriber:
         else:
             self.stream = self.decoder.stream(N, device, endpoint=self.endpoint, confidence=self.confidence,
                                               max_frames=self.max_frames if self.confidence is not None else None)
+        if self.keywords is not None:
+            self._kws, self._dets = self.keywords.stream(N, device), [[] for _ in range(N)]
+
+    def _spot(self, found):
+        for n, d in enumerate(found):
+            self._dets[n] += d
+
+    def detections(self):
+        """keywords: per stream the list of keywords.Detections emitted since the last call, in the order they were emitted"""
+        if self.keywords is None:
+            raise ValueError("detections() belongs to a session with keywords=")
+        out, self._dets = self._dets, [[] for _ in self._dets]
+        return out
 
     def words(self, nbest=1, frame_seconds=None):
         """Per stream the confidence.Hypothesis list of everything fed so far, as ``decoder.decode_words`` gives it on the
@@ -151,6 +168,8 @@ class StreamingTranscriber:
         finally:
             m.train(was_training)
         self.stream.feed(out, out_lens)                # (N, T', C) stays on the device
+        if self._kws is not None:
+            self._spot(self._kws.feed(out, out_lens))
         return self.best()
 
     def feed_wave(self, wav, nsamples, final=False):
@@ -226,6 +245,9 @@ class StreamingTranscriber:
         self.hs = None
         if self.stream is not None:
             self.stream.reset()
+        if self._kws is not None:
+            self._kws.reset()
+            self._dets = [[] for _ in self._dets]
         if self._state is not None:
             self._state["buf"].zero_()
             self._state["cur"] = [0, 0, 0]
@@ -313,7 +335,11 @@ class StreamingTranscriber:
                     probs = m.stream_head(y, N, J3)
                     self.last_output = (probs, sizes)
                     self.stream.feed(probs, torch.tensor(sizes, dtype=torch.int))
+                    if self._kws is not None:
+                        self._spot(self._kws.feed(probs, torch.tensor(sizes, dtype=torch.int)))
                     self._text = self.best()
+        if final and self._kws is not None:
+            self._spot(self._kws.end())
         if final and self.endpoint is not None:
             self.stream.end()                      # the last segment closes; the open one is empty from here on
             self._text = [''] * N
@@ -350,7 +376,7 @@ class StreamPool:
     one recurrent stack over the rows that retire an RNN frame, one lookahead, one head, one decoder feed -- and per stream the
     probabilities emitted over its feeds, concatenated, are the one-shot eval ``forward`` of that utterance alone."""
 
-    def __init__(self, model, decoder, capacity, max_frames=6000, front_end=None, endpoint=None, confidence=None):
+    def __init__(self, model, decoder, capacity, max_frames=6000, front_end=None, endpoint=None, confidence=None, keywords=None):
         """model: a uni-directional DeepSpeech on a HIP device (run in eval mode, no autograd); decoder: a BeamCTCDecoder or
         GreedyDecoder over its labels; max_frames bounds the output frames per stream of a beam decoder; front_end: a causal
         SpectrogramFrontEnd for feed_wave (None = one with the model's spect_cfg and normalize="running", made on first use).
@@ -359,7 +385,10 @@ class StreamPool:
         last one, max_frames bounds a segment and not the stream, and the acoustic state is not reset at an endpoint.
         confidence: a confidence.Confidence makes the decoder stream keep max_frames frames of probabilities per slot on the
         device and gives the pool ``words(slot)``; with an endpoint the frames live in a ring, ``segments(slot)`` returns
-        decoder.WordSegments that carry ``.hypotheses``, and ``words(slot)`` is the open segment's partial."""
+        decoder.WordSegments that carry ``.hypotheses``, and ``words(slot)`` is the open segment's partial.
+        keywords: a keywords.KeywordSpotter gets the block and the sizes of every feed as the decoder stream does (DESIGN.md
+        section 3.9); ``detections(slot)`` drains what it found in the slot's stream, ``open`` resets the slot's keyword state, a
+        final feed or ``end`` emits the slot's open candidates."""
         if model.bidirectional:
             raise ValueError("a StreamPool needs a uni-directional model: a reverse direction cannot be streamed exactly")
         if int(capacity) < 1:
@@ -370,6 +399,8 @@ class StreamPool:
             endpoint.check_max_frames(self.max_frames)
         S = self.capacity
         self._segs = [[] for _ in range(S)]                # endpoint: per slot the finished segments not yet handed out
+        self.keywords, self._kws = keywords, None
+        self._dets = [[] for _ in range(S)]                # keywords: per slot the detections not yet handed out
         self.stream, self._state, self._h = None, None, None
         self._open = [False] * S
         self._fed, self._ended, self._text = [0] * S, [False] * S, [''] * S
@@ -395,6 +426,9 @@ class StreamPool:
             if self.endpoint is not None:
                 self._pull_segments()
             self.stream.reset([s])
+        if self._kws is not None:
+            self._kws.reset([s])
+        self._dets[s] = []
         self._segs[s] = []
         if self._h is not None and not self._h_zero[s]:
             self._h[:, :, s].zero_()
@@ -418,6 +452,14 @@ class StreamPool:
         if self.stream is not None:
             self._pull_segments()
         out, self._segs[s] = self._segs[s], []
+        return out
+
+    def detections(self, slot):
+        """keywords: the keywords.Detections of the slot's stream emitted since the last call, in the order they were emitted"""
+        s = self._check_slots([slot])[0]
+        if self.keywords is None:
+            raise ValueError("detections() belongs to a pool with keywords=")
+        out, self._dets[s] = self._dets[s], []
         return out
 
     def frames(self, slot):
@@ -552,6 +594,8 @@ class StreamPool:
             self.stream = self.decoder.stream(S, self.max_frames, dev, endpoint=self.endpoint, confidence=self.confidence) if beam else \
                 self.decoder.stream(S, dev, endpoint=self.endpoint, confidence=self.confidence,
                                     max_frames=self.max_frames if self.confidence is not None else None)
+            if self.keywords is not None:
+                self._kws = self.keywords.stream(S, dev)
         dtype = m._stream_begin()
         st = self._state
         if st is None or st["dtype"] != dtype:
@@ -600,14 +644,22 @@ class StreamPool:
                 if rp.cnt3[i] > 0:
                     self.last_output[sl[i]] = probs[r, :rp.cnt3[i]]
             self.stream.feed(full, torch.tensor(sizes, dtype=torch.int))
+            if self._kws is not None:
+                self._spot(self._kws.feed(full, torch.tensor(sizes, dtype=torch.int)))
             text = self.stream.best()[0] if beam else self.stream.text
             for s in sl:
                 self._text[s] = text[s]
+        if fin and self._kws is not None:
+            self._spot(self._kws.end(sorted(fin)))
         if fin and self.endpoint is not None:
             self.stream.end(sorted(fin))           # the last segment closes; the open one is empty from here on
             for s in fin:
                 self._text[s] = ''
         return [self._text[s] for s in sl]
+
+    def _spot(self, found):
+        for n, d in enumerate(found):
+            self._dets[n] += d
 
     def _advance(self, slots, bit):
         """a launched stage wrote its next carry for these slots: the other buffer holds it now, and it is no longer fresh"""

@@ -664,6 +664,52 @@ int ds2_endpoint_gather(const float* x, long stride_n, long stride_t, int N, int
 int ds2_endpoint_commit(const int* events, const int* tokens, const int* offsets, long row_stride, int ranks, const int* lens,
                         const float* scores, const float* acoustic, int N, void* ring, int* pending, int slots, ds2_stream_t stream);
 
+/* ---- keyword spotting on the CTC outputs, one-shot and streamed ------------------------------------
+ * THE RULE (tests/kws_reference.py restates it in numpy; every word is pinned by tests).
+ * Frame scores: for frame t with class scores x_t[c], r_t[c] = lp_t[c] - max_c' lp_t[c'] <= 0, where lp = x for mode 0 (logits)
+ *   and 2 (log-probabilities) and lp = logf(x) for mode 1 (probabilities); the log-normaliser cancels, so logits need no
+ *   log-sum-exp.  A detection's score is a log-likelihood ratio: the best path through the keyword on its frames against the
+ *   greedy path on the same frames; it is 0 exactly when the greedy path spells the keyword there.
+ * Lattice: a keyword is labels y_1..y_L, 1 <= L <= 64, never the blank; the space label may stand anywhere.  2L - 1 states
+ *   y_1, blank, y_2, blank, ..., y_L (no leading or trailing blank), each with a value v (fp32) and the absolute frame b at which
+ *   its path started.  At frame t state 0 takes max(v_{t-1}(0), 0), the fresh start (b = t) only when 0 is strictly greater, so
+ *   a run of y_1 keeps its first frame.  State s > 0 takes the best of s, s - 1 and, for a label state with y_i != y_{i-1},
+ *   s - 2, tried in that order, a candidate replacing the current best only when strictly greater.  After the max, r_t[ext_s] is
+ *   added.  An unreachable state is exactly -inf with b = -1.  All arithmetic is fp32, in this order.
+ * End score: (s_t, b_t) = value and start of state 2L - 2 after frame t.
+ * Events: thr_abs = fp32(threshold * L) (threshold in nats per label), hold >= 1 frames.  At frame t, in this order:
+ *   1. a candidate is open and t - cand.end >= hold: it is emitted and closed;
+ *   2. s_t >= thr_abs and s_t > -inf: (s_t, b_t, t) opens a candidate when none is open; else it replaces the candidate when
+ *      s_t > cand.score, or s_t == cand.score and b_t == cand.start (a hit extends through the run of its last label).
+ *   An end (end_mask / end_all) emits an open candidate after the feed's frames.  A hit is (keyword, start, end, score).
+ * Best: every (stream, keyword) tracks the largest s_t so far with (b_t, t), replaced only when strictly greater; -inf, -1, -1
+ *   before any path exists.
+ * lanes: the host's packing, int32 [waves * 64][4] on the device, 16-byte aligned: per lane (label, flags, keyword index,
+ *   thr_abs bits).  The keywords fill waves of 64 lanes in list order, one lane per label, no keyword straddling a wave; flags:
+ *   1 = the keyword's first label, 2 = its last, 4 = y_i != y_{i-1}; an unused lane has label -1.
+ * state: ds2_kws_state_bytes(N, waves, K) bytes, 16-byte aligned: [N][waves][4][64] lattice words (label value, blank value,
+ *   label start, blank start), [N][K][8] keyword words (candidate score, start, end; best score, start, end; two reserved; end
+ *   -1 = no candidate), [N][waves] int32 frame counters (2^31 frames per stream).  ds2_kws_reset: the streams with mask[n] != 0
+ *   (null = all) start again: no path, no candidate, no best, frame 0.
+ * ds2_kws_feed: x is the chunk (N, Tc, C) with ds2_beam_stream_feed's strides, Tc >= 0 (0: an end alone, x may be null); sizes
+ *   [N] int32 on the device (null = Tc); frames at and beyond sizes[n] are never read, and sizes[n] == 0 leaves the state of
+ *   stream n bitwise as it is unless the stream ends.  Streams with end_mask[n] != 0 (device int32 [N], may be null), or all with
+ *   end_all != 0, end after their frames.  out: int32 [N][ds2_kws_out_stride(K, max_hits)], 16-byte aligned: per stream the
+ *   header (hits, dropped, frames consumed, 0), then the hits emitted by THIS feed as (keyword, start, end, score bits),
+ *   keyword-major and in time order within a keyword.  Of one keyword's hits in one feed the first max_hits are kept and the
+ *   others counted in dropped.  ws: ds2_kws_ws_bytes(N, Tc, K, max_hits) bytes, 16-byte aligned.  A one-shot call is
+ *   ds2_kws_reset + one ds2_kws_feed with end_all.  Three launches (two when Tc == 0), no atomics, the same bits every time.
+ * DS2_ERR_ARG: a null pointer other than sizes / mask / end_mask (x only when Tc > 0), N < 1 or > 65535, C, waves or K < 1,
+ *   Tc < 0, a blank outside [0, C), a mode outside [0, 2], hold < 1, max_hits outside [1, 4096].  DS2_ERR_ALIGN as above.  Size
+ *   queries: -1. */
+long ds2_kws_state_bytes(int N, int waves, int K);
+long ds2_kws_ws_bytes(int N, int Tc, int K, int max_hits);
+long ds2_kws_out_stride(int K, int max_hits);
+int ds2_kws_reset(void* state, int N, int waves, int K, const int* mask, ds2_stream_t stream);
+int ds2_kws_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, int mode, const int* sizes, int blank,
+                 const int* lanes, int waves, int K, int hold, int max_hits, const int* end_mask, int end_all, void* state, int* out,
+                 void* ws, ds2_stream_t stream);
+
 /* ---- exact chunked inference: conv front-end and lookahead with carried time context -------------
  * For a uni-directional model in eval mode: fed chunk by chunk, the three kernels below give the frames of the one-shot forward.
  * Each reads, per stream n, a VIRTUAL WINDOW over time: position i < K comes from `carry` (the K positions in front of the
