@@ -6,7 +6,8 @@
 // Geometry: 512 threads = 8 waves as 2 (M) x 4 (N); a wave owns 128 x 64 of the tile = 4 x 2 accumulators of
 // v_mfma_f32_32x32x16_bf16 (128 registers).  K-tile 64.  LDS: two K-tile buffers of 64 KiB (A 32 KiB | B 32 KiB), filled by
 // global_load_lds_dwordx4 (lane-linear destination; the bank-conflict XOR lives in the per-lane SOURCE address and in the
-// fragment read address -- both or neither).
+// fragment read address -- both or neither).  Behind the buffers, 2 KiB: the tile's output rows and bias values (NT), fetched with the
+// prologue and read by the epilogue.
 //
 // Schedule (one K-tile = four phases, one quadrant 64 x 32 of the wave's tile each = 8 MFMAs = 256 matrix-pipe cycles):
 //   phase 0   read A(m-half 0) [8 x ds_read_b128] + B(n-half 0) [4]     | MFMA (0,0)
@@ -51,6 +52,9 @@ struct G8Args {
   int stag_cus, stag_ticks;   // start offsets of the first round (g8_stagger_wait): CU count, span in 10 ns ticks (0 = none)
 };
 
+constexpr int G8_LDS_OPERANDS = 131072;      // two K-tile buffers; the epilogue's row indices (1 KiB) and bias (1 KiB) follow
+constexpr int G8_LDS_BYTES = G8_LDS_OPERANDS + 2048;
+
 #define G8_WAIT_VM(n) asm volatile("s_waitcnt vmcnt(" #n ")" ::: "memory")
 #define G8_WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define G8_BARRIER()                        \
@@ -77,6 +81,20 @@ __device__ __forceinline__ void g8_tile(const G8Problem& P, int t_id, unsigned c
   const int nkt = (K_ + 63) / 64;                       // NT: K % 64 == 0 (host check); TN: a ragged last K-tile is zero-filled in LDS
   const int krem = K_ - (nkt - 1) * 64;                 // valid k-rows of the last K-tile (1..64)
   const bool tail = TN && krem < 64;
+
+  // What the epilogue needs from memory is fetched here, one word per thread, in front of the loads that the DMA addresses wait
+  // for anyway, and parked in LDS behind the operand buffers once the prologue's DMA is out: no load then stands between the last
+  // MFMA and the stores.  Waves 0-3: the tile's 256 output rows (the row list's entries); waves 4-7: its 256 bias values (0 where
+  // there is none, which is what the epilogue added before).  TN tiles have neither.
+  int* const ep_rows = reinterpret_cast<int*>(lds + G8_LDS_OPERANDS);
+  float* const ep_bias = reinterpret_cast<float*>(lds + G8_LDS_OPERANDS + 1024);
+  int ep_word = 0;
+  if constexpr (!TN) {
+    const int r = min(m0 + tid, P.M - 1), c = n0 + tid - 256;
+    const int* src = wm == 0 ? (P.rows ? P.rows + r : nullptr) : ((P.bias && c < P.N) ? reinterpret_cast<const int*>(P.bias + c) : nullptr);
+    ep_word = wm == 0 ? r : 0;
+    if (src) ep_word = *src;
+  }
 
   ds2_f32x16 acc[4][2];
 #pragma unroll
@@ -348,6 +366,7 @@ __device__ __forceinline__ void g8_tile(const G8Problem& P, int t_id, unsigned c
   } else {
     G8_WAIT_VM(0);
   }
+  if constexpr (!TN) ep_rows[tid] = ep_word;      // ep_bias = ep_rows + 256; visible behind the K-tiles' waits and barriers
   G8_BARRIER();
   if (wm == 1) G8_BARRIER();        // M-half 1 runs one barrier behind
   for (int kt = 0; kt < nkt; kt += 2) {
@@ -362,6 +381,12 @@ __device__ __forceinline__ void g8_tile(const G8Problem& P, int t_id, unsigned c
   const float* bias = P.bias;
   const int M_ = P.M, N_ = P.N;
   const long ldc = P.ldc;
+  auto row_of = [&](int lrow, int grow) -> long {      // row of C that tile row lrow (row m0 + lrow = grow of the problem) is stored to
+    if constexpr (!TN)
+      return ep_rows[lrow];
+    else
+      return grow;                                     // a TN problem's row list runs over the contraction, not over C
+  };
   if (!P.out_is_f32 && (ldc % 8 == 0) && ((((uintptr_t)P.C) & 15) == 0)) {
     // bf16 output: through LDS (free now: every wave is past the last barrier, nothing reads the operand tiles any more), so that
     // a store instruction writes whole 128-byte row segments (8 rows x 128 B per instruction) instead of 16-byte pieces of 32
@@ -380,7 +405,10 @@ __device__ __forceinline__ void g8_tile(const G8Problem& P, int t_id, unsigned c
             const int col = j * 32 + 8 * q + 4 * elq;
             const int gcol = n0 + wn * 64 + col;
             float bv[4] = {0.f, 0.f, 0.f, 0.f};
-            if (bias) {
+            if constexpr (!TN) {
+              const float4 b4 = *reinterpret_cast<const float4*>(ep_bias + wn * 64 + col);
+              bv[0] = b4.x, bv[1] = b4.y, bv[2] = b4.z, bv[3] = b4.w;
+            } else if (bias) {
 #pragma unroll
               for (int e = 0; e < 4; ++e) bv[e] = gcol + e < N_ ? bias[gcol + e] : 0.f;
             }
@@ -395,7 +423,7 @@ __device__ __forceinline__ void g8_tile(const G8Problem& P, int t_id, unsigned c
         const uint4 d = *reinterpret_cast<const uint4*>(ep + row_l * 144 + seg * 16);
         const int grow = m0 + wm * 128 + half * 64 + row_l, gcol = n0 + wn * 64 + seg * 8;
         if (grow < M_) {
-          bf16_t* cp = Cb + (long)(P.rows ? P.rows[grow] : grow) * ldc + gcol;
+          bf16_t* cp = Cb + row_of(wm * 128 + half * 64 + row_l, grow) * ldc + gcol;
           if (gcol + 7 < N_) {
             *reinterpret_cast<uint4*>(cp) = d;
           } else {
@@ -422,8 +450,15 @@ __device__ __forceinline__ void g8_tile(const G8Problem& P, int t_id, unsigned c
         if (col >= N_) continue;
         float v[4];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = acc[i][j][4 * q + e] + ((bias && col + e < N_) ? bias[col + e] : 0.f);
-        const long off = (long)((!TN && P.rows) ? P.rows[row] : row) * ldc + col;
+        for (int e = 0; e < 4; ++e) {
+          float b;
+          if constexpr (!TN)
+            b = ep_bias[col - n0 + e];
+          else
+            b = (bias && col + e < N_) ? bias[col + e] : 0.f;
+          v[e] = acc[i][j][4 * q + e] + b;
+        }
+        const long off = row_of(wm * 128 + i * 32 + eli, row) * ldc + col;
         if (P.out_is_f32) {
           float* cp = (float*)P.C + off;
           if (col + 3 < N_ && n_vec_ok) {
@@ -465,7 +500,7 @@ __device__ __forceinline__ void g8_stagger_wait(int id, int cus, int ticks) {
 // places on one XCD (id % 8) get a contiguous run of its tiles (neighbouring tiles share operand panels in that XCD's L2).
 template <int MODE, bool SPREAD>
 __global__ void __launch_bounds__(512, 2) k_gemm8(G8Args g) {
-  __shared__ __attribute__((aligned(1024))) unsigned char lds[131072];
+  __shared__ __attribute__((aligned(1024))) unsigned char lds[G8_LDS_BYTES];
   const int id = blockIdx.x;
   g8_stagger_wait(id, g.stag_cus, g.stag_ticks);
   int pi = 0, first = 0;

@@ -269,25 +269,31 @@ def gemm_nt_rows2(A, A2, m_split, B, M, N, K, lda, ldb, splitk=1, coresident=Fal
     return out
 
 
-def gemm8_nt(A, B, bias=None, out_dtype=None, M=None, N=None, K=None, lda=None, ldb=None, rows=None, stagger_us=None):
+def gemm8_nt(A, B, bias=None, out_dtype=None, M=None, N=None, K=None, lda=None, ldb=None, rows=None, stagger_us=None, out=None):
     """C[M][N] = A[M][K] * B[N][K]^T (+bias) on the 256x256 phase-split kernel (bf16 operands, K % 64 == 0); rows: see gemm_nt.
     stagger_us (tests, A/B): the span of the first round's start offsets in microseconds, clamped to
-    query("ds2_gemm8_stagger_plan", -1, 0, 0); None = the library's policy.  The result does not depend on it."""
+    query("ds2_gemm8_stagger_plan", -1, 0, 0); None = the library's policy.  The result does not depend on it.
+    out: write into this [M][>= N] tensor (bf16 or fp32, unit column stride; its row stride is C's leading dimension) instead of a
+    new one -- a column window of a wider buffer; with `rows` the unlisted rows keep what they held."""
     M = A.shape[-2] if M is None else M
     N = B.shape[-2] if N is None else N
     K = A.shape[-1] if K is None else K
     lda = A.stride(-2) if lda is None else lda
     ldb = B.stride(-2) if ldb is None else ldb
-    out = torch.empty((M, N), dtype=out_dtype or A.dtype, device=A.device)
+    if out is None:
+        out = torch.empty((M, N), dtype=out_dtype or A.dtype, device=A.device)
+    elif out.dim() != 2 or out.shape[0] < M or out.shape[1] < N or out.stride(1) != 1 or out.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("gemm8_nt: out must be a [>= %d][>= %d] bf16 / fp32 tensor with unit column stride" % (M, N))
+    ldc = out.stride(0)
     if stagger_us is not None:
-        call("ds2_gemm8_nt_rows_stagger", P(A), P(B), P(out), PF(bias), M, N, K, lda, ldb, N, 1 if out.dtype == torch.float32 else 0, P(rows),
+        call("ds2_gemm8_nt_rows_stagger", P(A), P(B), P(out), PF(bias), M, N, K, lda, ldb, ldc, 1 if out.dtype == torch.float32 else 0, P(rows),
              rows.numel() if rows is not None else 0, int(stagger_us), S())
         return out
     if rows is not None:
-        call("ds2_gemm8_nt_rows", P(A), P(B), P(out), PF(bias), M, N, K, lda, ldb, N, 1 if out.dtype == torch.float32 else 0, P(rows),
+        call("ds2_gemm8_nt_rows", P(A), P(B), P(out), PF(bias), M, N, K, lda, ldb, ldc, 1 if out.dtype == torch.float32 else 0, P(rows),
              rows.numel(), S())
         return out
-    call("ds2_gemm8_nt", P(A), P(B), P(out), PF(bias), M, N, K, lda, ldb, N, 1 if out.dtype == torch.float32 else 0, S())
+    call("ds2_gemm8_nt", P(A), P(B), P(out), PF(bias), M, N, K, lda, ldb, ldc, 1 if out.dtype == torch.float32 else 0, S())
     return out
 
 
