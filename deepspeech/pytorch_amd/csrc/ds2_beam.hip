@@ -1099,9 +1099,9 @@ int hot_args_from(HotArgs& H, int C, int blank, int space, const void* hot_table
   return 0;
 }
 
-// the checks and the fields that ds2_beam_decode_lm and its grid form share; alpha and beta are left to the caller
+// the checks and the fields of the language-model entry points (the grid form passes alpha = beta = 0: its points carry them)
 int lm_args_from(LmArgs& A, int C, int blank, int space, const void* word_table, long word_slots, const void* ngram_table,
-                 long ngram_slots, int order, int bos, int lexicon, float* acoustic) {
+                 long ngram_slots, int order, int bos, float alpha, float beta, int lexicon, float* acoustic) {
   DS2_REQUIRE(C > 0 && space >= 0 && space < C && space != blank, DS2_ERR_ARG);
   DS2_REQUIRE(order >= 1 && order <= BEAM_LM_MAX_ORDER && bos >= 0, DS2_ERR_ARG);
   DS2_REQUIRE(word_table && ngram_table, DS2_ERR_ARG);
@@ -1116,8 +1116,8 @@ int lm_args_from(LmArgs& A, int C, int blank, int space, const void* word_table,
   A.order = order;
   A.bos = bos;
   A.lexicon = lexicon != 0;
-  A.alpha = 0.f;
-  A.beta = 0.f;
+  A.alpha = alpha;
+  A.beta = beta;
   A.acoustic = acoustic;
   return 0;
 }
@@ -1151,10 +1151,9 @@ int ds2_beam_decode_lm(const float* x, long stride_n, long stride_t, int N, int 
                        const void* ngram_table, long ngram_slots, int order, int bos, float alpha, float beta, int lexicon,
                        int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
   LmArgs A;
-  const int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  const int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, alpha, beta, lexicon,
+                              acoustic);
   if (rc) return rc;
-  A.alpha = alpha;
-  A.beta = beta;
   return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
                      (hipStream_t)st_, &A);
 }
@@ -1213,10 +1212,9 @@ int ds2_beam_stream_feed_lm(const float* x, long stride_n, long stride_t, int N,
                             void* state, int max_frames, int* tokens, int* offsets, long row_stride, int out_ranks, int* lens,
                             float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
   LmArgs A;
-  const int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  const int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, alpha, beta, lexicon,
+                              acoustic);
   if (rc) return rc;
-  A.alpha = alpha;
-  A.beta = beta;
   return beam_stream_feed(x, stride_n, stride_t, N, Tc, C, sizes, blank, B, cutoff_top_n, cutoff_prob, state, max_frames, tokens,
                           offsets, row_stride, out_ranks, lens, scores, ws, (hipStream_t)st_, &A);
 }
@@ -1242,10 +1240,9 @@ int ds2_beam_decode_lm_hot(const float* x, long stride_n, long stride_t, int N, 
                            const void* hot_table, long hot_slots, float hot_oov_logp, int* tokens, int* offsets, int* lens,
                            float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
   LmArgs A;
-  int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, alpha, beta, lexicon,
+                        acoustic);
   if (rc) return rc;
-  A.alpha = alpha;
-  A.beta = beta;
   HotArgs H;
   rc = hot_args_from(H, C, blank, space, hot_table, hot_slots, hot_oov_logp, nullptr);
   if (rc) return rc;
@@ -1274,10 +1271,9 @@ int ds2_beam_stream_feed_lm_hot(const float* x, long stride_n, long stride_t, in
                                 int* offsets, long row_stride, int out_ranks, int* lens, float* scores, float* acoustic, void* ws,
                                 ds2_stream_t st_) {
   LmArgs A;
-  int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, alpha, beta, lexicon,
+                        acoustic);
   if (rc) return rc;
-  A.alpha = alpha;
-  A.beta = beta;
   HotArgs H;
   rc = hot_args_from(H, C, blank, space, hot_table, hot_slots, hot_oov_logp, nullptr);
   if (rc) return rc;
@@ -1301,7 +1297,8 @@ int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N,
                             ds2_stream_t st_) {
   DS2_REQUIRE(G >= 1 && G <= BEAM_MAX_POINTS && alphas && betas, DS2_ERR_ARG);
   LmArgs A;
-  const int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, lexicon, acoustic);
+  const int rc = lm_args_from(A, C, blank, space, word_table, word_slots, ngram_table, ngram_slots, order, bos, 0.f, 0.f, lexicon,
+                              acoustic);
   if (rc) return rc;
   return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
                      (hipStream_t)st_, &A, G, alphas, betas);
@@ -1311,42 +1308,69 @@ int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N,
 
 namespace {
 
-int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
-                int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
-                const LmArgs* lm, int G, const float* alphas, const float* betas, const HotArgs* hot) {
-  DS2_REQUIRE(N > 0 && T > 0 && C > 0 && C <= BEAM_MAXC && blank >= 0 && blank < C, DS2_ERR_ARG);
+// the sixteen leading arguments of k_beam_search, and where it is launched
+struct SearchArgs {
+  dim3 grid;
+  hipStream_t st;
+  int T, C, blank, B, K;
+  const int* sizes;
+  float* plp;
+  int *pcnt, *pcls, *parent, *label, *frame, *tokens, *offsets, *lens;
+  float* scores;
+};
+
+// What the one-shot and the resumable search share: the checks of their common arguments, K, the kept lists' place in ws (L is
+// ws_layout's or stream_ws_layout's) and the launch that fills them, none for T == 0 (min_T == 0: the resumable form allows it).
+int beam_prune(SearchArgs& a, const float* x, long stride_n, long stride_t, int N, int T, int min_T, int C, const int* sizes,
+               int blank, int B, int cutoff_top_n, float cutoff_prob, void* ws, const WsLayout& L, hipStream_t st) {
+  DS2_REQUIRE(N > 0 && T >= min_T && C > 0 && C <= BEAM_MAXC && blank >= 0 && blank < C, DS2_ERR_ARG);
   DS2_REQUIRE(B >= 1 && B <= BEAM_MAXB && cutoff_top_n >= 1, DS2_ERR_ARG);
   const int K = cutoff_top_n < C ? cutoff_top_n : C;
   DS2_REQUIRE(K <= BEAM_MAXK, DS2_ERR_ARG);
-  DS2_REQUIRE(x && tokens && (offsets || alphas) && lens && scores && ws, DS2_ERR_ARG);
-  DS2_REQUIRE(((uintptr_t)ws & 255) == 0, DS2_ERR_ALIGN);
-  const WsLayout L = ws_layout(N, T, B, G);
   char* w = (char*)ws;
-  int* pcnt = (int*)(w + L.cnt);
-  int* pcls = (int*)(w + L.cls);
-  float* plp = (float*)(w + L.lp);
+  a = {dim3(N), st, T, C, blank, B, K, sizes, (float*)(w + L.lp), (int*)(w + L.cnt), (int*)(w + L.cls)};
+  if (T == 0) return 0;
   const int use_cut = cutoff_prob < 1.0f;
   const long frames = (long)N * T;
   hipLaunchKernelGGL(k_beam_prune, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, x, stride_n, stride_t, N, T, C, sizes, K,
-                     use_cut, (double)cutoff_prob, pcnt, pcls, plp);
+                     use_cut, (double)cutoff_prob, a.pcnt, a.pcls, a.plp);
   DS2_CHECK_LAUNCH();
-  if (hot && lm)
-    hipLaunchKernelGGL((k_beam_search<true, LmArgs, HotArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls,
-                       plp, (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *lm, *hot);
-  else if (hot)
-    hipLaunchKernelGGL((k_beam_search<false, HotArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls, plp,
-                       (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *hot);
-  else if (lm && alphas) {
-    const GridArgs grid = {alphas, betas, L.pool / 4};
-    hipLaunchKernelGGL((k_beam_search<true, LmArgs, GridArgs>), dim3(N, G), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt,
-                       pcls, plp, (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *lm,
-                       grid);
-  } else if (lm)
-    hipLaunchKernelGGL((k_beam_search<true, LmArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls, plp,
-                       (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores, *lm);
-  else
-    hipLaunchKernelGGL((k_beam_search<false>), dim3(N), dim3(BEAM_THREADS), 0, st, T, C, sizes, blank, B, K, pcnt, pcls, plp,
-                       (int*)(w + L.parent), (int*)(w + L.label), (int*)(w + L.frame), tokens, offsets, lens, scores);
+  return 0;
+}
+
+template <bool LM, class... Extra>
+void launch_search(const SearchArgs& a, const Extra&... extra) {
+  hipLaunchKernelGGL((k_beam_search<LM, Extra...>), a.grid, dim3(BEAM_THREADS), 0, a.st, a.T, a.C, a.sizes, a.blank, a.B, a.K, a.pcnt,
+                     a.pcls, a.plp, a.parent, a.label, a.frame, a.tokens, a.offsets, a.lens, a.scores, extra...);
+}
+
+// The search with the language model and the hot words that are given.  tail: nothing, or the StreamArgs.  grid: null, or the points
+// of ds2_beam_decode_lm_grid, which has a language model, no hot words and no tail.
+template <class... Tail>
+void launch_search_with(const SearchArgs& a, const LmArgs* lm, const HotArgs* hot, const GridArgs* grid, const Tail&... tail) {
+  if (hot)
+    lm ? launch_search<true>(a, *lm, *hot, tail...) : launch_search<false>(a, *hot, tail...);
+  else if (grid) {
+    if constexpr (sizeof...(Tail) == 0) launch_search<true>(a, *lm, *grid);
+  } else
+    lm ? launch_search<true>(a, *lm, tail...) : launch_search<false>(a, tail...);
+}
+
+int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
+                const LmArgs* lm, int G, const float* alphas, const float* betas, const HotArgs* hot) {
+  DS2_REQUIRE(x && tokens && (offsets || alphas) && lens && scores && ws, DS2_ERR_ARG);
+  DS2_REQUIRE(((uintptr_t)ws & 255) == 0, DS2_ERR_ALIGN);
+  const WsLayout L = ws_layout(N, T, B, G);
+  SearchArgs a;
+  const int rc = beam_prune(a, x, stride_n, stride_t, N, T, 1, C, sizes, blank, B, cutoff_top_n, cutoff_prob, ws, L, st);
+  if (rc) return rc;
+  char* w = (char*)ws;
+  a.parent = (int*)(w + L.parent), a.label = (int*)(w + L.label), a.frame = (int*)(w + L.frame);
+  a.tokens = tokens, a.offsets = offsets, a.lens = lens, a.scores = scores;
+  const GridArgs grid = {alphas, betas, L.pool / 4};
+  a.grid.y = G;      // the grid form: G x N workgroups
+  launch_search_with(a, lm, hot, alphas ? &grid : nullptr);
   DS2_CHECK_LAUNCH();
   return 0;
 }
@@ -1354,46 +1378,21 @@ int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int 
 int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
                      int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets, long row_stride,
                      int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm, const HotArgs* hot) {
-  DS2_REQUIRE(N > 0 && Tc >= 0 && C > 0 && C <= BEAM_MAXC && blank >= 0 && blank < C, DS2_ERR_ARG);
-  DS2_REQUIRE(B >= 1 && B <= BEAM_MAXB && cutoff_top_n >= 1, DS2_ERR_ARG);
-  const int K = cutoff_top_n < C ? cutoff_top_n : C;
-  DS2_REQUIRE(K <= BEAM_MAXK, DS2_ERR_ARG);
   DS2_REQUIRE(state && max_frames > 0 && ((long)max_frames + 1) * B <= 0x7fffffffl, DS2_ERR_ARG);
   const bool out = tokens != nullptr;
   DS2_REQUIRE(out == (offsets != nullptr) && out == (lens != nullptr) && out == (scores != nullptr), DS2_ERR_ARG);
   DS2_REQUIRE(!out || (row_stride >= 0 && out_ranks >= 1 && out_ranks <= B), DS2_ERR_ARG);
   DS2_REQUIRE(Tc > 0 ? (x && ws) : out, DS2_ERR_ARG);
   DS2_REQUIRE((((uintptr_t)ws | (uintptr_t)state) & 255) == 0, DS2_ERR_ALIGN);
+  SearchArgs a;
+  const int rc = beam_prune(a, x, stride_n, stride_t, N, Tc, 0, C, sizes, blank, B, cutoff_top_n, cutoff_prob, ws,
+                            stream_ws_layout(N, Tc), st);
+  if (rc) return rc;
   const StreamLayout SL = stream_layout(N, B, max_frames, (lm ? kStreamFlagLm : 0) | (hot ? kStreamFlagHot : 0));
-  const WsLayout L = stream_ws_layout(N, Tc);
-  char* w = (char*)ws;
   char* sb = (char*)state;
-  int* pcnt = (int*)(w + L.cnt);
-  int* pcls = (int*)(w + L.cls);
-  float* plp = (float*)(w + L.lp);
-  if (Tc > 0) {
-    const int use_cut = cutoff_prob < 1.0f;
-    const long frames = (long)N * Tc;
-    hipLaunchKernelGGL(k_beam_prune, dim3((unsigned)((frames + 3) / 4)), dim3(256), 0, st, x, stride_n, stride_t, N, Tc, C, sizes, K,
-                       use_cut, (double)cutoff_prob, pcnt, pcls, plp);
-    DS2_CHECK_LAUNCH();
-  }
-  const StreamArgs SA = {sb, SL.state_stride, max_frames, row_stride, out_ranks};
-  if (hot && lm)
-    hipLaunchKernelGGL((k_beam_search<true, LmArgs, HotArgs, StreamArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, Tc, C, sizes, blank, B, K,
-                       pcnt, pcls, plp, (int*)(sb + SL.parent), (int*)(sb + SL.label), (int*)(sb + SL.frame), tokens, offsets, lens,
-                       scores, *lm, *hot, SA);
-  else if (hot)
-    hipLaunchKernelGGL((k_beam_search<false, HotArgs, StreamArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, Tc, C, sizes, blank, B, K, pcnt,
-                       pcls, plp, (int*)(sb + SL.parent), (int*)(sb + SL.label), (int*)(sb + SL.frame), tokens, offsets, lens, scores,
-                       *hot, SA);
-  else if (lm)
-    hipLaunchKernelGGL((k_beam_search<true, LmArgs, StreamArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, Tc, C, sizes, blank, B, K, pcnt,
-                       pcls, plp, (int*)(sb + SL.parent), (int*)(sb + SL.label), (int*)(sb + SL.frame), tokens, offsets, lens, scores,
-                       *lm, SA);
-  else
-    hipLaunchKernelGGL((k_beam_search<false, StreamArgs>), dim3(N), dim3(BEAM_THREADS), 0, st, Tc, C, sizes, blank, B, K, pcnt, pcls,
-                       plp, (int*)(sb + SL.parent), (int*)(sb + SL.label), (int*)(sb + SL.frame), tokens, offsets, lens, scores, SA);
+  a.parent = (int*)(sb + SL.parent), a.label = (int*)(sb + SL.label), a.frame = (int*)(sb + SL.frame);
+  a.tokens = tokens, a.offsets = offsets, a.lens = lens, a.scores = scores;
+  launch_search_with(a, lm, hot, nullptr, StreamArgs{sb, SL.state_stride, max_frames, row_stride, out_ranks});
   DS2_CHECK_LAUNCH();
   return 0;
 }

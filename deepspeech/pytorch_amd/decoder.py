@@ -435,6 +435,11 @@ class BeamCTCDecoder:
             self._hot_dev[device] = torch.from_numpy(self._hot_host).to(device)
         return self._hot_dev[device]
 
+    def _hot_args(self, device):
+        """The hot dict of ops.beam_search / ops.beam_stream_open for `device`, None without hot words."""
+        ht = self._hot_table(device)
+        return None if ht is None else dict(space=self.space_index, table=ht, oov_logp=self.hot_oov_logp)
+
     def decode_beams(self, probs, sizes=None):
         """(strings, offsets, scores): strings[n] = beam_width transcripts (best first), offsets[n] = the matching int tensors of
         frames, scores = host (N, beam_width) float tensor of -log p, with an LM -(log p + lm) (lower is better; +inf where no
@@ -449,25 +454,23 @@ class BeamCTCDecoder:
             self._tables[device] = (torch.from_numpy(wt).to(device), torch.from_numpy(gt).to(device))
         return self._tables[device]
 
+    def _lm_args(self, device):
+        """The lm dict of ops.beam_search / ops.beam_stream_open for `device`, None without a language model."""
+        if self.lm is None:
+            return None
+        wt, gt = self._lm_tables(device)
+        return dict(space=self.space_index, word_table=wt, ngram_table=gt, order=self.lm.order, bos=self.lm.bos, alpha=self.alpha,
+                    beta=self.beta, lexicon=self.lexicon)
+
     def _search(self, probs, sizes, words=None):
         """The one-shot search in the form this decoder is set up for (plain, hot words, LM, LM with hot words); words: the
         settings of ops' confidence pass for decode_words, None for the plain results."""
-        ht = self._hot_table(probs.device)
-        if self.lm is None and ht is not None:
+        lm, hot = self._lm_args(probs.device), self._hot_args(probs.device)
+        if lm is None and hot is not None:      # by its own name: test_gpu_beam_hot counts the calls of ops.beam_decode_hot
             return ops.beam_decode_hot(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
-                                       self.space_index, ht, _words=words)
-        if self.lm is None:
-            res = ops.beam_decode(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
-                                  _words=words)
-            return res if words is not None else res + (res[2],)
-        wt, gt = self._lm_tables(probs.device)
-        if ht is not None:
-            return ops.beam_decode_lm_hot(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
-                                          self.space_index, wt, gt, self.lm.order, self.lm.bos, self.alpha, self.beta, self.lexicon,
-                                          ht, self.hot_oov_logp, _words=words)
-        return ops.beam_decode_lm(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
-                                  self.space_index, wt, gt, self.lm.order, self.lm.bos, self.alpha, self.beta, self.lexicon,
-                                  _words=words)
+                                       hot["space"], hot["table"], _words=words)
+        return ops.beam_search(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob, lm, hot,
+                               _words=words)
 
     def decode_beams_detailed(self, probs, sizes=None):
         """(strings, offsets, scores, acoustic): decode_beams' three values and the acoustic -log p of the same beams.  With an
@@ -520,10 +523,10 @@ class BeamCTCDecoder:
             raise ValueError("decode_grid needs at least one (alpha, beta) point")
         if not probs.is_cuda:
             probs = probs.to("cuda")
-        wt, gt = self._lm_tables(probs.device)
+        lm = self._lm_args(probs.device)
         return ops.beam_decode_lm_grid(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
-                                       self.space_index, wt, gt, self.lm.order, self.lm.bos, [a for a, _ in points],
-                                       [b for _, b in points], self.lexicon, max_ws_bytes)
+                                       lm["space"], lm["word_table"], lm["ngram_table"], lm["order"], lm["bos"],
+                                       [a for a, _ in points], [b for _, b in points], lm["lexicon"], max_ws_bytes)
 
     def decode_grid(self, probs, sizes, points):
         """decode's best transcript at every (alpha, beta) of `points`, from one launch: strings[g][n], offsets[g][n] (int tensor
@@ -568,16 +571,8 @@ class BeamStream:
         self.num_streams, self.max_frames = int(num_streams), int(max_frames)
         self.confidence, self._wc = _conf_settings(decoder, confidence)
         dev = torch.empty(0, device=device).device
-        lm = None
-        if d.lm is not None:
-            wt, gt = d._lm_tables(dev)
-            lm = dict(space=d.space_index, word_table=wt, ngram_table=gt, order=d.lm.order, bos=d.lm.bos, alpha=d.alpha,
-                      beta=d.beta, lexicon=d.lexicon)
-        ht, hot = d._hot_table(dev), None
-        if ht is not None:
-            hot = dict(space=d.space_index, table=ht, oov_logp=d.hot_oov_logp)
         self._h = ops.beam_stream_open(self.num_streams, self.max_frames, len(d.labels), d.blank_index, d.beam_width,
-                                       d.cutoff_top_n, d.cutoff_prob, dev, lm, hot)
+                                       d.cutoff_top_n, d.cutoff_prob, dev, d._lm_args(dev), d._hot_args(dev))
         self.frames = [0] * self.num_streams
         self._store = None
         if confidence is not None:

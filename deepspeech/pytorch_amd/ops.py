@@ -903,10 +903,7 @@ def softmax_rows(logits, Cc):
 def greedy_decode(scores, sizes, blank, _words=None):
     """scores: (N, T', C) f32 CUDA tensor (any strides with a contiguous class dimension); sizes: [N] int tensor.
     Returns host lists (tokens per sample, frame offsets per sample) -- reference decoder.py:164-181."""
-    if scores.dtype != torch.float32:
-        scores = scores.float()
-    if scores.stride(2) != 1:
-        scores = scores.contiguous()
+    scores = _f32_classes(scores)
     N, T, Cc = scores.shape
     dev = scores.device
     sz = sizes.to(dev, torch.int32) if sizes is not None else None
@@ -916,6 +913,12 @@ def greedy_decode(scores, sizes, blank, _words=None):
          S())
     if _words is not None:       # decode_words: the confidence pass reads the device buffers before anything travels
         return _words_to_host(scores, sz, buf[0][:, None], buf[1][:, None], counts[:, None], blank, _words, _words["kind"])
+    return _greedy_to_host(buf, counts)
+
+
+def _greedy_to_host(buf, counts):
+    """host lists (labels per sample, their frames per sample) from a greedy decode's buf (2, N, T) and counts [N]"""
+    N = counts.shape[0]
     cnt = counts.cpu()
     width = int(cnt.max().item()) if N > 0 else 0
     host = buf[:, :, :max(width, 1)].cpu()           # only the surviving labels + offsets travel
@@ -927,42 +930,41 @@ def greedy_decode(scores, sizes, blank, _words=None):
 BEAM_MAX_WIDTH, BEAM_MAX_TOP_N, BEAM_MAX_CLASSES = 256, 64, 8192     # ds2_beam_decode's limits
 
 
+BEAM_LM_MAX_ORDER = 5
+
+
+def beam_search(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm=None, hot=None, _words=None):
+    """CTC prefix beam search (ds2_beam_decode and its _lm, _hot and _lm_hot forms): the one body of beam_decode, beam_decode_lm,
+    beam_decode_hot and beam_decode_lm_hot.  probs: (N, T', C) CUDA tensor of probabilities (any strides with a contiguous class
+    dimension); sizes: [N] int tensor or None (= T').  lm, hot: None, or the dicts that beam_stream_open takes.  Returns host
+    lists: tokens[n][b] (labels of beam b, best first), offsets[n][b] (int tensor of their frames), a host (N, B) float tensor of
+    scores (-log p less the LM's and the hot words' terms: the total that ranked the beams; +inf where fewer than B beams are
+    alive) and one of the acoustic -log p of the same beams, which with neither an LM nor hot words is scores.  Only the
+    surviving labels, their frames and the scores travel."""
+    N, T, Cc = probs.shape
+    B, top_n, lm, hot = _beam_settings(Cc, probs.device, beam_width, cutoff_top_n, blank, lm, hot)
+    if N == 0 or T == 0:
+        return _beam_no_frames(N, B)
+    probs = _f32_classes(probs)
+    dev = probs.device
+    sz = sizes.to(dev, torch.int32) if sizes is not None else None
+    buf, lens, scores = _beam_outputs(N, B, T, dev)
+    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
+    _beam_launch(probs, sz, blank, B, top_n, cutoff_prob, lm, hot, buf, lens, scores, ws)
+    plain = lm is None and hot is None
+    if _words is not None:
+        sc = scores[:1 if plain else 2].cpu()
+        return _words_to_host(probs, sz, buf[0], buf[1], lens, blank, _words) + (sc[0], sc[-1])
+    return _beam_to_host(buf, lens, scores, N, B, plain=plain)
+
+
 def beam_decode(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, _words=None):
     """CTC prefix beam search without a language model (ds2_beam_decode).  probs: (N, T', C) CUDA tensor of probabilities (any
     strides with a contiguous class dimension); sizes: [N] int tensor or None (= T').  Returns host lists: tokens[n][b] (labels
     of beam b, best first), offsets[n][b] (int tensor of their frames) and a host (N, B) float tensor of scores (-log p, ctcdecode's
     convention; +inf where fewer than B beams are alive).  Only the surviving labels, their frames and the scores travel."""
-    N, T, Cc = probs.shape
-    B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
-    if N == 0 or T == 0:             # no frames: the only beam is the empty string, score 0
-        scores = torch.full((N, B), float("inf"))
-        scores[:, 0] = 0.0
-        return [[[] for _ in range(B)] for _ in range(N)], \
-            [[torch.zeros(0, dtype=torch.int32) for _ in range(B)] for _ in range(N)], scores
-    if probs.dtype != torch.float32:
-        probs = probs.float()
-    if probs.stride(2) != 1:
-        probs = probs.contiguous()
-    dev = probs.device
-    sz = sizes.to(dev, torch.int32) if sizes is not None else None
-    buf = torch.empty((2, N, B, T), dtype=torch.int32, device=dev)
-    lens = torch.empty((N, B), dtype=torch.int32, device=dev)
-    scores = torch.empty((N, B), dtype=torch.float32, device=dev)
-    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
-    call("ds2_beam_decode", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob),
-         P(buf[0]), P(buf[1]), P(lens), P(scores), P(ws), S())
-    if _words is not None:
-        sc = scores.cpu()
-        return _words_to_host(probs, sz, buf[0], buf[1], lens, blank, _words) + (sc, sc)
-    ln = lens.cpu().numpy()
-    width = max(int(ln.max()), 1)
-    host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
-    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(B)] for n in range(N)]
-    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(B)] for n in range(N)]
-    return toks, offs, scores.cpu()
-
-
-BEAM_LM_MAX_ORDER = 5
+    res = beam_search(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, _words=_words)
+    return res if len(res) == 5 else res[:3]         # five: the values of the _words pass, which end in scores and acoustic
 
 
 def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, word_table, ngram_table, order, bos,
@@ -971,67 +973,146 @@ def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, s
     label, the two tables of lm.build_tables as int64 CUDA tensors of shape (slots, 2) on the device of probs, the LM's order,
     the id of <s>, alpha, beta and the lexicon flag.  Returns beam_decode's three values, scores being -(log p + lm), and a host
     (N, B) float tensor of the acoustic -log p of the same beams."""
-    B, top_n = _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos)
-    N, T, Cc = probs.shape
-    if N == 0 or T == 0:             # no frames: the only beam is the empty string, score 0
-        scores = torch.full((N, B), float("inf"))
-        scores[:, 0] = 0.0
-        return [[[] for _ in range(B)] for _ in range(N)], \
-            [[torch.zeros(0, dtype=torch.int32) for _ in range(B)] for _ in range(N)], scores, scores.clone()
-    if probs.dtype != torch.float32:
-        probs = probs.float()
-    if probs.stride(2) != 1:
-        probs = probs.contiguous()
-    dev = probs.device
-    sz = sizes.to(dev, torch.int32) if sizes is not None else None
-    buf = torch.empty((2, N, B, T), dtype=torch.int32, device=dev)
-    lens = torch.empty((N, B), dtype=torch.int32, device=dev)
-    scores = torch.empty((2, N, B), dtype=torch.float32, device=dev)
-    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
-    call("ds2_beam_decode_lm", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob),
-         int(space), P(word_table), word_table.shape[0], P(ngram_table), ngram_table.shape[0], int(order), int(bos), float(alpha),
-         float(beta), int(bool(lexicon)), P(buf[0]), P(buf[1]), P(lens), P(scores[0]), P(scores[1]), P(ws), S())
-    if _words is not None:
-        sc = scores.cpu()
-        return _words_to_host(probs, sz, buf[0], buf[1], lens, blank, _words) + (sc[0], sc[1])
-    ln = lens.cpu().numpy()
-    width = max(int(ln.max()), 1)
-    host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
-    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(B)] for n in range(N)]
-    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(B)] for n in range(N)]
-    sc = scores.cpu()
-    return toks, offs, sc[0], sc[1]
+    lm = dict(space=space, word_table=word_table, ngram_table=ngram_table, order=order, bos=bos, alpha=alpha, beta=beta,
+              lexicon=lexicon)
+    return beam_search(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm, _words=_words)
+
+
+def beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, hot_table, _words=None):
+    """beam_decode with hot words (ds2_beam_decode_hot).  space: the space label; hot_table: the table of hotwords.build_table
+    as an int64 CUDA tensor of shape (slots, 2) on the device of probs.  Returns beam_decode's three values, scores being
+    -(log p + hot_end), the total that ranked the beams, and a host (N, B) float tensor of the acoustic -log p of the same beams."""
+    return beam_search(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, None, dict(space=space, table=hot_table),
+                       _words=_words)
+
+
+def beam_decode_lm_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, word_table, ngram_table, order, bos,
+                       alpha, beta, lexicon, hot_table, hot_oov_logp, _words=None):
+    """beam_decode_lm with hot words (ds2_beam_decode_lm_hot): its arguments, the table of hotwords.build_table and the ln P that a
+    covered out-of-vocabulary word event is charged.  Returns beam_decode_lm's four values, scores being -((log p + lm) + hot_end)."""
+    lm = dict(space=space, word_table=word_table, ngram_table=ngram_table, order=order, bos=bos, alpha=alpha, beta=beta,
+              lexicon=lexicon)
+    return beam_search(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm,
+                       dict(space=space, table=hot_table, oov_logp=hot_oov_logp), _words=_words)
+
+
+def _f32_classes(x):
+    """x (N, T, C) as the decode kernels read it: float32 with a contiguous class dimension; copies only where it has to"""
+    if x.dtype != torch.float32:
+        x = x.float()
+    if x.stride(2) != 1:
+        x = x.contiguous()
+    return x
+
+
+def _space_check(Cc, blank, space):
+    if not 0 <= space < Cc or space == blank:
+        raise ValueError("space label %d must be one of the %d classes and differ from the blank (%d)" % (space, Cc, blank))
+
+
+def _table_check(name, t, device):
+    """The checks of an open-addressing table (word_table, ngram_table, hot_table) for a search on `device`."""
+    if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous()):
+        raise ValueError("%s must be a contiguous int64 tensor of shape (slots, 2)" % name)
+    if t.shape[0] < 2 or t.shape[0] & (t.shape[0] - 1):
+        raise ValueError("%s: the number of slots must be a power of two >= 2, got %d" % (name, t.shape[0]))
+    if t.device != device or not t.is_cuda:
+        raise ValueError("%s must live on the device of the probabilities (%s), not %s" % (name, device, t.device))
 
 
 def _hot_checks(Cc, device, blank, space, hot_table, hot_oov_logp=0.0):
     """The argument checks of the hot-word calls: the space label, the table of hotwords.build_table on `device`, hot_oov_logp."""
-    if not 0 <= space < Cc or space == blank:
-        raise ValueError("space label %d must be one of the %d classes and differ from the blank (%d)" % (space, Cc, blank))
-    t = hot_table
-    if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous()):
-        raise ValueError("hot_table must be a contiguous int64 tensor of shape (slots, 2)")
-    if t.shape[0] < 2 or t.shape[0] & (t.shape[0] - 1):
-        raise ValueError("hot_table: the number of slots must be a power of two >= 2, got %d" % t.shape[0])
-    if t.device != device or not t.is_cuda:
-        raise ValueError("hot_table must live on the device of the probabilities (%s), not %s" % (device, t.device))
+    _space_check(Cc, blank, space)
+    _table_check("hot_table", hot_table, device)
     v = float(hot_oov_logp)
     if v != v or v in (float("inf"), float("-inf")) or abs(v) > 3.4e38:
         raise ValueError("hot_oov_logp must be a finite fp32 value, got %r" % (hot_oov_logp,))
 
 
-def _beam_outputs(N, B, T, dev):
-    return (torch.empty((2, N, B, T), dtype=torch.int32, device=dev), torch.empty((N, B), dtype=torch.int32, device=dev),
-            torch.empty((2, N, B), dtype=torch.float32, device=dev))
+def _beam_lm_checks(Cc, device, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos):
+    """The argument checks of a search with a language model, for Cc classes on `device`, which is all that they look at of the
+    probabilities (beam_stream_open has none); returns (B, top_n)."""
+    B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
+    _space_check(Cc, blank, space)
+    if not 1 <= int(order) <= BEAM_LM_MAX_ORDER:
+        raise ValueError("language-model order must be in [1, %d], got %d" % (BEAM_LM_MAX_ORDER, order))
+    if bos < 0:
+        raise ValueError("the id of <s> must not be negative, got %d" % bos)
+    _table_check("word_table", word_table, device)
+    _table_check("ngram_table", ngram_table, device)
+    return B, top_n
 
 
-def _beam_to_host(buf, lens, scores, N, B):
+def _beam_settings(Cc, device, beam_width, cutoff_top_n, blank, lm, hot):
+    """The argument checks of beam_search and beam_stream_open, in their order: the search's own, the language model's, the hot
+    words'.  Returns (B, top_n, lm, hot), the dicts with every scalar as the C call takes it."""
+    if lm is None:
+        B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
+    else:
+        B, top_n = _beam_lm_checks(Cc, device, beam_width, cutoff_top_n, blank, lm["space"], lm["word_table"], lm["ngram_table"],
+                                   lm["order"], lm["bos"])
+        lm = dict(lm, space=int(lm["space"]), order=int(lm["order"]), bos=int(lm["bos"]), alpha=float(lm["alpha"]),
+                  beta=float(lm["beta"]), lexicon=bool(lm.get("lexicon", True)))
+    if hot is not None:
+        _hot_checks(Cc, device, blank, int(hot["space"]), hot["table"], hot.get("oov_logp", 0.0))
+        hot = dict(space=int(hot["space"]), table=hot["table"], oov_logp=float(hot.get("oov_logp", 0.0)))
+        if lm is not None and lm["space"] != hot["space"]:
+            raise ValueError("the language model and the hot words must name one space label, got %d and %d"
+                             % (lm["space"], hot["space"]))
+    return B, top_n, lm, hot
+
+
+# The C entries of the one-shot and of the resumable search, by (language model, hot words).  After the arguments that all share
+# come _lm_block, then _hot_block, then the entry's own state and outputs.
+_BEAM_ENTRIES = {(False, False): ("ds2_beam_decode", "ds2_beam_stream_feed"),
+                 (True, False): ("ds2_beam_decode_lm", "ds2_beam_stream_feed_lm"),
+                 (False, True): ("ds2_beam_decode_hot", "ds2_beam_stream_feed_hot"),
+                 (True, True): ("ds2_beam_decode_lm_hot", "ds2_beam_stream_feed_lm_hot")}
+
+
+def _lm_block(lm):
+    """the language model's arguments in the C order: space, word_table, slots, ngram_table, slots, order, bos, alpha, beta, lexicon"""
+    if lm is None:
+        return ()
+    wt, gt = lm["word_table"], lm["ngram_table"]
+    return (lm["space"], P(wt), wt.shape[0], P(gt), gt.shape[0], lm["order"], lm["bos"], lm["alpha"], lm["beta"], int(lm["lexicon"]))
+
+
+def _hot_block(lm, hot):
+    """the hot words' arguments in the C order: table, slots, oov_logp after a language model's block; space, table, slots alone"""
+    if hot is None:
+        return ()
+    table = (P(hot["table"]), hot["table"].shape[0])
+    return (hot["space"],) + table if lm is None else table + (hot["oov_logp"],)
+
+
+def _beam_launch(probs, sz, blank, B, top_n, cutoff_prob, lm, hot, buf, lens, scores, ws):
+    """the launch of beam_search on ready tensors (probs f32 with contiguous classes, the outputs of _beam_outputs, ws of
+    ds2_beam_ws_bytes) and checked settings; acoustic, scores[1], exists for every form but the plain one"""
+    N, T, Cc = probs.shape
+    acoustic = () if lm is None and hot is None else (P(scores[1]),)
+    call(_BEAM_ENTRIES[lm is not None, hot is not None][0], P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank),
+         B, top_n, float(cutoff_prob), *_lm_block(lm), *_hot_block(lm, hot), P(buf[0]), P(buf[1]), P(lens), P(scores[0]), *acoustic,
+         P(ws), S())
+
+
+def _beam_outputs(N, R, ld, dev):
+    """the device outputs of a search that keeps R ranks in rows of ld labels: buf (2, N, R, ld) int32 = tokens and offsets,
+    lens (N, R) int32, scores (2, N, R) f32 = ranking and acoustic (the plain form leaves the second plane unwritten)"""
+    return (torch.empty((2, N, R, ld), dtype=torch.int32, device=dev), torch.empty((N, R), dtype=torch.int32, device=dev),
+            torch.empty((2, N, R), dtype=torch.float32, device=dev))
+
+
+def _beam_to_host(buf, lens, scores, N, R, cap=None, plain=False):
+    """tokens, offsets, scores and acoustic on the host from _beam_outputs' tensors after a launch; cap: the rows' width where
+    a length can pass it; plain: there is no acoustic plane, and acoustic is scores"""
     ln = lens.cpu().numpy()
-    width = max(int(ln.max()), 1)
+    width = max(int(ln.max()), 1) if cap is None else min(max(int(ln.max()), 1), cap)
     host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
-    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(B)] for n in range(N)]
-    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(B)] for n in range(N)]
-    sc = scores.cpu()
-    return toks, offs, sc[0], sc[1]
+    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(R)] for n in range(N)]
+    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(R)] for n in range(N)]
+    sc = scores[:1 if plain else 2].cpu()
+    return toks, offs, sc[0], sc[-1]
 
 
 def _beam_no_frames(N, B):
@@ -1040,83 +1121,6 @@ def _beam_no_frames(N, B):
     scores[:, 0] = 0.0
     return [[[] for _ in range(B)] for _ in range(N)], \
         [[torch.zeros(0, dtype=torch.int32) for _ in range(B)] for _ in range(N)], scores, scores.clone()
-
-
-def beam_decode_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, hot_table, _words=None):
-    """beam_decode with hot words (ds2_beam_decode_hot).  space: the space label; hot_table: the table of hotwords.build_table
-    as an int64 CUDA tensor of shape (slots, 2) on the device of probs.  Returns beam_decode's three values, scores being
-    -(log p + hot_end), the total that ranked the beams, and a host (N, B) float tensor of the acoustic -log p of the same beams."""
-    N, T, Cc = probs.shape
-    B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
-    _hot_checks(Cc, probs.device, blank, int(space), hot_table)
-    if N == 0 or T == 0:
-        return _beam_no_frames(N, B)
-    if probs.dtype != torch.float32:
-        probs = probs.float()
-    if probs.stride(2) != 1:
-        probs = probs.contiguous()
-    dev = probs.device
-    sz = sizes.to(dev, torch.int32) if sizes is not None else None
-    buf, lens, scores = _beam_outputs(N, B, T, dev)
-    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
-    call("ds2_beam_decode_hot", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob),
-         int(space), P(hot_table), hot_table.shape[0], P(buf[0]), P(buf[1]), P(lens), P(scores[0]), P(scores[1]), P(ws), S())
-    if _words is not None:
-        sc = scores.cpu()
-        return _words_to_host(probs, sz, buf[0], buf[1], lens, blank, _words) + (sc[0], sc[1])
-    return _beam_to_host(buf, lens, scores, N, B)
-
-
-def beam_decode_lm_hot(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, space, word_table, ngram_table, order, bos,
-                       alpha, beta, lexicon, hot_table, hot_oov_logp, _words=None):
-    """beam_decode_lm with hot words (ds2_beam_decode_lm_hot): its arguments, the table of hotwords.build_table and the ln P that a
-    covered out-of-vocabulary word event is charged.  Returns beam_decode_lm's four values, scores being -((log p + lm) + hot_end)."""
-    B, top_n = _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos)
-    N, T, Cc = probs.shape
-    _hot_checks(Cc, probs.device, blank, int(space), hot_table, hot_oov_logp)
-    if N == 0 or T == 0:
-        return _beam_no_frames(N, B)
-    if probs.dtype != torch.float32:
-        probs = probs.float()
-    if probs.stride(2) != 1:
-        probs = probs.contiguous()
-    dev = probs.device
-    sz = sizes.to(dev, torch.int32) if sizes is not None else None
-    buf, lens, scores = _beam_outputs(N, B, T, dev)
-    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
-    call("ds2_beam_decode_lm_hot", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n,
-         float(cutoff_prob), int(space), P(word_table), word_table.shape[0], P(ngram_table), ngram_table.shape[0], int(order), int(bos),
-         float(alpha), float(beta), int(bool(lexicon)), P(hot_table), hot_table.shape[0], float(hot_oov_logp), P(buf[0]), P(buf[1]),
-         P(lens), P(scores[0]), P(scores[1]), P(ws), S())
-    if _words is not None:
-        sc = scores.cpu()
-        return _words_to_host(probs, sz, buf[0], buf[1], lens, blank, _words) + (sc[0], sc[1])
-    return _beam_to_host(buf, lens, scores, N, B)
-
-
-def _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos):
-    """The argument checks of beam_decode_lm, for its grid form; returns (B, top_n)."""
-    return _beam_lm_checks_for(probs.shape[2], probs.device, beam_width, cutoff_top_n, blank, space, word_table, ngram_table,
-                               order, bos)
-
-
-def _beam_lm_checks_for(Cc, device, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos):
-    """_beam_lm_checks for Cc classes on `device`, which is all that it looks at of the probabilities (beam_stream_open has none)"""
-    B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
-    if not 0 <= space < Cc or space == blank:
-        raise ValueError("space label %d must be one of the %d classes and differ from the blank (%d)" % (space, Cc, blank))
-    if not 1 <= int(order) <= BEAM_LM_MAX_ORDER:
-        raise ValueError("language-model order must be in [1, %d], got %d" % (BEAM_LM_MAX_ORDER, order))
-    if bos < 0:
-        raise ValueError("the id of <s> must not be negative, got %d" % bos)
-    for name, t in (("word_table", word_table), ("ngram_table", ngram_table)):
-        if not (torch.is_tensor(t) and t.dtype == torch.int64 and t.dim() == 2 and t.shape[1] == 2 and t.is_contiguous()):
-            raise ValueError("%s must be a contiguous int64 tensor of shape (slots, 2)" % name)
-        if t.shape[0] < 2 or t.shape[0] & (t.shape[0] - 1):
-            raise ValueError("%s: the number of slots must be a power of two >= 2, got %d" % (name, t.shape[0]))
-        if t.device != device or not t.is_cuda:
-            raise ValueError("%s must live on the device of the probabilities (%s), not %s" % (name, device, t.device))
-    return B, top_n
 
 
 BEAM_GRID_MAX_POINTS = 65535     # points of one ds2_beam_decode_lm_grid launch
@@ -1149,7 +1153,8 @@ def beam_decode_lm_grid(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_pr
     first lens[g, n] entries of a row are valid, the rest 0), lens [G, N] int32, scores [G, N] = -(log p + lm) and acoustic [G, N]
     f32; row (g, n) is rank 0 of beam_decode_lm(alpha=alphas[g], beta=betas[g]) bit for bit.  The grid is cut into chunks of
     points whose workspace fits max_ws_bytes (plan_grid_chunks); the cut does not change the result."""
-    B, top_n = _beam_lm_checks(probs, beam_width, cutoff_top_n, blank, space, word_table, ngram_table, order, bos)
+    B, top_n = _beam_lm_checks(probs.shape[2], probs.device, beam_width, cutoff_top_n, blank, space, word_table, ngram_table,
+                               order, bos)
     if not probs.is_cuda:
         raise ValueError("probs must be a HIP device tensor")
     N, T, Cc = probs.shape
@@ -1165,10 +1170,7 @@ def beam_decode_lm_grid(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_pr
         return buf[0], buf[1], lens, scores[0], scores[1]
     one = query("ds2_beam_grid_ws_bytes", 1, N, T, B)
     chunks = plan_grid_chunks(G, one, query("ds2_beam_grid_ws_bytes", 2, N, T, B) - one, max_ws_bytes)
-    if probs.dtype != torch.float32:
-        probs = probs.float()
-    if probs.stride(2) != 1:
-        probs = probs.contiguous()
+    probs = _f32_classes(probs)
     sz = sizes.to(dev, torch.int32) if sizes is not None else None
     ws = torch.empty(query("ds2_beam_grid_ws_bytes", max(c for _, c in chunks), N, T, B), dtype=torch.uint8, device=dev)
     for g0, cnt in chunks:
@@ -1203,19 +1205,7 @@ def beam_stream_open(num_streams, max_frames, num_classes, blank, beam_width, cu
         raise ValueError("a beam stream lives on a HIP device, not on %s" % dev)
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
-    if lm is None:
-        B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
-    else:
-        B, top_n = _beam_lm_checks_for(Cc, dev, beam_width, cutoff_top_n, blank, lm["space"], lm["word_table"], lm["ngram_table"],
-                                       lm["order"], lm["bos"])
-        lm = dict(lm, space=int(lm["space"]), order=int(lm["order"]), bos=int(lm["bos"]), alpha=float(lm["alpha"]),
-                  beta=float(lm["beta"]), lexicon=bool(lm.get("lexicon", True)))
-    if hot is not None:
-        hot = dict(space=int(hot["space"]), table=hot["table"], oov_logp=float(hot.get("oov_logp", 0.0)))
-        _hot_checks(Cc, dev, blank, hot["space"], hot["table"], hot["oov_logp"])
-        if lm is not None and lm["space"] != hot["space"]:
-            raise ValueError("the language model and the hot words must name one space label, got %d and %d"
-                             % (lm["space"], hot["space"]))
+    B, top_n, lm, hot = _beam_settings(Cc, dev, beam_width, cutoff_top_n, blank, lm, hot)
     if (F + 1) * B > 2 ** 31 - 1:
         raise ValueError("max_frames=%d with beam_width=%d passes the node pool's 2^31 - 1 slots per stream" % (F, B))
     flags = int(lm is not None) | (2 if hot is not None else 0)      # the flag word of the ds2_beam_stream_* size queries
@@ -1244,66 +1234,36 @@ def _beam_checks(Cc, beam_width, cutoff_top_n, blank):
 
 def beam_stream_reset(h, streams=None):
     """Streams `streams` (indices; None = all) start again from the empty beam; the others are untouched."""
-    mask = None
-    if streams is not None:
-        m = torch.zeros(h.N, dtype=torch.int32)
-        for n in streams:
-            if not 0 <= int(n) < h.N:
-                raise ValueError("stream index %d out of range for %d streams" % (int(n), h.N))
-            m[int(n)] = 1
-        mask = m.to(h.device)
-    call("ds2_beam_stream_reset", P(h.state), h.N, h.B, h.max_frames, h.flags, P(mask), S())
+    call("ds2_beam_stream_reset", P(h.state), h.N, h.B, h.max_frames, h.flags, P(_stream_mask(streams, h.N, h.device)), S())
 
 
 def _beam_stream_call(h, probs, Tc, sz, row_stride, top_only=False):
     """one ds2_beam_stream_feed(_lm) call: a chunk (or none, Tc == 0), with the output stage when row_stride is given; the device
     writes, and the call allocates and copies, R = 1 rank with top_only and all B otherwise"""
-    dev, N, B = h.device, h.N, h.B
-    R = 1 if top_only else B
+    R = 1 if top_only else h.B
     buf = lens = scores = None
     if row_stride is not None:
         row_stride = max(int(row_stride), 1)
-        buf = torch.empty((2, N, R, row_stride), dtype=torch.int32, device=dev)
-        lens = torch.empty((N, R), dtype=torch.int32, device=dev)
-        scores = torch.empty((2, N, R), dtype=torch.float32, device=dev)
+        buf, lens, scores = _beam_outputs(h.N, R, row_stride, h.device)
     _beam_stream_launch(h, probs, Tc, sz, buf, lens, scores, row_stride, R)
     if buf is None:
         return None
-    ln = lens.cpu().numpy()
-    width = min(max(int(ln.max()), 1), row_stride)
-    host = buf[:, :, :, :width].cpu().numpy()        # only the surviving labels + offsets travel
-    toks = [[host[0, n, b, :ln[n, b]].tolist() for b in range(R)] for n in range(N)]
-    offs = [[torch.from_numpy(host[1, n, b, :ln[n, b]]) for b in range(R)] for n in range(N)]
-    sc = scores.cpu()
-    return (toks, offs, sc[0]) if h.lm is None and h.hot is None else (toks, offs, sc[0], sc[1])
+    plain = h.lm is None and h.hot is None
+    res = _beam_to_host(buf, lens, scores, h.N, R, row_stride, plain)
+    return res[:3] if plain else res
 
 
 def _beam_stream_launch(h, probs, Tc, sz, buf, lens, scores, row_stride, R):
-    """the launches of _beam_stream_call on the caller's output tensors (buf (2, N, R, row_stride) int32, lens (N, R) int32, scores
-    (2, N, R) f32: ranking and acoustic), or without the output stage (buf None); nothing is fetched"""
-    dev, N, B = h.device, h.N, h.B
-    ws = torch.empty(query("ds2_beam_stream_ws_bytes", N, Tc), dtype=torch.uint8, device=dev) if Tc > 0 else None
+    """the launches of _beam_stream_call on the caller's output tensors (_beam_outputs(N, R, row_stride, ...)), or without the
+    output stage (buf None); nothing is fetched"""
+    ws = torch.empty(query("ds2_beam_stream_ws_bytes", h.N, Tc), dtype=torch.uint8, device=h.device) if Tc > 0 else None
     x = (P(probs), probs.stride(0), probs.stride(1)) if Tc > 0 else (P(None), 0, 0)
-    out = (P(buf[0]), P(buf[1]), row_stride, R, P(lens), P(scores[0])) if buf is not None else \
-        (P(None), P(None), 0, 0, P(None), P(None))
-    acoustic = P(scores[1]) if buf is not None else P(None)
-    if h.hot is not None and h.lm is None:
-        call("ds2_beam_stream_feed_hot", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, h.hot["space"], P(h.hot["table"]),
-             h.hot["table"].shape[0], P(h.state), h.max_frames, *out, acoustic, P(ws), S())
-    elif h.hot is not None:
-        L = h.lm
-        call("ds2_beam_stream_feed_lm_hot", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, L["space"], P(L["word_table"]),
-             L["word_table"].shape[0], P(L["ngram_table"]), L["ngram_table"].shape[0], L["order"], L["bos"], L["alpha"], L["beta"],
-             int(L["lexicon"]), P(h.hot["table"]), h.hot["table"].shape[0], h.hot["oov_logp"], P(h.state), h.max_frames, *out,
-             acoustic, P(ws), S())
-    elif h.lm is None:
-        call("ds2_beam_stream_feed", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, P(h.state), h.max_frames, *out,
-             P(ws), S())
-    else:
-        L = h.lm
-        call("ds2_beam_stream_feed_lm", *x, N, Tc, h.C, P(sz), h.blank, B, h.top_n, h.cutoff_prob, L["space"], P(L["word_table"]),
-             L["word_table"].shape[0], P(L["ngram_table"]), L["ngram_table"].shape[0], L["order"], L["bos"], L["alpha"], L["beta"],
-             int(L["lexicon"]), P(h.state), h.max_frames, *out, P(scores[1]) if buf is not None else P(None), P(ws), S())
+    out = (P(buf[0]), P(buf[1]), row_stride, R, P(lens), P(scores[0]), P(scores[1])) if buf is not None else \
+        (P(None), P(None), 0, 0, P(None), P(None), P(None))
+    if h.lm is None and h.hot is None:       # the plain entry has no acoustic output
+        out = out[:-1]
+    call(_BEAM_ENTRIES[h.lm is not None, h.hot is not None][1], *x, h.N, Tc, h.C, P(sz), h.blank, h.B, h.top_n, h.cutoff_prob,
+         *_lm_block(h.lm), *_hot_block(h.lm, h.hot), P(h.state), h.max_frames, *out, P(ws), S())
 
 
 def _sizes_to_device(sizes, dev):
@@ -1330,10 +1290,7 @@ def beam_stream_feed(h, probs, sizes=None, row_stride=None):
     Tc = probs.shape[1]
     if Tc == 0:
         return None if row_stride is None else beam_stream_result(h, row_stride)
-    if probs.dtype != torch.float32:
-        probs = probs.float()
-    if probs.stride(2) != 1:
-        probs = probs.contiguous()
+    probs = _f32_classes(probs)
     sz = _sizes_to_device(sizes, h.device)
     if sz is not None and sz.shape != (h.N,):
         raise ValueError("sizes must have one entry per stream (%d), got shape %s" % (h.N, tuple(sz.shape)))
@@ -1427,10 +1384,7 @@ def endpoint_feed(h, probs, sizes=None):
             and probs.shape[2] > h.blank):
         raise ValueError("a chunk for this endpointer has shape (%d, Tc >= 1, C > %d), got %s"
                          % (h.N, h.blank, tuple(probs.shape) if torch.is_tensor(probs) else type(probs).__name__))
-    if probs.dtype != torch.float32:
-        probs = probs.float()
-    if probs.stride(2) != 1:
-        probs = probs.contiguous()
+    probs = _f32_classes(probs)
     sz = _sizes_to_device(sizes, h.device)
     if sz is not None and sz.shape != (h.N,):
         raise ValueError("sizes must have one entry per stream (%d), got shape %s" % (h.N, tuple(sz.shape)))
@@ -1481,11 +1435,9 @@ def endpoint_sink_open(bh, ranks, row_stride, slots):
     dev = bh.device
     words = 4 + 3 * R + 2 * R * rs
     ring = torch.empty(query("ds2_endpoint_ring_bytes", N, K, R, rs) // 4, dtype=torch.int32, device=dev).view(N, K, words)
+    buf, lens, scores = _beam_outputs(N, R, rs, dev)
     return EndpointSink(N=N, ranks=R, row_stride=rs, slots=K, words=words, ring=ring,
-                        pending=torch.zeros(N, dtype=torch.int32, device=dev),
-                        buf=torch.empty((2, N, R, rs), dtype=torch.int32, device=dev),
-                        lens=torch.empty((N, R), dtype=torch.int32, device=dev),
-                        scores=torch.empty((2, N, R), dtype=torch.float32, device=dev),
+                        pending=torch.zeros(N, dtype=torch.int32, device=dev), buf=buf, lens=lens, scores=scores,
                         acoustic=bh.lm is not None or bh.hot is not None)
 
 
@@ -1495,10 +1447,7 @@ def endpoint_beam_feed(eh, bh, sink, probs, sizes=None):
     the beam feed of the frames up to the cut with the output stage into the sink's stage; ds2_endpoint_commit, which moves the
     ended streams' rows into their ring; ds2_beam_stream_reset with the events' reason row as its mask; and, for chunks of more
     than one frame, ds2_endpoint_gather, ds2_endpoint_feed and the beam feed again on the frames after the cut."""
-    if probs.dtype != torch.float32:
-        probs = probs.float()
-    if probs.stride(2) != 1:
-        probs = probs.contiguous()
+    probs = _f32_classes(probs)
     cut, rest, ev = endpoint_feed(eh, probs, sizes)
     _beam_stream_launch(bh, probs, probs.shape[1], cut, sink.buf, sink.lens, sink.scores, sink.row_stride, sink.ranks)
     _endpoint_commit(ev, sink)
@@ -1558,22 +1507,14 @@ def greedy_stream_feed(scores, sizes, blank, carry):
         raise ValueError("carry must be a contiguous (%d, 2) int32 tensor on the device" % N)
     if N == 0 or T == 0:
         return [[] for _ in range(N)], [torch.zeros(0, dtype=torch.int32) for _ in range(N)]
-    if scores.dtype != torch.float32:
-        scores = scores.float()
-    if scores.stride(2) != 1:
-        scores = scores.contiguous()
+    scores = _f32_classes(scores)
     dev = scores.device
     sz = _sizes_to_device(sizes, dev)
     buf = torch.empty((2, N, T), dtype=torch.int32, device=dev)
     counts = torch.empty(N, dtype=torch.int32, device=dev)
     call("ds2_greedy_stream_feed", P(scores), scores.stride(0), scores.stride(1), N, T, Cc, P(sz), blank, P(carry), P(buf[0]),
          P(buf[1]), P(counts), S())
-    cnt = counts.cpu()
-    width = int(cnt.max().item())
-    host = buf[:, :, :max(width, 1)].cpu()           # only the surviving labels + offsets travel
-    toks = [host[0, i, :int(cnt[i])].tolist() for i in range(N)]
-    offs = [host[1, i, :int(cnt[i])] for i in range(N)]
-    return toks, offs
+    return _greedy_to_host(buf, counts)
 
 
 ERROR_COUNTS_MAX_LEN = 4096      # ds2_error_counts: labels of one hypothesis or reference
@@ -2018,9 +1959,7 @@ def beam_stream_words(h, store, row_stride, wc, sizes=None, t0=None):
     N, B = h.N, h.B
     R = 1 if int(wc["nbest"]) == 1 else B
     row_stride = max(int(row_stride), 1)
-    buf = torch.empty((2, N, R, row_stride), dtype=torch.int32, device=h.device)
-    lens = torch.empty((N, R), dtype=torch.int32, device=h.device)
-    scores = torch.empty((2, N, R), dtype=torch.float32, device=h.device)
+    buf, lens, scores = _beam_outputs(N, R, row_stride, h.device)
     _beam_stream_launch(h, None, 0, None, buf, lens, scores, row_stride, R)
     sc = scores.cpu()
     plain = h.lm is None and h.hot is None
