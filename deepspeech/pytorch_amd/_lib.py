@@ -105,6 +105,11 @@ SIGNATURES = {
     "ds2_resample_stream_state_bytes": (_l, [_i, _i]),
     "ds2_resample_stream_ws_bytes": (_l, [_i, _i]),
     "ds2_resample_stream_feed": (_i, [_vp, _l, _vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp, _vp, _l, _vp, _vp]),
+    "ds2_resample_classes": (_i, [_vp, _i, _vp, _vp]),
+    "ds2_resample_mixed": (_i, [_vp, _l, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _l, _vp, _vp]),
+    "ds2_resample_stream_state_bytes_mixed": (_l, [_i, _i]),
+    "ds2_resample_stream_ws_bytes_mixed": (_l, [_i, _i]),
+    "ds2_resample_stream_feed_mixed": (_i, [_vp, _l, _vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _l, _vp, _vp]),
     "ds2_greedy_decode":(_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "ds2_beam_ws_bytes": (_l, [_i, _i, _i]),
     "ds2_beam_decode": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp]),

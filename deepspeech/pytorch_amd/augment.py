@@ -104,6 +104,17 @@ def wsola_out_len(nsamples, tempo):
     return (S - 1) * WSOLA_ADVANCE + min(WSOLA_SEGMENT, int(nsamples) - wsola_start(S - 1, tempo))
 
 
+def speed_rate(rate, speed):
+    """The rate in Hz a clip recorded at `rate` is read at so that it plays `speed` times as fast: rate * speed, evaluated exactly
+    (the speed through its decimal string, 1.1 is 11 / 10).  Resampling from there to 16 kHz shortens the clip by `speed` and
+    moves pitch and formants with it.  Refuses a product that is not an integer number of Hz."""
+    import fractions
+    eff = fractions.Fraction(int(rate)) * fractions.Fraction(str(speed))
+    if eff.denominator != 1 or eff <= 0:
+        raise ValueError("rate %d Hz at speed %s is %s Hz: not a positive integer number of Hz" % (rate, speed, eff))
+    return int(eff)
+
+
 class NoiseBank:
     """The noise recordings of ``augmentation.noise_dir`` as ONE device buffer (fp32, back to back) with their offsets.  Reading
     audio files stays with the caller: hand the decoded mono waveforms (at the front-end's sample rate, on the [-1, 1] scale of
@@ -114,11 +125,27 @@ class NoiseBank:
         self.offsets = np.asarray(offsets, np.int64)             # [R + 1]: recording r = samples[offsets[r]:offsets[r + 1]]
 
     @classmethod
-    def from_waveforms(cls, waveforms, device="cuda"):
+    def from_waveforms(cls, waveforms, rates=None, device="cuda"):
+        """rates: the sample rate in Hz of each recording (None = all at 16 kHz already); recordings at other rates are converted
+        to 16 kHz once, here, on `device` in one launch (``resample.ResamplerBank``): offsets and lengths are those of the
+        converted recordings."""
         import torch
+        if isinstance(rates, (str, torch.device)):        # from_waveforms(waveforms, device), as before there were rates
+            rates, device = None, rates
         arrays = [np.ascontiguousarray(np.asarray(w, np.float32).reshape(-1)) for w in waveforms]
         if not arrays or any(a.size == 0 for a in arrays):
             raise ValueError("a noise bank needs at least one recording, and none of them empty")
+        if rates is not None and any(int(r) != 16000 for r in rates):
+            from .resample import ResamplerBank
+            rates = [int(r) for r in rates]
+            if len(rates) != len(arrays):
+                raise ValueError("rates has %d entries for %d recordings" % (len(rates), len(arrays)))
+            buf = torch.zeros((len(arrays), max(a.size for a in arrays)), dtype=torch.float32)
+            for i, a in enumerate(arrays):
+                buf[i, :a.size] = torch.from_numpy(a)
+            out, ns16 = ResamplerBank(sorted(set(rates)))(buf.to(device), [a.size for a in arrays], rates)
+            offsets = np.concatenate([[0], np.cumsum(ns16.numpy().astype(np.int64))])
+            return cls(torch.cat([out[i, :n] for i, n in enumerate(ns16.tolist())]), offsets)
         offsets = np.concatenate([[0], np.cumsum([a.size for a in arrays])])
         return cls(torch.from_numpy(np.concatenate(arrays)).to(device), offsets)
 
@@ -132,17 +159,20 @@ class NoiseBank:
 class WaveDraws:
     """One batch's draws of WaveAugment.  tempo / gain / level [N] float32 (None = that step is off for the batch; gain holds the
     LINEAR factor 10^(dB / 20), gain_db the drawn value), noise_off [N] int64 (-1 = no noise for the clip) and noise_start [N] int32
-    with level; nsamples [N] int64 = the sample counts after the tempo change, segments [N] = the clips' WSOLA segment counts."""
+    with level; nsamples [N] int64 = the sample counts after the tempo change, segments [N] = the clips' WSOLA segment counts.
+    With speed_choices: speed [N] float64 = the drawn factors, rates [N] int64 = the rates the clips are read at (rate * speed),
+    resampled [N] int64 = the sample counts at 16 kHz after that resampling, in front of the tempo change (None otherwise)."""
 
-    def __init__(self, tempo, gain, gain_db, level, noise_off, noise_start, nsamples, segments):
+    def __init__(self, tempo, gain, gain_db, level, noise_off, noise_start, nsamples, segments, speed=None, rates=None, resampled=None):
         self.tempo, self.gain, self.gain_db, self.level = tempo, gain, gain_db, level
         self.noise_off, self.noise_start, self.nsamples, self.segments = noise_off, noise_start, nsamples, segments
+        self.speed, self.rates, self.resampled = speed, rates, resampled
 
     def take(self, order):
         """the draws of the clips `order`, in that order."""
         pick = lambda a: None if a is None else a[np.asarray(order, np.int64)]      # noqa: E731
         return WaveDraws(*[pick(a) for a in (self.tempo, self.gain, self.gain_db, self.level, self.noise_off, self.noise_start,
-                                             self.nsamples, self.segments)])
+                                             self.nsamples, self.segments, self.speed, self.rates, self.resampled)])
 
     def arrays(self):
         """the arrays that go to the device, the 8-byte one first (SpectrogramFrontEnd.upload_draws keeps that order)."""
@@ -151,7 +181,14 @@ class WaveDraws:
 
 class WaveAugment:
     def __init__(self, speed_volume_perturb=False, tempo_range=(0.85, 1.15), gain_range=(-6, 8), noise_bank=None, noise_prob=0.4,
-                 noise_levels=(0.0, 0.5), sample_rate=16000):
+                 noise_levels=(0.0, 0.5), sample_rate=16000, speed_choices=None):
+        """speed_choices: None, or the factors of speed perturbation by resampling, (0.9, 1.0, 1.1) in the usual recipe: per clip one
+        is drawn uniformly -- the FIRST draw of the clip, and only when this is set, so every other configuration draws what it
+        drew -- and the clip is resampled as if recorded at rate * speed Hz (pitch and formants move, unlike the tempo change),
+        before tempo, gain and noise, which see the result.  The front-end does the resampling (``speed_rate``)."""
+        self.speed_choices = None if speed_choices is None else tuple(speed_choices)
+        if self.speed_choices is not None and (not self.speed_choices or any(not float(v) > 0.0 for v in self.speed_choices)):
+            raise ValueError("speed_choices must be None or positive factors, got %r" % (speed_choices,))
         self.speed_volume_perturb = bool(speed_volume_perturb)
         self.tempo_range, self.gain_range = tuple(tempo_range), tuple(gain_range)
         self.noise_bank, self.noise_prob, self.noise_levels = noise_bank, float(noise_prob), tuple(noise_levels)
@@ -172,16 +209,26 @@ class WaveAugment:
 
     @property
     def active(self):
-        return self.speed_volume_perturb or self.noise_bank is not None
+        return self.speed_volume_perturb or self.noise_bank is not None or bool(self.speed_choices)
 
-    def draw(self, nsamples, rng):
+    def draw(self, nsamples, rng, rates=None):
         """All draws of a batch on the host, from a numpy.random.Generator or RandomState, per clip in the reference's order:
         tempo and gain (load_randomly_augmented_audio, data_loader.py:398-401; both go to sox as '{:.3f}', :383, so they are rounded
         to three decimals here too), binomial(1, noise_prob) (:157), and for a clip that gets noise the recording (:114), the level
         (:115) and rand() for the start (:121: start = rand * (noise_len - data_len) seconds, truncated to samples here; data_len is
-        the length AFTER the tempo change).  A clip longer than its recording gets no noise.  Returns a WaveDraws."""
-        ns = np.asarray(nsamples, np.int64).reshape(-1)
+        the length AFTER the tempo change).  A clip longer than its recording gets no noise.  Returns a WaveDraws.
+        With speed_choices the clip's first draw is its speed, rng.choice(len(speed_choices)); nsamples then counts the samples
+        at `rates` (the rate of each clip, None = 16 kHz), and everything after sees ceil(n 16000 / (rate speed)) samples."""
+        ns = np.asarray(nsamples, np.int64).reshape(-1).copy()
         N, bank, sr = len(ns), self.noise_bank, float(self.sample_rate)
+        if rates is not None and not self.speed_choices:
+            raise ValueError("draw(rates=...) belongs to speed_choices: without them the clips come here at 16 kHz")
+        speed = eff = resampled = None
+        if self.speed_choices:
+            rates = [16000] * N if rates is None else list(rates)
+            if len(rates) != N:
+                raise ValueError("rates has %d entries for %d clips" % (len(rates), N))
+            speed, eff, resampled = np.ones(N, np.float64), np.zeros(N, np.int64), ns
         tempo = np.ones(N, np.float32) if self.speed_volume_perturb else None
         gain_db = np.zeros(N, np.float64) if self.speed_volume_perturb else None
         level = np.zeros(N, np.float32) if bank is not None else None
@@ -189,6 +236,10 @@ class WaveAugment:
         noise_start = np.zeros(N, np.int32) if bank is not None else None
         out_ns, segments = ns.copy(), np.zeros(N, np.int64)
         for n in range(N):
+            if self.speed_choices:
+                choice = self.speed_choices[int(rng.choice(len(self.speed_choices)))]
+                speed[n], eff[n] = choice, speed_rate(rates[n], choice)
+                ns[n] = out_ns[n] = -((-int(ns[n]) * 16000) // int(eff[n]))
             if self.speed_volume_perturb:
                 tempo[n] = float("%.3f" % rng.uniform(low=self.tempo_range[0], high=self.tempo_range[1]))
                 gain_db[n] = float("%.3f" % rng.uniform(low=self.gain_range[0], high=self.gain_range[1]))
@@ -203,4 +254,4 @@ class WaveAugment:
                 start = int(u * (noise_len / sr - data_len / sr) * sr)
                 level[n], noise_off[n], noise_start[n] = lv, bank.offsets[r], min(max(start, 0), noise_len - data_len)
         gain = np.power(10.0, gain_db / 20.0).astype(np.float32) if gain_db is not None else None
-        return WaveDraws(tempo, gain, gain_db, level, noise_off, noise_start, out_ns, segments)
+        return WaveDraws(tempo, gain, gain_db, level, noise_off, noise_start, out_ns, segments, speed, eff, resampled)

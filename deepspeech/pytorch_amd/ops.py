@@ -2084,6 +2084,39 @@ def resample_stream_feed(wav, rows, n_rows, max_new, max_emit, capacity, taps, u
     return out
 
 
+def resample_mixed(wav, nsamples, cls, classes, classes_dev, taps, ldo, out=None):
+    """Every clip of wav (N, Lmax) through the polyphase filter of ITS class, one launch: ds2_resample_mixed.  nsamples / cls: [N]
+    int32 on the device (sample counts, class per row); classes: the host's class table (int32 numpy, 10 words a class, as
+    ds2_resample_classes filled it), classes_dev / taps: the same table and the concatenated tap tables on the device.  Returns
+    (out (N, ldo), nsamples_out [N] int32), both on the device; entries of out beyond a clip's own outputs are zero."""
+    if not (torch.is_tensor(wav) and wav.is_cuda and wav.dim() == 2 and wav.dtype == torch.float32):
+        raise ValueError("the waveform kernels take a float32 HIP device batch of shape (N, Lmax)")
+    wav, N = wav.contiguous(), wav.shape[0]
+    for t, what in ((nsamples, "nsamples"), (cls, "cls")):
+        if not (t.is_cuda and t.dtype == torch.int32 and t.numel() == N and t.is_contiguous()):
+            raise ValueError("%s must be a contiguous int32 device tensor with one entry per clip" % what)
+    if out is None:
+        out = torch.empty((N, int(ldo)), dtype=torch.float32, device=wav.device)
+    if tuple(out.shape) != (N, int(ldo)) or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("out must be a contiguous float32 (N, ldo) tensor")
+    ns_out = torch.empty(N, dtype=torch.int32, device=wav.device)
+    call("ds2_resample_mixed", P(wav), wav.stride(0), P(nsamples), P(cls), N, C.c_void_p(classes.ctypes.data), P(classes_dev),
+         classes.size // 10, P(taps), P(out), int(ldo), P(ns_out), S())
+    return out, ns_out
+
+
+def resample_stream_feed_mixed(wav, rows, n_rows, max_new, max_emit, capacity, classes, classes_dev, taps, wmax, state):
+    """One feed of n_rows streams, each through the filter of its row's class: ds2_resample_stream_feed_mixed.  As
+    resample_stream_feed; the class travels in the row table, state = the carries [capacity][2 wmax]."""
+    dev = state.device
+    out = torch.empty((n_rows, int(max_emit)), dtype=torch.float32, device=dev)
+    ws = torch.empty(query("ds2_resample_stream_ws_bytes_mixed", n_rows, int(wmax)), dtype=torch.uint8, device=dev)
+    call("ds2_resample_stream_feed_mixed", P(wav) if max_new else P(None), wav.stride(0) if max_new else 0, P(rows), n_rows, int(max_new),
+         int(max_emit), int(capacity), C.c_void_p(classes.ctypes.data), P(classes_dev), classes.size // 10, P(taps), int(wmax), P(state),
+         P(out) if max_emit else P(None), int(max_emit), P(ws), S())
+    return out
+
+
 def _noise_args(N, dev, level, bank, noise_off, noise_start):
     lv = _per_clip(level, N, dev, torch.float32, "level")
     if lv is None:

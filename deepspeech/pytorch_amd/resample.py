@@ -8,15 +8,19 @@ the project's own windowed-sinc design, as the tempo change is the project's own
     every phase divided by its own sum, then rounded once to float32
     y[m] = sum_j h[p][j] x[n0 - W + 1 + j],  n0 = floor(m D / U),  p = (m D) mod U,  x = 0 outside the clip,  m < ceil(n U / D)
 
-The taps are built here in float64 and only here; the kernels take the table as an argument."""
+The taps are built here in float64 and only here; the kernels take the table as an argument.
+
+``ResamplerBank`` puts up to 16 such designs behind one launch, the rate belonging to the row: batches and pools that mix rates,
+speed perturbation by resampling (``augment.WaveAugment(speed_choices=...)``) and noise recordings at other rates go through it."""
 import collections
+import ctypes
 import math
 
 import numpy as np
 import torch
 
 from . import ops
-from ._lib import Ds2HipError, query
+from ._lib import Ds2HipError, call, query
 
 OUT_RATE = 16000
 MAX_TABLE_BYTES = 128 * 1024
@@ -198,6 +202,174 @@ class ResampleStream:
             rows = _ROW_STAGING.stage(self.device, [table.reshape(-1)])
             out = ops.resample_stream_feed(wav, rows, len(sl), max(ns), max(counts), S, rs.taps_on(self.device), rs.up, rs.down,
                                            rs.half_width, self._state)
+        for s, n in zip(sl, ns):
+            self.samples[s] += n
+            self.ended[s], self._fresh[s] = s in fin, False
+        return out, counts
+
+
+MAX_CLASSES = 16
+CLASS_WORDS = 10           # int32 words of one ds2_resample_class: U, D, W, nt, P, K, tile, cap, taps_off (2)
+
+
+class ResamplerBank:
+    """Up to 16 input rates behind one launch (ds2_resample_mixed; DESIGN.md section 7.2, "Mixed rates"): rate, half-width and tap
+    table belong to the row.  Class c is ``Resampler(rates[c])``'s design -- the same ``design_taps`` call, so the same bits -- and a
+    row of a mixed call equals that resampler's call on the clip alone, bit for bit.  16000 is the copy class: its rows ride in
+    the same launch and come out as they went in."""
+
+    def __init__(self, rates, zeros=24, rolloff=0.92, beta=9.0):
+        rates = list(rates)
+        if not rates or any(int(r) != r or int(r) <= 0 for r in rates):
+            raise ValueError("rates must be positive integer numbers of Hz, got %r" % (rates,))
+        rates = [int(r) for r in rates]
+        if len(set(rates)) != len(rates):
+            raise ValueError("rates must be distinct, got %r" % (rates,))
+        if len(rates) > MAX_CLASSES:
+            raise ValueError("a bank holds at most %d rates, got %d: %r" % (MAX_CLASSES, len(rates), rates))
+        self.rates = tuple(rates)
+        self.resamplers = [Resampler(r, zeros=zeros, rolloff=rolloff, beta=beta) for r in rates]   # refuses an oversized table, naming the rate
+        self.class_of = {r: c for c, r in enumerate(rates)}
+        self.half_width = max(rs.half_width for rs in self.resamplers)
+        C_ = len(rates)
+        udw = np.array([(rs.up, rs.down, rs.half_width) for rs in self.resamplers], dtype=np.int32)
+        self.classes = np.zeros(C_ * CLASS_WORDS, dtype=np.int32)
+        total = ctypes.c_long(0)
+        call("ds2_resample_classes", ctypes.c_void_p(udw.ctypes.data), C_, ctypes.c_void_p(self.classes.ctypes.data), ctypes.byref(total))
+        self.taps = np.concatenate([rs.taps.reshape(-1) for rs in self.resamplers]).astype(np.float32)
+        offs = self.classes.reshape(C_, CLASS_WORDS)[:, 8:10].copy().view(np.int64).reshape(-1)
+        assert self.taps.size == total.value and offs.tolist() == np.cumsum([0] + [rs.taps.size for rs in self.resamplers])[:-1].tolist()
+        self._dev = {}
+
+    def tile(self, rate):
+        """the consecutive outputs one workgroup of a one-shot launch computes for a row at `rate`"""
+        return int(self.classes.reshape(-1, CLASS_WORDS)[self._class(rate), 6])
+
+    def _class(self, rate):
+        c = self.class_of.get(int(rate)) if int(rate) == rate else None
+        if c is None:
+            raise ValueError("%r Hz is not a rate of this bank %r" % (rate, self.rates))
+        return c
+
+    def resampler(self, rate):
+        return self.resamplers[self._class(rate)]
+
+    def out_len(self, n, rate):
+        return self.resampler(rate).out_len(n)
+
+    def plan_resample(self, rate, samples_before, n_new, final=False):
+        return self.resampler(rate).plan_resample(samples_before, n_new, final)
+
+    def on(self, dev):
+        """(class table, taps) on `dev`, uploaded once per device"""
+        dev = torch.device(dev)
+        t = self._dev.get(dev)
+        if t is None:
+            t = self._dev[dev] = (torch.from_numpy(self.classes).to(dev), torch.from_numpy(self.taps).to(dev) if self.taps.size else None)
+        return t
+
+    def _run(self, wav, ns, rates):
+        """wav (N, Lmax) f32 on the device, ns [N] int32 on the host, rates: one of the bank per row, all checked by the caller ->
+        (wav16, its sample counts on the device, the same counts on the host in closed form).  One staged upload, one launch."""
+        cls = [self._class(r) for r in rates]
+        ns16 = torch.tensor([self.resamplers[c].out_len(v) for c, v in zip(cls, ns.tolist())], dtype=torch.int32)
+        N = len(cls)
+        up = _ROW_STAGING.stage(wav.device, [ns.numpy().astype(np.int32), np.asarray(cls, dtype=np.int32)])
+        classes_dev, taps = self.on(wav.device)
+        out, ns_dev = ops.resample_mixed(wav, up[:N], up[N:], self.classes, classes_dev, taps, int(ns16.max()))
+        return out, ns_dev, ns16
+
+    def __call__(self, wav, nsamples, rates):
+        """wav: [N][Lmax] float32 on a HIP device, nsamples: [N] ints >= 1, rates: [N] rates of the bank, the rate of each row.
+        Returns (wav16 (N, max out_len) on the device, zero beyond a clip's own samples; nsamples16 [N] int32 on the host)."""
+        if not wav.is_cuda:
+            raise Ds2HipError("ResamplerBank needs the waveforms on a HIP device; there is no CPU path")
+        ns = torch.as_tensor(nsamples, dtype=torch.int32).cpu().reshape(-1)
+        rates = list(rates)
+        if wav.dim() != 2 or ns.numel() != wav.shape[0] or len(rates) != wav.shape[0] or int(ns.min()) < 1:
+            raise ValueError("expected a [N][Lmax] waveform batch, one positive sample count and one rate per row")
+        if int(ns.max()) > wav.shape[1]:
+            raise ValueError("nsamples exceeds the waveform buffer")
+        out, _, ns16 = self._run(wav.float().contiguous(), ns, rates)
+        return out, ns16
+
+    def stream(self, capacity, device):
+        """A streaming handle over `capacity` slots, each at a rate of its own (``BankStream``)."""
+        return BankStream(self, capacity, device)
+
+
+class BankStream:
+    """The streaming form of a ``ResamplerBank`` (ds2_resample_stream_feed_mixed): ``ResampleStream`` with a rate per slot, given
+    by ``reset(slots, rates)`` for the stream that starts; slots at different rates advance in one feed."""
+
+    def __init__(self, bank, capacity, device):
+        if int(capacity) < 1:
+            raise ValueError("capacity must be >= 1, got %s" % (capacity,))
+        self.bank, self.capacity, self.device = bank, int(capacity), torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        S = self.capacity
+        self._wmax = max(bank.half_width, 1)
+        self._state = None              # the carries [S][2 Wmax] f32, allocated by the first feed
+        self.samples, self.ended, self._fresh, self.rates = [0] * S, [False] * S, [True] * S, [None] * S
+
+    def reset(self, slots=None, rates=None):
+        """These slots (None = all) start a new stream at rates[i] (one rate: all of them; None: the rate each had).  Their carry
+        reads as empty from the next feed on; nothing is launched."""
+        sl = list(range(self.capacity)) if slots is None else [int(v) for v in slots]
+        if rates is not None and not isinstance(rates, (list, tuple)):
+            rates = [rates] * len(sl)
+        if rates is not None and len(rates) != len(sl):
+            raise ValueError("reset: %d rates for %d slots" % (len(rates), len(sl)))
+        for s in sl:
+            if not 0 <= s < self.capacity:
+                raise ValueError("slot %d is not a slot of this stream (capacity %d)" % (s, self.capacity))
+        if rates is not None:
+            rates = [self.bank.rates[self.bank._class(r)] for r in rates]
+        for i, s in enumerate(sl):
+            self.samples[s], self.ended[s], self._fresh[s] = 0, False, True
+            if rates is not None:
+                self.rates[s] = rates[i]
+
+    def feed(self, slots, wav, nsamples, final=()):
+        """As ``ResampleStream.feed``; row i is at the rate of slots[i]."""
+        bank, S = self.bank, self.capacity
+        sl, fin = [int(s) for s in slots], set(int(s) for s in final)
+        if not sl or len(set(sl)) != len(sl) or any(not 0 <= s < S for s in sl):
+            raise ValueError("slots must be distinct and lie in [0, %d), got %s" % (S, sl))
+        if not fin <= set(sl):
+            raise ValueError("final names slots that are not in this feed: %s" % sorted(fin - set(sl)))
+        ns = [int(v) for v in nsamples]
+        if wav.dim() != 2 or wav.shape[0] != len(sl) or len(ns) != len(sl) or any(v < 0 or v > wav.shape[1] for v in ns):
+            raise ValueError("expected a [%d][L] waveform chunk and %d sample counts in [0, L], got %s and %s"
+                             % (len(sl), len(sl), tuple(wav.shape), ns))
+        for s in sl:
+            if self.rates[s] is None:
+                raise ValueError("slot %d has no rate yet: reset(slots, rates) gives it one" % s)
+            if self.ended[s]:
+                raise ValueError("the stream of slot %d has ended (a final feed); reset it first" % s)
+        if not wav.is_cuda or wav.device != self.device:
+            raise Ds2HipError("BankStream needs the waveforms on %s; there is no CPU path" % self.device)
+        wav = wav.float()
+        if wav.shape[1] and wav.stride(1) != 1:
+            wav = wav.contiguous()
+        cls = [bank.class_of[self.rates[s]] for s in sl]
+        plans = [bank.resamplers[c].plan_resample(self.samples[s], n, s in fin) for c, s, n in zip(cls, sl, ns)]
+        assert all(self.samples[s] == 0 for s in sl if self._fresh[s])
+        assert all(0 <= p.new_carry < max(2 * bank.resamplers[c].half_width, 1) for c, p in zip(cls, plans))
+        table = np.zeros((len(sl), RESAMPLE_ROW_WORDS), dtype=np.int32)
+        for i, (s, n, p, c) in enumerate(zip(sl, ns, plans, cls)):
+            copy = bank.resamplers[c].identity            # the copy class has no carry and counts no outputs before
+            table[i, :4] = (s, i, 0 if self._fresh[s] or copy else p.carried, n)
+            table[i, 4:6] = np.array([0 if copy else p.out_before], dtype=np.int64).view(np.int32)
+            table[i, 6:10] = (p.emit, int(s in fin), int(self._fresh[s]), c)
+        counts = [p.emit for p in plans]
+        if self._state is None:
+            self._state = torch.zeros(query("ds2_resample_stream_state_bytes_mixed", S, self._wmax), dtype=torch.uint8, device=self.device)
+        rows = _ROW_STAGING.stage(self.device, [table.reshape(-1)])
+        classes_dev, taps = bank.on(self.device)
+        out = ops.resample_stream_feed_mixed(wav, rows, len(sl), max(ns), max(counts), S, bank.classes, classes_dev, taps, self._wmax,
+                                             self._state)
         for s, n in zip(sl, ns):
             self.samples[s] += n
             self.ended[s], self._fresh[s] = s in fin, False

@@ -85,7 +85,12 @@ class SpectrogramFrontEnd:
         configuration asks for them; its draws come from rng too, before those of SpecAugment.  input_rate: the sample rate of
         the waveforms handed in, in Hz (None or 16000 = they are at 16 kHz already and nothing is added to any call); any other
         rate is converted to 16 kHz on the device first (``resample.Resampler``), and every count this class reports -- frames,
-        percentages, ``SpectStream.samples`` -- is one of the 16 kHz signal."""
+        percentages, ``SpectStream.samples`` -- is one of the 16 kHz signal.  A tuple or list of rates (``input_rate=(8000, 16000,
+        48000)``) is the SET of rates the clips may have: every call that takes waveforms then takes ``rates=[one per clip]``, and
+        the batch is converted in one launch whatever it mixes (``resample.ResamplerBank``).  A wave_augment with
+        ``speed_choices`` resamples too -- a clip at rate r drawn speed s is read as one recorded at r * s Hz -- so the front-end
+        then builds its bank from every rate x speed product and refuses a pair whose product is no integer number of Hz or
+        whose table does not fit."""
         sr = getattr(spect_cfg, "sample_rate", 16000)
         n_fft = int(sr * getattr(spect_cfg, "window_size", 0.02))
         hop = int(sr * getattr(spect_cfg, "window_stride", 0.01))
@@ -110,8 +115,29 @@ class SpectrogramFrontEnd:
         self.last_coef = None            # device [N][3]: the time-warp flow coefficients of the latest augmented call
         self.wave_augment = wave_augment
         self.last_wave = None            # (WaveDraws, device [N][Smax] WSOLA offsets or None) of the latest call with wave_augment
-        self.resampler = None
-        if input_rate is not None and int(input_rate) != 16000:
+        self.resampler = None            # one input rate other than 16 kHz
+        self.rates, self.bank = None, None       # a set of input rates (rates) and / or speed perturbation: every rate x speed product
+        speeds = getattr(wave_augment, "speed_choices", None)
+        if isinstance(input_rate, (tuple, list)):
+            if not input_rate or any(int(r) != r or int(r) <= 0 for r in input_rate) or len(set(input_rate)) != len(input_rate):
+                raise ValueError("input_rate as a set must hold distinct positive integer rates in Hz, got %r" % (input_rate,))
+            self.rates = tuple(int(r) for r in input_rate)
+        if self.rates is not None or speeds:
+            from .augment import speed_rate
+            from .resample import Resampler, ResamplerBank
+            self._one_rate = None if self.rates is not None else int(16000 if input_rate is None else input_rate)
+            products = []
+            for r in (self.rates if self.rates is not None else (self._one_rate,)):
+                for sp in (speeds or (1,)):
+                    eff = speed_rate(r, sp)
+                    try:
+                        Resampler(eff)
+                    except ValueError as e:
+                        raise ValueError("rate %d Hz at speed %s is read as %d Hz: %s" % (r, sp, eff, e)) from None
+                    if eff not in products:
+                        products.append(eff)
+            self.bank = ResamplerBank(products)
+        elif input_rate is not None and int(input_rate) != 16000:
             from .resample import Resampler
             self.resampler = Resampler(input_rate)
 
@@ -121,8 +147,23 @@ class SpectrogramFrontEnd:
             b = self._basis[dev] = torch.from_numpy(dft_basis(self.window)).to(dev)
         return b
 
-    def __call__(self, wav, nsamples, augment=False):
+    def _row_rates(self, rates, N):
+        """the input rate of each of N clips: `rates` checked against the front-end's set, or its one rate N times"""
+        if self.rates is None:
+            if rates is not None:
+                raise ValueError("rates=... belongs to a front-end built with a set of rates (input_rate=(...)); this one has "
+                                 "a single input rate")
+            return [self._one_rate] * N
+        if rates is None:
+            raise ValueError("this front-end takes clips at the rates %r: pass rates=[one per clip]" % (self.rates,))
+        rates = list(rates)
+        if len(rates) != N or any(int(r) != r or int(r) not in self.rates for r in rates):
+            raise ValueError("rates must hold one of %r per clip (%d clips), got %r" % (self.rates, N, rates))
+        return [int(r) for r in rates]
+
+    def __call__(self, wav, nsamples, augment=False, rates=None):
         """wav: [N][Lmax] float32 on a HIP device (row n = utterance n, zero beyond nsamples[n]); nsamples: [N] ints.
+        rates: the sample rate of each row, for a front-end built with a set of rates (and only for one).
         Returns (inputs (N,1,161,Tmax) float32, input_percentages [N] float32 (CPU), frames [N] int64 (CPU)).
         augment=True: every clip goes through the reference's spec_augment with draws from self.rng (one pinned upload, nothing is
         read back; the flow coefficients used stay on the device in self.last_coef)."""
@@ -137,6 +178,17 @@ class SpectrogramFrontEnd:
         if Lm > Lmax:
             raise ValueError("nsamples exceeds the waveform buffer")
         ns_dev = None
+        if self.bank is not None:
+            # the speed of a clip is the first draw of its augmentation and decides its class, so the draws come before the launch
+            base, wd = self._row_rates(rates, N), None
+            if self.wave_augment is not None and self.wave_augment.speed_choices:
+                wd = self.wave_augment.draw(ns.numpy(), self.rng, rates=base)
+            wav, ns_dev, ns = self.bank._run(wav, ns, base if wd is None else wd.rates.tolist())
+            if wd is not None:
+                return self._call_wave_augmented(wav, ns, augment, wd)
+            Lm = int(ns.max())
+        elif rates is not None:
+            self._row_rates(rates, N)
         if self.resampler is not None:   # everything below sees the 16 kHz signal and its lengths (known on the host in closed form)
             wav, ns_dev, ns = self.resampler._run(wav, ns)
             Lm = int(ns.max())
@@ -241,7 +293,7 @@ class SpectrogramFrontEnd:
             o += p.size
         return views
 
-    def collate(self, waveforms, transcripts=None, int16_scale=False, augment=False):
+    def collate(self, waveforms, transcripts=None, int16_scale=False, augment=False, rates=None):
         """waveforms: list of 1-D float tensors.  Sorts by length descending (as _collate_fn sorts by frame count,
         data_loader.py:251; with wave_augment by the length AFTER the tempo change; with input_rate the resampled length is
         monotone in the given one, so the order is that of the 16 kHz clips), pads, uploads and runs the front-end.
@@ -252,8 +304,24 @@ class SpectrogramFrontEnd:
         AMPLITUDE: log1p(|STFT|) is not scale-free.  The reference's load_audio (data_loader.py:23-30) hands
         compute_spectrogram samples in [-1, 1] (int16 / 32767); pass waveforms on that scale, or raw int16-range samples with
         int16_scale=True (they are divided by 32767 here, as load_audio does)."""
-        wd = None
-        if self.wave_augment is not None and self.wave_augment.active:
+        wd = eff = None
+        if self.bank is not None:
+            # a set of rates and / or speed perturbation: the order is that of the lengths at 16 kHz (after speed and tempo)
+            base, wa = self._row_rates(rates, len(waveforms)), self.wave_augment
+            lens = [len(w) for w in waveforms]
+            if wa is not None and wa.speed_choices:
+                wd = wa.draw(lens, self.rng, rates=base)
+                eff = wd.rates.tolist()
+            else:
+                eff = base
+                if wa is not None and wa.active:
+                    wd = wa.draw([self.bank.out_len(n, r) for n, r in zip(lens, eff)], self.rng)
+            key = wd.nsamples if wd is not None else [self.bank.out_len(n, r) for n, r in zip(lens, eff)]
+            order = sorted(range(len(waveforms)), key=lambda i: -int(key[i]))
+            wd = wd.take(order) if wd is not None else None
+        elif rates is not None:
+            self._row_rates(rates, len(waveforms))
+        elif self.wave_augment is not None and self.wave_augment.active:
             # the reference augments every clip as the sampler hands it out and _collate_fn sorts the RESULTS: draw in the given
             # order, sort by the length after the tempo change (known on the host)
             # (with input_rate: of the 16 kHz signal, the one the augmentations work on)
@@ -270,10 +338,14 @@ class SpectrogramFrontEnd:
         if int16_scale:
             buf /= 32767.0
         lens = [len(waveforms[i]) for i in order]
-        if wd is None:
+        if eff is not None and wd is None:
+            inputs, pct, _ = self(buf.cuda(), lens, augment=augment, rates=[eff[i] for i in order])
+        elif wd is None:
             inputs, pct, _ = self(buf.cuda(), lens, augment=augment)
         else:
             wav, ns = buf.cuda(), torch.tensor(lens, dtype=torch.int32)
+            if eff is not None:
+                wav, _, ns = self.bank._run(wav, ns, [eff[i] for i in order])
             if self.resampler is not None:
                 wav, _, ns = self.resampler._run(wav, ns)
             inputs, pct, _ = self._call_wave_augmented(wav, ns, augment, wd)
@@ -311,17 +383,27 @@ class SpectStream:
         self._state = torch.zeros(query("ds2_spect_stream_state_bytes", S), dtype=torch.uint8, device=self.device)
         self.samples, self.ended, self._fresh = [0] * S, [False] * S, [True] * S
         # a front-end with input_rate: the chunks arrive at that rate and pass a ResampleStream over the same slots first
+        # (with a set of rates: a BankStream, each slot at the rate reset() gives it)
         self._resample = front_end.resampler.stream(S, self.device) if front_end.resampler is not None else None
+        if front_end.rates is not None:
+            self._resample = front_end.bank.stream(S, self.device)
 
-    def reset(self, slots=None):
+    def reset(self, slots=None, rates=None):
         """These slots (None = all) start a new stream: their carry and statistics read as empty from the next feed on; nothing
-        is launched."""
-        for s in (range(self.capacity) if slots is None else [int(v) for v in slots]):
+        is launched.  rates: with a front-end built with a set of rates, the rate of each slot's new stream (None = the rate it
+        had); a slot is fed only once it has one."""
+        if rates is not None and self.front_end.rates is None:
+            raise ValueError("rates=... belongs to a front-end built with a set of rates (input_rate=(...))")
+        slots = list(range(self.capacity)) if slots is None else [int(v) for v in slots]
+        for s in slots:
             if not 0 <= s < self.capacity:
                 raise ValueError("slot %d is not a slot of this stream (capacity %d)" % (s, self.capacity))
-            self.samples[s], self.ended[s], self._fresh[s] = 0, False, True
-        if self._resample is not None:
+        if rates is not None:                  # refuses a rate that is not of the set before anything is reset
+            self._resample.reset(slots, rates)
+        elif self._resample is not None:
             self._resample.reset(slots)
+        for s in slots:
+            self.samples[s], self.ended[s], self._fresh[s] = 0, False, True
 
     def frames(self, slot):
         """frames emitted so far for the slot's stream"""

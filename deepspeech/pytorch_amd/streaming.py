@@ -408,19 +408,29 @@ class StreamPool:
         self._h_zero = [True] * S                          # the slot's hidden state is the zero state of a new stream
         self.front_end, self._wave = front_end, None       # feed_wave: the front-end and its streaming handle over the S slots
         self._source = [None] * S                          # per slot: "spect" or "wave", what its stream is fed with
+        self._rate = [None] * S                            # per slot: its stream's sample rate, for a front-end with a set of rates
         self.last_output = {}                              # slot -> (cnt3, C) probabilities of the last feed that held the slot
 
     # ---- slots ------------------------------------------------------------------------------------------------------------------
-    def open(self):
-        """A free slot with fresh state: zero hidden state, carries that read as zero, a reset decoder stream, no frames fed."""
+    def open(self, rate=None):
+        """A free slot with fresh state: zero hidden state, carries that read as zero, a reset decoder stream, no frames fed.
+        rate: the sample rate in Hz of the stream that starts, one of the front-end's ``input_rate`` set -- required when the
+        front-end was built with a set of rates, refused otherwise."""
+        rates = getattr(self.front_end, "rates", None)
+        if rates is None and rate is not None:
+            raise ValueError("open(rate=%r): the pool's front-end has one input rate; build it with input_rate=(...) for a rate "
+                             "per stream" % (rate,))
+        if rates is not None and (rate is None or int(rate) != rate or int(rate) not in rates):
+            raise ValueError("the pool's front-end takes the rates %r: open(rate=...) must name one of them, got %r" % (rates, rate))
         if all(self._open):
             raise ValueError("the pool is full: all %d slots are open" % self.capacity)
         s = self._open.index(False)
+        self._rate[s] = None if rate is None else int(rate)
         self._open[s] = True
         self._fed[s], self._ended[s], self._text[s], self._fresh[s] = 0, False, '', 7
         self._source[s] = None
         if self._wave is not None:
-            self._wave.reset([s])
+            self._wave.reset([s]) if rate is None else self._wave.reset([s], rates=[int(rate)])
         self.last_output.pop(s, None)
         if self.stream is not None:
             if self.endpoint is not None:
@@ -546,6 +556,9 @@ class StreamPool:
                              "whole utterance, which a stream does not have yet; build it with normalize='running'")
         if self._wave is None:
             self._wave = self.front_end.stream(self.capacity, wav.device)
+            rated = [s for s in range(self.capacity) if self._rate[s] is not None]
+            if rated:
+                self._wave.reset(rated, rates=[self._rate[s] for s in rated])
         spect, frames = self._wave.feed(sl, wav, nsamples, final=fin)
         for s in sl:
             self._source[s] = "wave"

@@ -487,7 +487,7 @@ typedef struct ds2_resample_stream_row {
   int32_t emit;          /* outputs this feed emits */
   int32_t final;         /* the utterance ends with this feed */
   int32_t fresh;         /* the slot's carry reads as that of a new stream */
-  int32_t pad;
+  int32_t pad;           /* ds2_resample_stream_feed_mixed: the row's class; ds2_resample_stream_feed does not read it */
 } ds2_resample_stream_row;
 long ds2_resample_out_len(long n, int U, int D);
 int ds2_resample_tile(int U, int D, int W);
@@ -498,6 +498,41 @@ long ds2_resample_stream_state_bytes(int S, int W);
 long ds2_resample_stream_ws_bytes(int n_rows, int W);
 int ds2_resample_stream_feed(const float* wav, long ldw, const ds2_resample_stream_row* rows, int n_rows, int max_new, int max_emit, int S,
                              const float* taps, int U, int D, int W, void* state, float* out, long ldo, void* ws, ds2_stream_t stream);
+
+/* Mixed rates: U, D, W and the table belong to the row, not to the launch.  A CLASS is one (U, D, W, taps), what the entries above
+ * take; a call carries C <= 16 of them.  (1, 1, 0) is the COPY class, y[m] = x[m] bit for bit (16 kHz rows ride in the same
+ * launch); it has no table.  A row of a mixed call is, bit for bit, the row of the single-rate call with its class's numbers, and
+ * a streamed row the one-shot row however it is cut into feeds.
+ * ds2_resample_classes (host only): udw [C][3] = (U, D, W) per class -> table [C], with each class's tile shape (the one
+ *   ds2_resample_tile reports) and taps_off, and *taps_floats = the floats of the taps buffer: the tables one behind the other in
+ *   class order, class c's taps_off floats in (always even: 8-byte aligned).  The caller keeps the table and uploads the same bytes
+ *   as the device table; the entries take both, the host's for the launch shape, the device's for the kernels.
+ * ds2_resample_mixed: ds2_resample with cls [N] int32 (device), the class of each row.  nsamples_out = min(out_len of the row's
+ *   class, ldo).  A row whose class is outside [0, C) computes nothing: zeros and a count of 0.
+ * ds2_resample_stream_feed_mixed: ds2_resample_stream_feed with the class in the row's pad word.  state [S][2 Wmax] f32 and ws
+ *   [n_rows][2 Wmax] f32 (the _mixed size queries), Wmax >= every W of the table and >= 1; a slot keeps at most 2 W - 1 samples
+ *   of its class.  A fresh row reads its slot's carry as empty, whatever a stream of another class left there.  A row whose
+ *   class is outside [0, C) writes zeros and leaves its slot alone; the copy class emits its n_new samples and carries nothing.
+ * One compute launch per call whatever C is (streaming adds the carry launch).
+ * DS2_ERR_ARG: as above, and C outside [1, 16], a class that is neither the copy class nor has U, D, W >= 1 and a table of at most
+ *   128 KiB, a host table whose tile shape is not the one ds2_resample_classes gives, Wmax < a W, taps null with a class that has
+ *   a table; DS2_ERR_ALIGN: taps, rows or classes_dev not 8-byte aligned, an odd taps_off.  Nothing is launched then. */
+typedef struct ds2_resample_class {
+  int32_t U, D, W;
+  int32_t nt, P, K;      /* threads that work, outputs between two outputs of a thread, outputs per thread */
+  int32_t tile;          /* P K: the consecutive outputs one workgroup computes */
+  int32_t cap;           /* floats of the input span staged in LDS, 0 = read from global memory */
+  int64_t taps_off;      /* floats in front of the class's table in the taps buffer */
+} ds2_resample_class;
+int ds2_resample_classes(const int* udw, int C, ds2_resample_class* table, long* taps_floats);
+int ds2_resample_mixed(const float* wav, long ldw, const int* nsamples, const int* cls, int N, const ds2_resample_class* classes,
+                       const ds2_resample_class* classes_dev, int C, const float* taps, float* out, long ldo, int* nsamples_out,
+                       ds2_stream_t stream);
+long ds2_resample_stream_state_bytes_mixed(int S, int Wmax);
+long ds2_resample_stream_ws_bytes_mixed(int n_rows, int Wmax);
+int ds2_resample_stream_feed_mixed(const float* wav, long ldw, const ds2_resample_stream_row* rows, int n_rows, int max_new, int max_emit,
+                                   int S, const ds2_resample_class* classes, const ds2_resample_class* classes_dev, int C, const float* taps,
+                                   int Wmax, void* state, float* out, long ldo, void* ws, ds2_stream_t stream);
 
 /* ---- greedy CTC decoding on the device (validation_step, model.py:256 -> GreedyDecoder.decode, decoder.py:164-181) -------
  * x[n*stride_n + t*stride_t + c] f32 scores (probabilities or logits), C <= 64; sizes [N] int32 on the device (null = T).

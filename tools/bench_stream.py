@@ -9,6 +9,7 @@ forward sweep takes h0/c0 and returns hn/cn).  Prints one JSON line per model: p
     python tools/bench_stream.py --carry [--decode greedy --chunk 0.2 --streams 1]
     python tools/bench_stream.py --pool 8 [--chunk 0.2 --seconds 10 --pool-modes sessions,pool,session,pool_lockstep --pool-launches]
     python tools/bench_stream.py --carry --wave      /      --pool 8 --wave      [--rate 48000]
+    python tools/bench_stream.py --pool 8 --wave --rates 8000,16000,48000     # one pool at mixed rates against one pool per rate
 
 With --decode greedy|beam the drop-in class runs inside a streaming.StreamingTranscriber: every chunk's output goes to the decoder
 stream on the device and the best transcript so far comes back per chunk (no output leaves the device, nothing is decoded twice).
@@ -242,6 +243,73 @@ def run_pool(a):
         measure(mode)
 
 
+def run_pool_rates(a):
+    """--pool S --wave --rates R1,R2,...: stream k arrives at rates[k % len(rates)] and joins at tick k.  `pool_mixed` is ONE
+    StreamPool of S slots whose front-end takes the set of rates (open(rate=...)): one feed_wave per tick.  `pool_per_rate` is
+    what a single-rate front-end leaves: one StreamPool per rate, each fed once per tick.  Only the ticks in which all S streams
+    are open and none ends are timed.  One JSON line per mode."""
+    from deepspeech.pytorch_amd import configs, decoder as D, streaming
+    from deepspeech.pytorch_amd.spectrogram import SpectrogramFrontEnd
+    dev, S, tc = "cuda", a.pool, int(a.chunk * 100)
+    nch = int(a.seconds * 100) // tc
+    rates = [int(r) for r in a.rates.split(",")]
+    rate_of = [rates[k % len(rates)] for k in range(S)]
+    spc = [int(round(a.chunk * r)) for r in rate_of]
+    m = _uni_lstm(dev)
+    rng = np.random.RandomState(0)
+    audio = [torch.from_numpy(0.1 * rng.standard_normal(nch * n).astype(np.float32)).to(dev) for n in spc]
+    max_frames = nch * tc // 2 + 2
+    fe_of = lambda r: SpectrogramFrontEnd(configs.SpectConfig(), normalize="running", input_rate=r)
+    plan = []
+    for t in range(S - 1 + nch):
+        rows = [(k, t - k) for k in range(S) if 0 <= t - k < nch]
+        plan.append((rows, len(rows) == S and all(j < nch - 1 for _, j in rows)))
+
+    def batch(rows):
+        if not rows:                      # a pool none of whose streams is open in this tick
+            return None
+        buf =torch.zeros((len(rows), max(spc[k] for k, _ in rows)), device=dev)
+        for i, (k, j) in enumerate(rows):
+            buf[i, :spc[k]] = audio[k][j * spc[k]:(j + 1) * spc[k]]
+        return buf
+
+    def measure(mode):
+        groups = [list(range(S))] if mode == "pool_mixed" else [[k for k in range(S) if rate_of[k] == r] for r in rates]
+        groups = [g for g in groups if g]
+        pools = [streaming.StreamPool(m, D.GreedyDecoder(configs.LABELS), len(g), max_frames=max_frames,
+                                      front_end=fe_of(tuple(rates) if mode == "pool_mixed" else rate_of[g[0]])) for g in groups]
+        feeds = [[(rows_g, batch(rows_g)) for rows_g in ([(k, j) for k, j in rows if k in g] for g in groups)] for rows, _ in plan]
+        lat = []
+        for r in range(a.reps + 1):
+            slot = {}
+            for i, (rows, timed) in enumerate(plan):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for pool, (rows_g, buf) in zip(pools, feeds[i]):
+                    if not rows_g:
+                        continue
+                    for k, j in rows_g:
+                        if j == 0:
+                            slot[k] = pool.open(rate=rate_of[k]) if mode == "pool_mixed" else pool.open()
+                    pool.feed_wave([slot[k] for k, _ in rows_g], buf, [spc[k] for k, _ in rows_g],
+                                   final=[slot[k] for k, j in rows_g if j == nch - 1])
+                    for k, j in rows_g:
+                        if j == nch - 1:
+                            pool.close(slot[k])
+                torch.cuda.synchronize()
+                if timed and r > 0:
+                    lat.append(time.perf_counter() - t0)
+        lat = np.array(lat)
+        print(json.dumps({"metric": "one tick of S exact streams at mixed rates (every open stream advances one chunk)", "mode": mode,
+                          "streams": S, "rates": rate_of, "pools": len(pools), "model": "uni-LSTM-1024x5+lookahead", "decode": "greedy",
+                          "chunk_seconds": a.chunk, "chunks_per_stream": nch, "ticks_timed": int(lat.size),
+                          "ms_per_tick_median": round(float(np.median(lat)) * 1e3, 3),
+                          "ms_per_tick_p95": round(float(np.percentile(lat, 95)) * 1e3, 3), "dtype": "bf16"}), flush=True)
+
+    for mode in ("pool_per_rate", "pool_mixed", "pool_per_rate", "pool_mixed"):
+        measure(mode)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--seconds", type=float, default=30.0)
@@ -258,6 +326,8 @@ def main():
     ap.add_argument("--wave", action="store_true", help="--carry / --pool: feed raw audio (feed_wave) to the exact modes")
     ap.add_argument("--endpoint", action="store_true", help="--pool: the sessions and the pool cut their streams into utterances")
     ap.add_argument("--rate", type=int, default=None, help="--wave: the sample rate of the audio fed (the front-end's input_rate)")
+    ap.add_argument("--rates", default=None, help="--pool --wave: comma-separated rates, stream k at rates[k %% len]: one pool at "
+                                                  "mixed rates against one pool per rate")
     a = ap.parse_args()
     if a.wave and not (a.pool or a.carry):
         raise SystemExit("--wave goes with --carry or --pool")
@@ -265,6 +335,10 @@ def main():
         raise SystemExit("--endpoint goes with --pool")
     if a.rate and not a.wave:
         raise SystemExit("--rate goes with --wave")
+    if a.rates and not (a.pool and a.wave) or a.rates and a.rate:
+        raise SystemExit("--rates goes with --pool and --wave, and without --rate")
+    if a.pool and a.rates:
+        return run_pool_rates(a)
     if a.pool:
         return run_pool(a)
     from deepspeech.pytorch_amd import configs

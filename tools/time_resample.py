@@ -1,6 +1,9 @@
 """Times the resampler (csrc/ds2_resample.hip) next to what it feeds.  profiles/resample_timing.md holds its output.
 
     python tools/time_resample.py oneshot --rate 48000        # 32 clips of 12-15 s: ds2_resample, then the spectrogram call on its output
+    python tools/time_resample.py oneshot --mixed 8000,16000,48000     # the same clips spread over the rates: ONE ds2_resample_mixed
+                                                                       # launch, then the single-rate call per rate it replaces
+    python tools/time_resample.py oneshot --speed [--rate 48000]       # three-way speed perturbation: the classes rate x 0.9 / 1 / 1.1
     python tools/time_resample.py stream [--rate 48000]       # SpectStream.feed, 8 slots, 0.2 s chunks (no --rate: the 16 kHz path)
     python tools/time_resample.py copy                        # device copy bandwidth (the HBM floor's yardstick)
     python tools/time_resample.py summarise DIR               # per-kernel table from a rocprofv3 --kernel-trace --output-format csv run
@@ -68,6 +71,47 @@ def oneshot(a):
     print(json.dumps(res))
 
 
+def mixed(a):
+    """32 clips of 12-15 s, clip i at rates[i % len(rates)]: one mixed launch against one single-rate launch per rate other than
+    16 kHz (a 16 kHz clip costs the single-rate path nothing: its rows are not touched)"""
+    import numpy as np
+    import torch
+    from deepspeech.pytorch_amd import ops
+    from deepspeech.pytorch_amd.augment import speed_rate
+    from deepspeech.pytorch_amd.resample import ResamplerBank
+    rates = [speed_rate(a.rate or 16000, s) for s in (0.9, 1.0, 1.1)] if a.speed else [int(r) for r in a.mixed.split(",")]
+    bank = ResamplerBank(rates)
+    rng = np.random.RandomState(0)
+    secs = sorted(rng.uniform(12.0, 15.0, size=32), reverse=True)
+    rate_of = [rates[i % len(rates)] for i in range(32)]
+    lens = [int(v * r) for v, r in zip(secs, rate_of)]
+    g = torch.Generator(device="cuda").manual_seed(0)
+    wav = 0.1 * torch.randn((32, max(lens)), device="cuda", generator=g)
+    ns = torch.tensor(lens, dtype=torch.int32, device="cuda")
+    cls = torch.tensor([bank.class_of[r] for r in rate_of], dtype=torch.int32, device="cuda")
+    lens16 = [bank.out_len(n, r) for n, r in zip(lens, rate_of)]
+    out = torch.empty((32, max(lens16)), dtype=torch.float32, device="cuda")
+    classes_dev, taps = bank.on(wav.device)
+    res = {"mode": "oneshot-speed" if a.speed else "oneshot-mixed", "rates": rates, "clips": 32,
+           "clips_per_rate": {str(r): rate_of.count(r) for r in rates}, "audio_seconds": round(float(sum(secs)), 1),
+           "bytes_in": 4 * sum(lens), "bytes_out": 4 * sum(lens16)}
+    res["ds2_resample_mixed"] = _timed(lambda i: ops.resample_mixed(wav, ns, cls, bank.classes, classes_dev, taps, out.shape[1], out=out))
+    groups = []
+    for r in rates:
+        rs, idx = bank.resampler(r), [i for i in range(32) if rate_of[i] == r]
+        if rs.identity or not idx:
+            continue
+        n_r = [lens[i] for i in idx]
+        groups.append((rs, wav[idx, :max(n_r)].contiguous(), torch.tensor(n_r, dtype=torch.int32, device="cuda"), rs.taps_on(wav.device),
+                       torch.empty((len(idx), rs.out_len(max(n_r))), dtype=torch.float32, device="cuda")))
+
+    def per_rate(i):
+        for rs, w, n, t, o in groups:
+            ops.resample(w, n, t, rs.up, rs.down, rs.half_width, o.shape[1], out=o)
+    res["ds2_resample_per_rate"] = dict(_timed(per_rate), launches=len(groups))
+    print(json.dumps(res))
+
+
 def stream(a):
     import numpy as np
     import torch
@@ -128,11 +172,15 @@ def main():
     ap.add_argument("dir", nargs="?")
     ap.add_argument("--rate", type=int, default=None)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--mixed", default=None, help="oneshot: comma-separated rates, clip i at rates[i %% len]")
+    ap.add_argument("--speed", action="store_true", help="oneshot: the classes --rate (default 16000) x 0.9 / 1.0 / 1.1")
     ap.add_argument("--only", default=None, help="summarise: comma-separated substrings of the kernel names to keep")
     a = ap.parse_args()
     sys.path.insert(0, a.root)
+    if a.mode == "oneshot" and (a.mixed or a.speed):
+        return mixed(a)
     if a.mode == "oneshot" and not a.rate:
-        raise SystemExit("oneshot needs --rate")
+        raise SystemExit("oneshot needs --rate, --mixed or --speed")
     {"oneshot": oneshot, "stream": stream, "copy": copy, "summarise": summarise}[a.mode](a)
 
 
