@@ -121,6 +121,13 @@ SIGNATURES = {
     "ds2_beam_grid_ws_bytes": (_l, [_i, _i, _i, _i]),
     "ds2_beam_decode_lm_grid": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _i, _vp, _l, _vp, _l, _i, _i, _i, _i, _vp, _vp,
                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    # the character-LM block after cutoff_prob: cid, ngram_table, slots, order, bos, alpha, beta (the grid: G, alphas, betas)
+    "ds2_beam_decode_clm": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _l, _i, _i, _f, _f,
+                                 _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_beam_decode_clm_grid": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _l, _i, _i, _i, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ds2_beam_stream_feed_clm": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _i, _i, _f, _vp, _vp, _l, _i, _i, _f, _f,
+                                      _vp, _i, _vp, _vp, _l, _i, _vp, _vp, _vp, _vp, _vp]),
     "ds2_greedy_stream_feed": (_i, [_vp, _l, _l, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "ds2_beam_stream_bytes": (_l, [_i, _i, _i, _i]),
     "ds2_beam_stream_ws_bytes": (_l, [_i, _i]),

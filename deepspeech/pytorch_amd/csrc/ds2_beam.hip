@@ -45,6 +45,11 @@
 // + v(match), from a second per-beam state (HotState) that is a function of the string alone.  P2 probes the phrase table with
 // two keys at once per new candidate, P6 repeats that for a new string and probes once more for its space extension.  Every
 // addition sits under `if constexpr (HOT)`; the six instantiations above compile to the instructions they had without it.
+// k_beam_search<false, ClmArgs>, <false, ClmArgs, StreamArgs>, <false, ClmArgs, GridArgs> (ds2_beam_decode_clm,
+// ds2_beam_stream_feed_clm, ds2_beam_decode_clm_grid) score with a character n-gram model (DESIGN.md "ds2_beam", character language
+// model): every new candidate of P2 is an event of the model, probed there; a beam carries lm, its last order - 1 label ids and the
+// backoffs of its context suffixes (ClmState, probed once in P6), and there is no end-of-utterance term.  Every addition sits under
+// `if constexpr (CLM)`; the ten instantiations above compile to the instructions they had without it.
 #include <float.h>
 
 #include "ds2_common.h"
@@ -205,6 +210,120 @@ __device__ __forceinline__ LmState* lm_state() {
   return s;
 }
 
+// ---- character language model --------------------------------------------------------------------------------------------
+// DESIGN.md "ds2_beam", character language model: every label is an event of the n-gram model, so the model is charged for every
+// new candidate in P2.  cid maps a class to its unigram id (-1: none).  A beam carries lm, the ids of its last order - 1 labels
+// (ctx[0] the most recent, <s> in front of a short string, -1 the out-of-vocabulary mark) and the log10 backoffs of its context
+// suffixes, bo[m] of (ctx[m] .. ctx[0]), 0 where that context is not stored: a function of the string alone, probed once in P6.
+struct ClmArgs {
+  const int* cid;           // [C] class -> unigram id, -1 when the file has none (the blank's entry is not read)
+  const ulonglong2* gtab;   // n-gram table [gmask + 1] x (key, log10 p bits | log10 backoff bits << 32)
+  unsigned gmask;
+  int order, bos;
+  float alpha, beta;
+  float* acoustic;          // [N][B] -lse(pb, pnb), or null
+};
+struct NoClm {};
+
+struct ClmState {
+  float lm[BEAM_MAXB];                                 // sum of the label bonuses
+  int ctx[BEAM_LM_MAX_ORDER - 1][BEAM_MAXB];
+  float bo[BEAM_LM_MAX_ORDER - 1][BEAM_MAXB];
+};
+static_assert(sizeof(ClmState) == sizeof(LmState), "the character-LM state takes the room of the word-LM state");
+
+// like lm_state(): only the character-LM instantiations name it
+__device__ __forceinline__ ClmState* clm_state() {
+  __shared__ ClmState s[2];
+  return s;
+}
+
+__device__ __forceinline__ float clm_scale(const ClmArgs& A, double lnp) {
+  return (float)__dadd_rn(__dmul_rn((double)A.alpha, lnp), (double)A.beta);
+}
+
+// NP keys of the n-gram table at once, as word_bonus probes: one unconditional round of loads, later rounds (bounded by the table
+// size) only while a key is displaced.  Returns the mask of the keys found, their values in val.
+template <int NP>
+__device__ __forceinline__ unsigned clm_find(const ClmArgs& A, const uint64_t (&key)[NP], unsigned pending, uint64_t (&val)[NP]) {
+  unsigned slot[NP], found = 0;
+#pragma unroll
+  for (int j = 0; j < NP; ++j) {
+    slot[j] = tab_slot(key[j], A.gmask);
+    val[j] = 0;
+  }
+  for (unsigned probe = 0; probe <= A.gmask && pending; ++probe) {
+    ulonglong2 e[NP];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) e[j] = A.gtab[slot[j]];
+#pragma unroll
+    for (int j = 0; j < NP; ++j) {
+      const bool open = pending >> j & 1, match = e[j].x == key[j], free_slot = e[j].x == kTabEmpty;
+      val[j] = open && match ? e[j].y : val[j];
+      found |= (unsigned)(open && match) << j;
+      pending &= ~((unsigned)(open && (match || free_slot)) << j);
+      slot[j] = open && !match && !free_slot ? (slot[j] + 1) & A.gmask : slot[j];
+    }
+  }
+  return found;
+}
+
+// The bonus of the label with unigram id w after the context c (c[0] the most recent) whose suffixes have the backoffs bo: the
+// keys of (c[m-1] .. c[0], w), m = 0 .. order-1, are probed together; the longest stored one gives log10 p, and every shorter step
+// above it first adds the backoff of the context it drops.
+__device__ __forceinline__ float clm_bonus(const ClmArgs& A, int w, const int (&c)[BEAM_LM_MAX_ORDER - 1],
+                                           const float (&bo)[BEAM_LM_MAX_ORDER - 1]) {
+  bool oov = w < 0;
+#pragma unroll
+  for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) oov |= m < A.order - 1 && c[m] < 0;
+  if (oov) return clm_scale(A, kOovScore);
+  uint64_t key[BEAM_LM_MAX_ORDER], val[BEAM_LM_MAX_ORDER];
+  unsigned pending = 1u;
+  uint64_t h = ngram_mix(kNgramSeed, w);
+  key[0] = h;
+#pragma unroll
+  for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) {
+    h = ngram_mix(h, c[m]);
+    key[m + 1] = h;
+    if (m < A.order - 1) pending |= 1u << (m + 1);
+  }
+  const unsigned found = clm_find<BEAM_LM_MAX_ORDER>(A, key, pending, val);
+  double acc = 0.0;
+  bool hit = false;
+#pragma unroll
+  for (int m = BEAM_LM_MAX_ORDER - 1; m >= 0; --m) {
+    if (m < A.order && !hit) {
+      if (found >> m & 1) {
+        acc = __dadd_rn(acc, (double)__uint_as_float((unsigned)val[m]));
+        hit = true;
+      } else if (m > 0) {
+        acc = __dadd_rn(acc, (double)bo[m - 1]);
+      }
+    }
+  }
+  if (!hit) return clm_scale(A, kOovScore);   // an id without a unigram: not built by lm.py
+  return clm_scale(A, __ddiv_rn(acc, kLog10e));
+}
+
+// the backoffs of the suffixes of the context c, for a new string: bo[m] of (c[m] .. c[0]), 0 when it is not stored or holds -1
+__device__ __forceinline__ void clm_backoffs(const ClmArgs& A, const int (&c)[BEAM_LM_MAX_ORDER - 1],
+                                             float (&bo)[BEAM_LM_MAX_ORDER - 1]) {
+  uint64_t key[BEAM_LM_MAX_ORDER - 1], val[BEAM_LM_MAX_ORDER - 1];
+  unsigned pending = 0;
+  uint64_t g = kNgramSeed;
+  bool known = true;
+#pragma unroll
+  for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) {
+    g = ngram_mix(g, c[m]);
+    key[m] = g;
+    known &= c[m] >= 0;
+    if (m < A.order - 1 && known) pending |= 1u << m;
+  }
+  const unsigned found = clm_find<BEAM_LM_MAX_ORDER - 1>(A, key, pending, val);
+#pragma unroll
+  for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) bo[m] = found >> m & 1 ? __uint_as_float((unsigned)(val[m] >> 32)) : 0.f;
+}
+
 // ---- hot words -----------------------------------------------------------------------------------------------------------
 // DESIGN.md "ds2_beam", hot words.  The table (hotwords.py) has one entry for every non-empty prefix q of every phrase: key = the
 // string hash of q (space label included), value = v(q) bits | c(q) bits << 32 | whole phrase << 63.  A beam carries the hash of its
@@ -342,6 +461,23 @@ __device__ __forceinline__ auto hot_args(const A& a, const R&... r) {
 }
 template <class X, class... Extra> struct Has { static constexpr bool value = (__is_same(Extra, X) || ...); };
 
+// the packs of the character-LM instantiations: ClmArgs [, GridArgs | StreamArgs], with LM = false
+__device__ __forceinline__ NoLm lm_args(const ClmArgs&) { return {}; }
+__device__ __forceinline__ NoLm lm_args(const ClmArgs&, const GridArgs&) { return {}; }
+__device__ __forceinline__ NoLm lm_args(const ClmArgs&, const StreamArgs&) { return {}; }
+__device__ __forceinline__ const StreamArgs& stream_args(const ClmArgs&, const StreamArgs& s) { return s; }
+__device__ __forceinline__ long grid_pool(const ClmArgs&, const GridArgs& g) { return (long)blockIdx.y * g.pool_stride; }
+template <class... R>
+__device__ __forceinline__ NoClm clm_args(const R&...) { return {}; }
+__device__ __forceinline__ ClmArgs clm_args(const ClmArgs& a) { return a; }
+__device__ __forceinline__ ClmArgs clm_args(const ClmArgs& a, const StreamArgs&) { return a; }
+__device__ __forceinline__ ClmArgs clm_args(const ClmArgs& a, const GridArgs& g) {
+  ClmArgs r = a;
+  r.alpha = g.alphas[blockIdx.y];
+  r.beta = g.betas[blockIdx.y];
+  return r;
+}
+
 // whether the last of the kernel's trailing argument types is X
 template <class X, class... Extra> struct LastIs { static constexpr bool value = false; };
 template <class X, class A> struct LastIs<X, A> { static constexpr bool value = __is_same(A, X); };
@@ -446,7 +582,9 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 
   constexpr bool GRID = LastIs<GridArgs, Extra...>::value, STREAM = LastIs<StreamArgs, Extra...>::value;
   constexpr bool HOT = Has<HotArgs, Extra...>::value;
+  constexpr bool CLM = Has<ClmArgs, Extra...>::value;
   [[maybe_unused]] const auto A = lm_args(extra...);
+  [[maybe_unused]] const auto CA = clm_args(extra...);
   [[maybe_unused]] const auto H = hot_args(extra...);
   const int n = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
   int size = sizes ? sizes[n] : T;
@@ -494,6 +632,20 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 #pragma unroll
       for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) L[0].ctx[m][0] = A.bos;
     }
+    if constexpr (CLM) {
+      ClmState* L = clm_state();
+      int cx[BEAM_LM_MAX_ORDER - 1];
+      float bo[BEAM_LM_MAX_ORDER - 1];
+#pragma unroll
+      for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) cx[m] = CA.bos;
+      clm_backoffs(CA, cx, bo);
+      L[0].lm[0] = 0.f;
+#pragma unroll
+      for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) {
+        L[0].ctx[m][0] = cx[m];
+        L[0].bo[m][0] = bo[m];
+      }
+    }
     if constexpr (HOT) {
       HotState* HS = hot_state();
       HS[0].mh[0] = kHashEmpty;
@@ -532,6 +684,16 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 #pragma unroll
           for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) L[0].ctx[m][tid] = li[(1 + m) * B + tid];
         }
+        if constexpr (CLM) {
+          ClmState* L = clm_state();
+          const float* lf = (const float*)(sp + (long)kStreamBeamBytes * B);
+          L[0].lm[tid] = lf[tid];
+#pragma unroll
+          for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) {
+            L[0].ctx[m][tid] = ((const int*)lf)[(1 + m) * B + tid];
+            L[0].bo[m][tid] = lf[(BEAM_LM_MAX_ORDER + m) * B + tid];
+          }
+        }
         if constexpr (HOT) {
           HotState* HS = hot_state();
           const char* hp = sp + stream_hot_off(LM, B);
@@ -549,11 +711,13 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
   // kept list of the next frame, in registers of wave 0 (lane k holds slot k)
   int pf_cnt = 0, pf_c = 0;
   float pf_lp = 0.f;
+  [[maybe_unused]] int pf_id = -1;                     // character LM: the unigram id of pf_c
   if (size > 0) {
     pf_cnt = pcnt[fbase + t0];
     if (tid < K) {
       pf_c = pcls[(fbase + t0) * BEAM_MAXK + tid];
       pf_lp = plp[(fbase + t0) * BEAM_MAXK + tid];
+      if constexpr (CLM) pf_id = CA.cid[pf_c < 0 ? 0 : (pf_c >= C ? C - 1 : pf_c)];
     }
   }
   __syncthreads();
@@ -569,6 +733,8 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
       kc[tid] = c;
       klp[tid] = pf_lp;
       kidx[c] = (short)tid;
+      // the kept classes' unigram ids, in the histogram's room: P4 zeroes it only after P2 and P3 are done with them
+      if constexpr (CLM) ((int*)hist)[tid] = pf_id;
     }
     if (tid < nb) {
       int slot = hash_slot(S.hash[tid], S.len[tid]);
@@ -589,6 +755,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
       if (tid < K) {
         pf_c = pcls[(fbase + t + 1) * BEAM_MAXK + tid];
         pf_lp = plp[(fbase + t + 1) * BEAM_MAXK + tid];
+        if constexpr (CLM) pf_id = CA.cid[pf_c < 0 ? 0 : (pf_c >= C ? C - 1 : pf_c)];
       }
     }
     // ---- P2: extensions
@@ -644,6 +811,17 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
             if (c == A.space) l += LS.spb[i];   // a word event; 0 (open mode) or -inf (lexicon mode) where it is none
             else if (A.lexicon && word_lookup(A, hash_ext(LS.whash[i], c)) == kWordAbsent) l = -INFINITY;
             s = mass + l;
+          } else if constexpr (CLM) {
+            // a label event: the bonus of this label after the beam's context, probed here for a new candidate only
+            const ClmState& LS = clm_state()[cur];
+            int cx[BEAM_LM_MAX_ORDER - 1];
+            float bo[BEAM_LM_MAX_ORDER - 1];
+#pragma unroll
+            for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) {
+              cx[m2] = LS.ctx[m2][i];
+              bo[m2] = LS.bo[m2][i];
+            }
+            s = mass + (LS.lm[i] + clm_bonus(CA, ((const int*)hist)[k], cx, bo));
           }
         }
       }
@@ -666,6 +844,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         if constexpr (LM) cs[i * W] = (lse(npb, npnb) + lm_state()[cur].lm[i]) + hot;
         else cs[i * W] = lse(npb, npnb) + hot;
       } else if constexpr (LM) cs[i * W] = lse(npb, npnb) + lm_state()[cur].lm[i];
+      else if constexpr (CLM) cs[i * W] = lse(npb, npnb) + clm_state()[cur].lm[i];
       else cs[i * W] = lse(npb, npnb);
     }
     __syncthreads();
@@ -776,6 +955,16 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 #pragma unroll
           for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) LD.ctx[m2][r] = LS.ctx[m2][i];
         }
+        if constexpr (CLM) {
+          const ClmState& LS = clm_state()[cur];
+          ClmState& LD = clm_state()[cur ^ 1];
+          LD.lm[r] = LS.lm[i];
+#pragma unroll
+          for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) {
+            LD.ctx[m2][r] = LS.ctx[m2][i];
+            LD.bo[m2][r] = LS.bo[m2][i];
+          }
+        }
         if constexpr (HOT) {
           const HotState& HS = hot_state()[cur];
           HotState& HD = hot_state()[cur ^ 1];
@@ -790,7 +979,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         const int c = kc[m - 1];
         const int id = t * B + r;
         D.pb[r] = -INFINITY;
-        if constexpr (LM || HOT) D.pnb[r] = (c == S.last[i] ? S.pb[i] : score[i]) + klp[m - 1];   // the acoustic mass, as P2 formed it
+        if constexpr (LM || HOT || CLM) D.pnb[r] = (c == S.last[i] ? S.pb[i] : score[i]) + klp[m - 1];   // the acoustic mass, as P2 formed it
         else D.pnb[r] = cs[q];
         D.lpc[r] = klp[m - 1];
         D.hash[r] = hash_ext(S.hash[i], c);
@@ -870,6 +1059,29 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 #pragma unroll
           for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) LD.ctx[m2][r] = cx[m2];
         }
+        if constexpr (CLM) {
+          // the candidate's total less its acoustic mass is not its lm bit for bit, so the bonus is formed again as P2 formed it
+          const ClmState& LS = clm_state()[cur];
+          ClmState& LD = clm_state()[cur ^ 1];
+          int cx[BEAM_LM_MAX_ORDER - 1];
+          float bo[BEAM_LM_MAX_ORDER - 1];
+#pragma unroll
+          for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) {
+            cx[m2] = LS.ctx[m2][i];
+            bo[m2] = LS.bo[m2][i];
+          }
+          const int w = CA.cid[c];
+          LD.lm[r] = LS.lm[i] + clm_bonus(CA, w, cx, bo);
+#pragma unroll
+          for (int m2 = BEAM_LM_MAX_ORDER - 2; m2 > 0; --m2) cx[m2] = cx[m2 - 1];
+          cx[0] = w;
+          clm_backoffs(CA, cx, bo);
+#pragma unroll
+          for (int m2 = 0; m2 < BEAM_LM_MAX_ORDER - 1; ++m2) {
+            LD.ctx[m2][r] = cx[m2];
+            LD.bo[m2][r] = bo[m2];
+          }
+        }
       }
     }
     if (tid < nk) kidx[kc[tid]] = -1;
@@ -904,6 +1116,16 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
 #pragma unroll
           for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) li[(1 + m) * B + tid] = LE.ctx[m][tid];
         }
+        if constexpr (CLM) {
+          const ClmState& LE = clm_state()[cur];
+          float* lf = (float*)(sp + (long)kStreamBeamBytes * B);
+          lf[tid] = LE.lm[tid];
+#pragma unroll
+          for (int m = 0; m < BEAM_LM_MAX_ORDER - 1; ++m) {
+            ((int*)lf)[(1 + m) * B + tid] = LE.ctx[m][tid];
+            lf[(BEAM_LM_MAX_ORDER + m) * B + tid] = LE.bo[m][tid];
+          }
+        }
         if constexpr (HOT) {
           const HotState& HE = hot_state()[cur];
           char* hp = sp + stream_hot_off(LM, B);
@@ -932,6 +1154,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
   [[maybe_unused]] float* acoustic = nullptr;
   if constexpr (LM) acoustic = A.acoustic;
   else if constexpr (HOT) acoustic = H.acoustic;
+  else if constexpr (CLM) acoustic = CA.acoustic;
   if constexpr (HOT) {
     // end of utterance with hot words: hot_end pays a match that is a whole phrase and nothing for an unfinished one; with an
     // LM the end is covered only by a whole phrase, so a hot word cut short is out of vocabulary again.  Re-ranked by the total.
@@ -979,6 +1202,14 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
       for (int s = 0; s < nb; ++s) orank += score[s] > tot || (score[s] == tot && s < tid);
     }
   }
+  if constexpr (CLM) {
+    // no end-of-utterance term and no re-rank: the ranks are the last selection's
+    if (tid < nb) {
+      const float ac = lse(S.pb[tid], S.pnb[tid]);
+      score[tid] = ac + clm_state()[cur].lm[tid];
+      stay_pb[tid] = ac;
+    }
+  }
   // every rank writes its row; in a grid only rank 0 does (thread 0 where no beam is alive), at row (g, n)
   bool emit = GRID ? orank == 0 : true;
   if constexpr (STREAM) emit = orank < stream_args(extra...).out_ranks;   // a stream writes its best out_ranks beams only
@@ -1002,7 +1233,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
         node = parent[node];
       }
       lens[o] = len;
-      if constexpr (LM || HOT) {
+      if constexpr (LM || HOT || CLM) {
         scores[o] = -score[tid] + 0.f;
         if (acoustic) acoustic[o] = -stay_pb[tid] + 0.f;
       } else {
@@ -1011,7 +1242,7 @@ __global__ void __launch_bounds__(BEAM_THREADS) k_beam_search(int T, int C, cons
     } else {
       lens[o] = 0;
       scores[o] = INFINITY;
-      if constexpr (LM || HOT) {
+      if constexpr (LM || HOT || CLM) {
         if (acoustic) acoustic[o] = INFINITY;
       }
     }
@@ -1042,7 +1273,7 @@ WsLayout ws_layout(int N, int T, int B, int G = 1) {
 int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
                 int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
                 const LmArgs* lm, int G = 1, const float* alphas = nullptr, const float* betas = nullptr,
-                const HotArgs* hot = nullptr);
+                const HotArgs* hot = nullptr, const ClmArgs* clm = nullptr);
 
 // A stream session's buffer: the states, then the node pool's three arrays
 struct StreamLayout {
@@ -1050,6 +1281,9 @@ struct StreamLayout {
 };
 
 constexpr int kStreamFlagLm = 1, kStreamFlagHot = 2;   // the flag word of the ds2_beam_stream_* size queries and reset
+constexpr int kStreamFlagClm = 4;                      // with kStreamFlagLm and without hot words: the model scores characters
+// the flag words that name a form of the search: 0 .. 3, and 5 (the character LM's state has the size of the word LM's)
+bool stream_flags_ok(int flags) { return (flags >= 0 && flags <= 3) || flags == (kStreamFlagLm | kStreamFlagClm); }
 
 StreamLayout stream_layout(int N, int B, int max_frames, int flags) {
   StreamLayout L;
@@ -1083,7 +1317,7 @@ __global__ void k_beam_stream_reset(char* state, long state_stride, int N, const
 int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
                      int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets, long row_stride,
                      int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm,
-                     const HotArgs* hot = nullptr);
+                     const HotArgs* hot = nullptr, const ClmArgs* clm = nullptr);
 
 // the checks and the fields of the hot-word entry points
 int hot_args_from(HotArgs& H, int C, int blank, int space, const void* hot_table, long hot_slots, float oov_logp, float* acoustic) {
@@ -1116,6 +1350,24 @@ int lm_args_from(LmArgs& A, int C, int blank, int space, const void* word_table,
   A.order = order;
   A.bos = bos;
   A.lexicon = lexicon != 0;
+  A.alpha = alpha;
+  A.beta = beta;
+  A.acoustic = acoustic;
+  return 0;
+}
+
+// the checks and the fields of the character-LM entry points (the grid form passes alpha = beta = 0: its points carry them)
+int clm_args_from(ClmArgs& A, int C, const int* cid, const void* ngram_table, long ngram_slots, int order, int bos, float alpha,
+                  float beta, float* acoustic) {
+  DS2_REQUIRE(C > 0 && cid && ngram_table, DS2_ERR_ARG);
+  DS2_REQUIRE(order >= 1 && order <= BEAM_LM_MAX_ORDER && bos >= 0, DS2_ERR_ARG);
+  DS2_REQUIRE(ngram_slots >= 2 && ngram_slots <= (1l << 31) && (ngram_slots & (ngram_slots - 1)) == 0, DS2_ERR_ARG);
+  DS2_REQUIRE(((uintptr_t)ngram_table & 15) == 0 && ((uintptr_t)cid & 3) == 0, DS2_ERR_ALIGN);
+  A.cid = cid;
+  A.gtab = (const ulonglong2*)ngram_table;
+  A.gmask = (unsigned)(ngram_slots - 1);
+  A.order = order;
+  A.bos = bos;
   A.alpha = alpha;
   A.beta = beta;
   A.acoustic = acoustic;
@@ -1158,15 +1410,16 @@ int ds2_beam_decode_lm(const float* x, long stride_n, long stride_t, int N, int 
                      (hipStream_t)st_, &A);
 }
 
-// flags: bit 0 a language model, bit 1 hot words (0 and 1 are the former values of this argument)
+// flags: bit 0 a language model, bit 1 hot words (0 and 1 are the former values of this argument), bit 2 the language model
+// scores characters (only as 5: with bit 0, without bit 1); any other word gives 0
 long ds2_beam_stream_bytes(int N, int B, int max_frames, int flags) {
-  if (N <= 0 || B <= 0 || max_frames <= 0 || flags < 0 || flags > 3) return 0;
+  if (N <= 0 || B <= 0 || max_frames <= 0 || !stream_flags_ok(flags)) return 0;
   return stream_layout(N, B, max_frames, flags).total;
 }
 
 // bytes between two streams' states at the front of a session's buffer
 long ds2_beam_stream_state_stride(int B, int flags) {
-  if (B <= 0 || flags < 0 || flags > 3) return 0;
+  if (B <= 0 || !stream_flags_ok(flags)) return 0;
   return stream_layout(1, B, 1, flags).state_stride;
 }
 
@@ -1179,7 +1432,7 @@ long ds2_beam_stream_ws_bytes(int N, int Tc) {
 // stream with a non-zero entry starts again from the empty beam (null = every stream); the others are untouched.  A new buffer is
 // reset as a whole before its first feed.
 int ds2_beam_stream_reset(void* state, int N, int B, int max_frames, int flags, const int* mask, ds2_stream_t st_) {
-  DS2_REQUIRE(state && N > 0 && B >= 1 && B <= BEAM_MAXB && max_frames > 0 && flags >= 0 && flags <= 3, DS2_ERR_ARG);
+  DS2_REQUIRE(state && N > 0 && B >= 1 && B <= BEAM_MAXB && max_frames > 0 && stream_flags_ok(flags), DS2_ERR_ARG);
   DS2_REQUIRE(((uintptr_t)state & 255) == 0, DS2_ERR_ALIGN);
   const StreamLayout L = stream_layout(N, B, max_frames, flags);
   hipLaunchKernelGGL(k_beam_stream_reset, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)st_, (char*)state,
@@ -1304,6 +1557,49 @@ int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N,
                      (hipStream_t)st_, &A, G, alphas, betas);
 }
 
+// The search with a character n-gram language model (DESIGN.md "ds2_beam", character language model): every label is an event
+// of the model.  cid: [C] device int32, the unigram id of every class, -1 where the file has none (the blank's entry is not
+// read); ngram_table as for ds2_beam_decode_lm; order 1 .. 5; bos: the id of <s>.  No word table, no lexicon, no end-of-utterance
+// term: scores = -(acoustic + lm) of the last selection's ranks; acoustic (may be null): -lse(pb, pnb) of the same ranks.
+int ds2_beam_decode_clm(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                        int cutoff_top_n, float cutoff_prob, const int* cid, const void* ngram_table, long ngram_slots, int order,
+                        int bos, float alpha, float beta, int* tokens, int* offsets, int* lens, float* scores, float* acoustic,
+                        void* ws, ds2_stream_t st_) {
+  ClmArgs A;
+  const int rc = clm_args_from(A, C, cid, ngram_table, ngram_slots, order, bos, alpha, beta, acoustic);
+  if (rc) return rc;
+  return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
+                     (hipStream_t)st_, nullptr, 1, nullptr, nullptr, nullptr, &A);
+}
+
+// ds2_beam_stream_feed with the character language model of ds2_beam_decode_clm (the same ids, table and weights in every call on
+// one state buffer, which was sized with flags = 5).  acoustic [N][out_ranks] may be null.
+int ds2_beam_stream_feed_clm(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                             int cutoff_top_n, float cutoff_prob, const int* cid, const void* ngram_table, long ngram_slots,
+                             int order, int bos, float alpha, float beta, void* state, int max_frames, int* tokens, int* offsets,
+                             long row_stride, int out_ranks, int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
+  ClmArgs A;
+  const int rc = clm_args_from(A, C, cid, ngram_table, ngram_slots, order, bos, alpha, beta, acoustic);
+  if (rc) return rc;
+  return beam_stream_feed(x, stride_n, stride_t, N, Tc, C, sizes, blank, B, cutoff_top_n, cutoff_prob, state, max_frames, tokens,
+                          offsets, row_stride, out_ranks, lens, scores, ws, (hipStream_t)st_, nullptr, nullptr, &A);
+}
+
+// ds2_beam_decode_clm for G points (alphas[g], betas[g]) at once, as ds2_beam_decode_lm_grid: outputs of every (point, sample)'s
+// top beam, row (g, n) equal to rank 0 of sample n of ds2_beam_decode_clm at that point bit for bit.  ws:
+// ds2_beam_grid_ws_bytes(G, N, T, B) bytes.
+int ds2_beam_decode_clm_grid(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                             int cutoff_top_n, float cutoff_prob, const int* cid, const void* ngram_table, long ngram_slots,
+                             int order, int bos, int G, const float* alphas, const float* betas, int* tokens, int* offsets,
+                             int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t st_) {
+  DS2_REQUIRE(G >= 1 && G <= BEAM_MAX_POINTS && alphas && betas, DS2_ERR_ARG);
+  ClmArgs A;
+  const int rc = clm_args_from(A, C, cid, ngram_table, ngram_slots, order, bos, 0.f, 0.f, acoustic);
+  if (rc) return rc;
+  return beam_decode(x, stride_n, stride_t, N, T, C, sizes, blank, B, cutoff_top_n, cutoff_prob, tokens, offsets, lens, scores, ws,
+                     (hipStream_t)st_, nullptr, G, alphas, betas, nullptr, &A);
+}
+
 }  // extern "C"
 
 namespace {
@@ -1347,8 +1643,12 @@ void launch_search(const SearchArgs& a, const Extra&... extra) {
 // The search with the language model and the hot words that are given.  tail: nothing, or the StreamArgs.  grid: null, or the points
 // of ds2_beam_decode_lm_grid, which has a language model, no hot words and no tail.
 template <class... Tail>
-void launch_search_with(const SearchArgs& a, const LmArgs* lm, const HotArgs* hot, const GridArgs* grid, const Tail&... tail) {
-  if (hot)
+void launch_search_with(const SearchArgs& a, const LmArgs* lm, const HotArgs* hot, const GridArgs* grid, const ClmArgs* clm,
+                        const Tail&... tail) {
+  if (clm) {           // the character LM: alone, with the points of a grid, or with the tail
+    if constexpr (sizeof...(Tail) == 0) grid ? launch_search<false>(a, *clm, *grid) : launch_search<false>(a, *clm);
+    else launch_search<false>(a, *clm, tail...);
+  } else if (hot)
     lm ? launch_search<true>(a, *lm, *hot, tail...) : launch_search<false>(a, *hot, tail...);
   else if (grid) {
     if constexpr (sizeof...(Tail) == 0) launch_search<true>(a, *lm, *grid);
@@ -1358,7 +1658,7 @@ void launch_search_with(const SearchArgs& a, const LmArgs* lm, const HotArgs* ho
 
 int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
                 int cutoff_top_n, float cutoff_prob, int* tokens, int* offsets, int* lens, float* scores, void* ws, hipStream_t st,
-                const LmArgs* lm, int G, const float* alphas, const float* betas, const HotArgs* hot) {
+                const LmArgs* lm, int G, const float* alphas, const float* betas, const HotArgs* hot, const ClmArgs* clm) {
   DS2_REQUIRE(x && tokens && (offsets || alphas) && lens && scores && ws, DS2_ERR_ARG);
   DS2_REQUIRE(((uintptr_t)ws & 255) == 0, DS2_ERR_ALIGN);
   const WsLayout L = ws_layout(N, T, B, G);
@@ -1370,14 +1670,15 @@ int beam_decode(const float* x, long stride_n, long stride_t, int N, int T, int 
   a.tokens = tokens, a.offsets = offsets, a.lens = lens, a.scores = scores;
   const GridArgs grid = {alphas, betas, L.pool / 4};
   a.grid.y = G;      // the grid form: G x N workgroups
-  launch_search_with(a, lm, hot, alphas ? &grid : nullptr);
+  launch_search_with(a, lm, hot, alphas ? &grid : nullptr, clm);
   DS2_CHECK_LAUNCH();
   return 0;
 }
 
 int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
                      int cutoff_top_n, float cutoff_prob, void* state, int max_frames, int* tokens, int* offsets, long row_stride,
-                     int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm, const HotArgs* hot) {
+                     int out_ranks, int* lens, float* scores, void* ws, hipStream_t st, const LmArgs* lm, const HotArgs* hot,
+                     const ClmArgs* clm) {
   DS2_REQUIRE(state && max_frames > 0 && ((long)max_frames + 1) * B <= 0x7fffffffl, DS2_ERR_ARG);
   const bool out = tokens != nullptr;
   DS2_REQUIRE(out == (offsets != nullptr) && out == (lens != nullptr) && out == (scores != nullptr), DS2_ERR_ARG);
@@ -1388,11 +1689,11 @@ int beam_stream_feed(const float* x, long stride_n, long stride_t, int N, int Tc
   const int rc = beam_prune(a, x, stride_n, stride_t, N, Tc, 0, C, sizes, blank, B, cutoff_top_n, cutoff_prob, ws,
                             stream_ws_layout(N, Tc), st);
   if (rc) return rc;
-  const StreamLayout SL = stream_layout(N, B, max_frames, (lm ? kStreamFlagLm : 0) | (hot ? kStreamFlagHot : 0));
+  const StreamLayout SL = stream_layout(N, B, max_frames, (lm || clm ? kStreamFlagLm : 0) | (hot ? kStreamFlagHot : 0));
   char* sb = (char*)state;
   a.parent = (int*)(sb + SL.parent), a.label = (int*)(sb + SL.label), a.frame = (int*)(sb + SL.frame);
   a.tokens = tokens, a.offsets = offsets, a.lens = lens, a.scores = scores;
-  launch_search_with(a, lm, hot, nullptr, StreamArgs{sb, SL.state_stride, max_frames, row_stride, out_ranks});
+  launch_search_with(a, lm, hot, nullptr, clm, StreamArgs{sb, SL.state_stride, max_frames, row_stride, out_ranks});
   DS2_CHECK_LAUNCH();
   return 0;
 }

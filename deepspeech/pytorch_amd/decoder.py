@@ -392,16 +392,33 @@ class BeamCTCDecoder:
     ``hotwords`` is a list of phrases the search should prefer (hotwords.py; DESIGN.md "ds2_beam", hot words): strings, or
     (string, weight) pairs, the weight in natural-log units per non-space label (default ``hotword_weight``).  With an LM a hot
     word outside its vocabulary is charged ``ln P = hot_oov_logp`` in place of -1000 and survives the lexicon.  ``None`` or an empty
-    list runs the entry points without hot words.  These three are keywords of this class only."""
+    list runs the entry points without hot words.  These three are keywords of this class only.
+
+    ``lm_unit`` says what the n-gram model's units are: ``"word"`` (the default), ``"char"`` -- every label is an event of the
+    model, ``alpha * ln P(label | the last order - 1 labels) + beta``, for label sets without word boundaries (DESIGN.md
+    "ds2_beam", character language model) -- or ``"auto"``, which picks ``"char"`` exactly when every unigram of the file other
+    than ``<s>``, ``</s>``, ``<unk>`` is one code point long (ctcdecode's test).  ``self.lm_unit`` holds the resolved value.  In
+    character mode a label is looked up in the file as it is written in ``labels``; the space label as ``space_token`` (e.g.
+    ``"|"``) when that is given and otherwise not at all (it is out of vocabulary).  No space label is needed, ``lexicon`` is
+    ignored, there is no end-of-utterance term, and hot words are refused (ValueError).  Keywords of this class only."""
 
     def __init__(self, labels, lm_path=None, alpha=0, beta=0, cutoff_top_n=40, cutoff_prob=1.0, beam_width=100,
-                 num_processes=4, blank_index=0, lexicon=True, hotwords=None, hotword_weight=2.0, hot_oov_logp=-11.5):
+                 num_processes=4, blank_index=0, lexicon=True, hotwords=None, hotword_weight=2.0, hot_oov_logp=-11.5,
+                 lm_unit="word", space_token=None):
         self.lm, self.lexicon, self._tables = None, bool(lexicon), {}
+        if lm_unit not in ("word", "char", "auto"):
+            raise ValueError("lm_unit must be 'word', 'char' or 'auto', got %r" % (lm_unit,))
+        self.lm_unit, self.space_token = "word", space_token
         if lm_path:
             from . import lm as _lm
-            if ' ' not in labels or labels.index(' ') == blank_index:
+            lm = _lm.load_arpa(lm_path)          # ValueError unless it is an ARPA text file of order 1 to 5
+            if lm_unit == "auto":
+                lm_unit = "char" if _lm.is_character_based(lm) else "word"
+            if lm_unit == "word" and (' ' not in labels or labels.index(' ') == blank_index):
                 raise ValueError("BeamCTCDecoder: a language model needs a space label other than the blank to end words")
-            self.lm = _lm.load_arpa(lm_path)     # ValueError unless it is an ARPA text file of order 1 to 5
+            if lm_unit == "char":
+                _lm.char_ids(lm, labels, blank_index, space_token)       # ValueError for a space_token that is no unigram
+            self.lm, self.lm_unit = lm, lm_unit
         self.labels = labels
         self.int_to_char = dict((i, c) for (i, c) in enumerate(labels))
         self.blank_index = blank_index
@@ -422,6 +439,9 @@ class BeamCTCDecoder:
         hotwords.py.  Calls and streams opened from now on use the new table; an open BeamStream keeps the one it was opened with."""
         hotwords = list(hotwords) if hotwords else []
         table = None
+        if hotwords and self.lm is not None and self.lm_unit == "char":
+            raise ValueError("BeamCTCDecoder: hot words are defined on word boundaries and are not supported with a character "
+                             "language model (lm_unit='char')")
         if hotwords:
             from . import hotwords as _hot
             table = _hot.build_table(hotwords, self.labels, self.blank_index, self.hotword_weight)
@@ -450,7 +470,10 @@ class BeamCTCDecoder:
         """The LM's two tables on `device`: built and uploaded on first use, then kept."""
         if device not in self._tables:
             from . import lm as _lm
-            wt, gt = _lm.build_tables(self.lm, self.labels, self.blank_index, self.space_index)
+            if self.lm_unit == "char":           # (label ids, n-gram table)
+                wt, gt = _lm.build_char_tables(self.lm, self.labels, self.blank_index, self.space_token)
+            else:
+                wt, gt = _lm.build_tables(self.lm, self.labels, self.blank_index, self.space_index)
             self._tables[device] = (torch.from_numpy(wt).to(device), torch.from_numpy(gt).to(device))
         return self._tables[device]
 
@@ -459,6 +482,9 @@ class BeamCTCDecoder:
         if self.lm is None:
             return None
         wt, gt = self._lm_tables(device)
+        if self.lm_unit == "char":
+            return dict(unit="char", label_ids=wt, ngram_table=gt, order=self.lm.order, bos=self.lm.bos, alpha=self.alpha,
+                        beta=self.beta)
         return dict(space=self.space_index, word_table=wt, ngram_table=gt, order=self.lm.order, bos=self.lm.bos, alpha=self.alpha,
                     beta=self.beta, lexicon=self.lexicon)
 
@@ -524,6 +550,10 @@ class BeamCTCDecoder:
         if not probs.is_cuda:
             probs = probs.to("cuda")
         lm = self._lm_args(probs.device)
+        if self.lm_unit == "char":
+            return ops.beam_decode_clm_grid(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
+                                            lm["label_ids"], lm["ngram_table"], lm["order"], lm["bos"],
+                                            [a for a, _ in points], [b for _, b in points], max_ws_bytes)
         return ops.beam_decode_lm_grid(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
                                        lm["space"], lm["word_table"], lm["ngram_table"], lm["order"], lm["bos"],
                                        [a for a, _ in points], [b for _, b in points], lm["lexicon"], max_ws_bytes)

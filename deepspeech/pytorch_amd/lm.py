@@ -11,6 +11,9 @@ open-addressing tables (load <= 1/2, linear probing, power-of-two sizes) are bui
 
 Both are int64 arrays of shape (slots, 2): [key, value]; a free slot holds EMPTY_KEY.  The build raises when two inserted keys
 are equal, so the lookup of a present key is exact.  KenLM's binary format is not read (it needs KenLM itself).
+
+A character model (ds2_beam_decode_clm; DESIGN.md "ds2_beam", character language model) is the same file read with the labels
+as its units: char_ids maps every label to its unigram id, the n-gram table is the same, and there is no word table.
 """
 import numpy as np
 
@@ -164,9 +167,10 @@ def load_arpa(path):
     return ArpaLM(words, ids, logp, backoff, counts)
 
 
-def make_table(keys, values, what="table"):
+def make_table(keys, values, what="table", spread=1):
     """Open-addressing table of shape (slots, 2) int64 [key, value] from uint64 keys and int64-representable values: slots = the
-    power of two >= 2 * len(keys) (>= 2), linear probing from slot_of(key).  ValueError if two keys are equal or one is EMPTY_KEY."""
+    power of two >= 2 * len(keys) (>= 2), times spread (a power of two: load <= 1 / (2 * spread)), linear probing from
+    slot_of(key).  ValueError if two keys are equal or one is EMPTY_KEY."""
     keys = np.asarray(keys, np.uint64).reshape(-1)
     values = np.asarray(values).reshape(-1)
     assert len(keys) == len(values)
@@ -177,6 +181,8 @@ def make_table(keys, values, what="table"):
     slots = 2
     while slots < 2 * len(keys):
         slots *= 2
+    assert spread >= 1 and spread & (spread - 1) == 0, spread
+    slots *= spread
     mask = np.uint64(slots - 1)
     tk = np.full(slots, EMPTY_KEY, np.uint64)
     tv = np.zeros(slots, np.uint64)
@@ -265,3 +271,48 @@ def build_tables(lm, labels, blank, space):
     bbits = np.concatenate(lm.backoff).view(np.uint32).astype(np.uint64)
     gt = make_table(keys, pbits | (bbits << np.uint64(32)), "n-gram table")
     return wt, gt
+
+
+# ---- character language models (ds2_beam_decode_clm; DESIGN.md "ds2_beam", character language model) --------------------
+SPECIAL_TOKENS = ("<s>", "</s>", "<unk>")
+
+
+def is_character_based(lm):
+    """ctcdecode's test: every unigram other than <s>, </s>, <unk> is one Unicode code point long."""
+    return all(len(w) == 1 for w in lm.words if w not in SPECIAL_TOKENS)
+
+
+def char_ids(lm, labels, blank, space_token=None):
+    """int32 [C]: the unigram id of every label (exact string match), -1 where the file has no such unigram and at the blank.
+    A label " " is looked up as space_token when that is given (ValueError if it is no unigram) and as " " otherwise, which no
+    ARPA file holds: the space is then out of vocabulary."""
+    if space_token is not None and space_token not in lm.word_id:
+        raise ValueError("space_token %r is no unigram of the language model" % (space_token,))
+    ids = np.full(len(labels), -1, np.int32)
+    for c, tok in enumerate(labels):
+        if c == blank:
+            continue
+        if tok == " " and space_token is not None:
+            tok = space_token
+        ids[c] = lm.word_id.get(tok, -1)
+    return ids
+
+
+# The character search looks up, per new candidate, keys of which most are absent (the long n-grams), and an absent key walks to
+# a free slot; at load 1/2 that is 2 to 3 dependent rounds in a crowded table, at load 1/8 rarely more than one.  Measured on an
+# MI355X (DESIGN.md "ds2_beam", character language model): 153 -> 85 us per time step with an order-5 file.  16 bytes a slot.
+CHAR_TABLE_SPREAD = 4
+
+
+def ngram_table(lm, spread=1):
+    """The n-gram table of build_tables on its own, with make_table's spread."""
+    keys = np.concatenate([_ngram_keys(lm.ids[m]) for m in range(lm.order)])
+    pbits = np.concatenate(lm.logp).view(np.uint32).astype(np.uint64)
+    bbits = np.concatenate(lm.backoff).view(np.uint32).astype(np.uint64)
+    return make_table(keys, pbits | (bbits << np.uint64(32)), "n-gram table", spread)
+
+
+def build_char_tables(lm, labels, blank, space_token=None, spread=CHAR_TABLE_SPREAD):
+    """(label ids int32 [C], n-gram table int64 (slots, 2)) of a character-mode search; the table has the word mode's layout and
+    keys at load <= 1 / (2 * spread)."""
+    return char_ids(lm, labels, blank, space_token), ngram_table(lm, spread)

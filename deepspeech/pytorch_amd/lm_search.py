@@ -1,5 +1,6 @@
 """Search of the language-model weights of ``BeamCTCDecoder`` on the device: the reference's ``search_lm_params.py`` runs one
-evaluation per (alpha, beta) trial; here every batch is decoded at all points in one launch (``ops.beam_decode_lm_grid``) and the
+evaluation per (alpha, beta) trial; here every batch is decoded at all points in one launch (``ops.beam_decode_lm_grid``, or
+``ops.beam_decode_clm_grid`` for a decoder in character mode) and the
 character and word errors of every point's best transcript are counted on the device (``ops.error_counts``), so that per batch no
 transcript travels to the host.  ``LMGridSearch.save`` writes the JSON list of ``[alpha, beta, WER, CER]`` that the reference's
 ``select_lm_params.py`` loads."""
@@ -12,7 +13,8 @@ from . import ops
 
 class LMGridSearch:
     def __init__(self, decoder, points, max_ws_bytes=1 << 30):
-        """decoder: a BeamCTCDecoder with lm_path (None: points and counters only); points: a sequence of (alpha, beta) pairs."""
+        """decoder: a BeamCTCDecoder with lm_path, in word or in character mode (None: points and counters only); points: a
+        sequence of (alpha, beta) pairs."""
         self.points = [(float(a), float(b)) for a, b in points]
         if not self.points:
             raise ValueError("LMGridSearch needs at least one (alpha, beta) point")

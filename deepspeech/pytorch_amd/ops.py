@@ -936,7 +936,8 @@ BEAM_LM_MAX_ORDER = 5
 def beam_search(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm=None, hot=None, _words=None):
     """CTC prefix beam search (ds2_beam_decode and its _lm, _hot and _lm_hot forms): the one body of beam_decode, beam_decode_lm,
     beam_decode_hot and beam_decode_lm_hot.  probs: (N, T', C) CUDA tensor of probabilities (any strides with a contiguous class
-    dimension); sizes: [N] int tensor or None (= T').  lm, hot: None, or the dicts that beam_stream_open takes.  Returns host
+    dimension); sizes: [N] int tensor or None (= T').  lm, hot: None, or the dicts that beam_stream_open takes (lm with
+    unit="char": a character model, ds2_beam_decode_clm, which takes no hot words).  Returns host
     lists: tokens[n][b] (labels of beam b, best first), offsets[n][b] (int tensor of their frames), a host (N, B) float tensor of
     scores (-log p less the LM's and the hot words' terms: the total that ranked the beams; +inf where fewer than B beams are
     alive) and one of the acoustic -log p of the same beams, which with neither an LM nor hot words is scores.  Only the
@@ -975,6 +976,16 @@ def beam_decode_lm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, s
     (N, B) float tensor of the acoustic -log p of the same beams."""
     lm = dict(space=space, word_table=word_table, ngram_table=ngram_table, order=order, bos=bos, alpha=alpha, beta=beta,
               lexicon=lexicon)
+    return beam_search(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm, _words=_words)
+
+
+def beam_decode_clm(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, label_ids, ngram_table, order, bos, alpha, beta,
+                    _words=None):
+    """CTC prefix beam search with a character n-gram language model (ds2_beam_decode_clm): every label is an event of the
+    model.  Arguments as beam_decode, plus the two values of lm.build_char_tables on the device of probs (label_ids: int32 [C],
+    the unigram id of every class, -1 for none, the blank's entry ignored; ngram_table: int64 (slots, 2)), the LM's order, the id
+    of <s>, alpha and beta.  Returns beam_decode_lm's four values; there is no end-of-utterance term."""
+    lm = dict(unit="char", label_ids=label_ids, ngram_table=ngram_table, order=order, bos=bos, alpha=alpha, beta=beta)
     return beam_search(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm, _words=_words)
 
 
@@ -1043,11 +1054,44 @@ def _beam_lm_checks(Cc, device, beam_width, cutoff_top_n, blank, space, word_tab
     return B, top_n
 
 
+def _lm_is_char(lm):
+    """whether the lm dict of a search names a character language model (unit="char"; absent or "word": a word model)"""
+    if lm is None:
+        return False
+    unit = lm.get("unit", "word")
+    if unit not in ("word", "char"):
+        raise ValueError("the language model's unit must be 'word' or 'char', got %r" % (unit,))
+    return unit == "char"
+
+
+def _beam_clm_checks(Cc, device, beam_width, cutoff_top_n, blank, label_ids, ngram_table, order, bos):
+    """The argument checks of a search with a character language model, in the manner of _beam_lm_checks; returns (B, top_n)."""
+    B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
+    if not 1 <= int(order) <= BEAM_LM_MAX_ORDER:
+        raise ValueError("language-model order must be in [1, %d], got %d" % (BEAM_LM_MAX_ORDER, order))
+    if bos < 0:
+        raise ValueError("the id of <s> must not be negative, got %d" % bos)
+    if not (torch.is_tensor(label_ids) and label_ids.dtype == torch.int32 and label_ids.dim() == 1 and label_ids.shape[0] == Cc
+            and label_ids.is_contiguous()):
+        raise ValueError("label_ids must be a contiguous int32 tensor with one entry per class (%d)" % Cc)
+    if label_ids.device != device or not label_ids.is_cuda:
+        raise ValueError("label_ids must live on the device of the probabilities (%s), not %s" % (device, label_ids.device))
+    _table_check("ngram_table", ngram_table, device)
+    return B, top_n
+
+
 def _beam_settings(Cc, device, beam_width, cutoff_top_n, blank, lm, hot):
     """The argument checks of beam_search and beam_stream_open, in their order: the search's own, the language model's, the hot
     words'.  Returns (B, top_n, lm, hot), the dicts with every scalar as the C call takes it."""
     if lm is None:
         B, top_n = _beam_checks(Cc, beam_width, cutoff_top_n, blank)
+    elif _lm_is_char(lm):
+        if hot is not None:
+            raise ValueError("hot words are defined on word boundaries; a character language model takes none")
+        B, top_n = _beam_clm_checks(Cc, device, beam_width, cutoff_top_n, blank, lm["label_ids"], lm["ngram_table"], lm["order"],
+                                    lm["bos"])
+        lm = dict(unit="char", label_ids=lm["label_ids"], ngram_table=lm["ngram_table"], order=int(lm["order"]),
+                  bos=int(lm["bos"]), alpha=float(lm["alpha"]), beta=float(lm["beta"]))
     else:
         B, top_n = _beam_lm_checks(Cc, device, beam_width, cutoff_top_n, blank, lm["space"], lm["word_table"], lm["ngram_table"],
                                    lm["order"], lm["bos"])
@@ -1064,16 +1108,28 @@ def _beam_settings(Cc, device, beam_width, cutoff_top_n, blank, lm, hot):
 
 # The C entries of the one-shot and of the resumable search, by (language model, hot words).  After the arguments that all share
 # come _lm_block, then _hot_block, then the entry's own state and outputs.
+_BEAM_CLM_ENTRIES = ("ds2_beam_decode_clm", "ds2_beam_stream_feed_clm")     # a character LM: its own block, never hot words
 _BEAM_ENTRIES = {(False, False): ("ds2_beam_decode", "ds2_beam_stream_feed"),
                  (True, False): ("ds2_beam_decode_lm", "ds2_beam_stream_feed_lm"),
                  (False, True): ("ds2_beam_decode_hot", "ds2_beam_stream_feed_hot"),
                  (True, True): ("ds2_beam_decode_lm_hot", "ds2_beam_stream_feed_lm_hot")}
 
 
+def _beam_entry(lm, hot, stream):
+    """the name of the one-shot (stream = 0) or resumable (1) C entry of a search with these dicts"""
+    if _lm_is_char(lm):
+        return _BEAM_CLM_ENTRIES[stream]
+    return _BEAM_ENTRIES[lm is not None, hot is not None][stream]
+
+
 def _lm_block(lm):
-    """the language model's arguments in the C order: space, word_table, slots, ngram_table, slots, order, bos, alpha, beta, lexicon"""
+    """the language model's arguments in the C order: space, word_table, slots, ngram_table, slots, order, bos, alpha, beta, lexicon;
+    of a character model: label_ids, ngram_table, slots, order, bos, alpha, beta"""
     if lm is None:
         return ()
+    if _lm_is_char(lm):
+        gt = lm["ngram_table"]
+        return (P(lm["label_ids"]), P(gt), gt.shape[0], lm["order"], lm["bos"], lm["alpha"], lm["beta"])
     wt, gt = lm["word_table"], lm["ngram_table"]
     return (lm["space"], P(wt), wt.shape[0], P(gt), gt.shape[0], lm["order"], lm["bos"], lm["alpha"], lm["beta"], int(lm["lexicon"]))
 
@@ -1091,7 +1147,7 @@ def _beam_launch(probs, sz, blank, B, top_n, cutoff_prob, lm, hot, buf, lens, sc
     ds2_beam_ws_bytes) and checked settings; acoustic, scores[1], exists for every form but the plain one"""
     N, T, Cc = probs.shape
     acoustic = () if lm is None and hot is None else (P(scores[1]),)
-    call(_BEAM_ENTRIES[lm is not None, hot is not None][0], P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank),
+    call(_beam_entry(lm, hot, 0), P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank),
          B, top_n, float(cutoff_prob), *_lm_block(lm), *_hot_block(lm, hot), P(buf[0]), P(buf[1]), P(lens), P(scores[0]), *acoustic,
          P(ws), S())
 
@@ -1155,6 +1211,14 @@ def beam_decode_lm_grid(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_pr
     points whose workspace fits max_ws_bytes (plan_grid_chunks); the cut does not change the result."""
     B, top_n = _beam_lm_checks(probs.shape[2], probs.device, beam_width, cutoff_top_n, blank, space, word_table, ngram_table,
                                order, bos)
+    block = (int(space), P(word_table), word_table.shape[0], P(ngram_table), ngram_table.shape[0], int(order), int(bos),
+             int(bool(lexicon)))
+    return _beam_grid("ds2_beam_decode_lm_grid", probs, sizes, blank, B, top_n, cutoff_prob, block, alphas, betas, max_ws_bytes)
+
+
+def _beam_grid(entry, probs, sizes, blank, B, top_n, cutoff_prob, block, alphas, betas, max_ws_bytes):
+    """the one body of beam_decode_lm_grid and beam_decode_clm_grid after their checks; block: the language model's arguments
+    in the C order up to the points"""
     if not probs.is_cuda:
         raise ValueError("probs must be a HIP device tensor")
     N, T, Cc = probs.shape
@@ -1175,11 +1239,20 @@ def beam_decode_lm_grid(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_pr
     ws = torch.empty(query("ds2_beam_grid_ws_bytes", max(c for _, c in chunks), N, T, B), dtype=torch.uint8, device=dev)
     for g0, cnt in chunks:
         g1 = g0 + cnt
-        call("ds2_beam_decode_lm_grid", P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n,
-             float(cutoff_prob), int(space), P(word_table), word_table.shape[0], P(ngram_table), ngram_table.shape[0], int(order),
-             int(bos), int(bool(lexicon)), cnt, P(al[g0:g1]), P(be[g0:g1]), P(buf[0, g0:g1]), P(buf[1, g0:g1]), P(lens[g0:g1]),
-             P(scores[0, g0:g1]), P(scores[1, g0:g1]), P(ws), S())
+        call(entry, P(probs), probs.stride(0), probs.stride(1), N, T, Cc, P(sz), int(blank), B, top_n, float(cutoff_prob), *block,
+             cnt, P(al[g0:g1]), P(be[g0:g1]), P(buf[0, g0:g1]), P(buf[1, g0:g1]), P(lens[g0:g1]), P(scores[0, g0:g1]),
+             P(scores[1, g0:g1]), P(ws), S())
     return buf[0], buf[1], lens, scores[0], scores[1]
+
+
+def beam_decode_clm_grid(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, label_ids, ngram_table, order, bos, alphas,
+                         betas, max_ws_bytes=1 << 30):
+    """beam_decode_clm at G weight points (alphas[g], betas[g]) in one launch of G x N workgroups (ds2_beam_decode_clm_grid), as
+    beam_decode_lm_grid: the same DEVICE tensors, row (g, n) being rank 0 of beam_decode_clm(alpha=alphas[g], beta=betas[g]) bit
+    for bit."""
+    B, top_n = _beam_clm_checks(probs.shape[2], probs.device, beam_width, cutoff_top_n, blank, label_ids, ngram_table, order, bos)
+    block = (P(label_ids), P(ngram_table), ngram_table.shape[0], int(order), int(bos))
+    return _beam_grid("ds2_beam_decode_clm_grid", probs, sizes, blank, B, top_n, cutoff_prob, block, alphas, betas, max_ws_bytes)
 
 
 class BeamStreamHandle:
@@ -1193,7 +1266,8 @@ class BeamStreamHandle:
 def beam_stream_open(num_streams, max_frames, num_classes, blank, beam_width, cutoff_top_n, cutoff_prob, device="cuda", lm=None,
                      hot=None):
     """Opens N = num_streams resumable CTC prefix beam searches of up to max_frames frames each.  lm: None, or the dict of
-    beam_decode_lm's language-model arguments (space, word_table, ngram_table, order, bos, alpha, beta, lexicon).  hot: None, or
+    beam_decode_lm's language-model arguments (space, word_table, ngram_table, order, bos, alpha, beta, lexicon), or with
+    unit="char" those of beam_decode_clm (label_ids, ngram_table, order, bos, alpha, beta; no hot words then).  hot: None, or
     the dict of the hot-word arguments (space, table, and with an LM oov_logp); the session keeps this table.  The checks and
     messages are beam_decode's / beam_decode_lm's.  The handle owns ds2_beam_stream_bytes(...) bytes of device memory: the
     states and the node pool, 12 * beam_width bytes per frame and stream.  Every stream starts fresh."""
@@ -1208,7 +1282,8 @@ def beam_stream_open(num_streams, max_frames, num_classes, blank, beam_width, cu
     B, top_n, lm, hot = _beam_settings(Cc, dev, beam_width, cutoff_top_n, blank, lm, hot)
     if (F + 1) * B > 2 ** 31 - 1:
         raise ValueError("max_frames=%d with beam_width=%d passes the node pool's 2^31 - 1 slots per stream" % (F, B))
-    flags = int(lm is not None) | (2 if hot is not None else 0)      # the flag word of the ds2_beam_stream_* size queries
+    # the flag word of the ds2_beam_stream_* size queries: bit 0 an LM, bit 1 hot words, bit 2 the LM scores characters
+    flags = int(lm is not None) | (2 if hot is not None else 0) | (4 if _lm_is_char(lm) else 0)
     state = torch.empty(query("ds2_beam_stream_bytes", N, B, F, flags), dtype=torch.uint8, device=dev)
     # state_stride: bytes between two streams' states at the front of the buffer; the node pool follows them
     h = BeamStreamHandle(state=state, N=N, B=B, max_frames=F, C=Cc, blank=int(blank), top_n=top_n, cutoff_prob=float(cutoff_prob),
@@ -1262,7 +1337,7 @@ def _beam_stream_launch(h, probs, Tc, sz, buf, lens, scores, row_stride, R):
         (P(None), P(None), 0, 0, P(None), P(None), P(None))
     if h.lm is None and h.hot is None:       # the plain entry has no acoustic output
         out = out[:-1]
-    call(_BEAM_ENTRIES[h.lm is not None, h.hot is not None][1], *x, h.N, Tc, h.C, P(sz), h.blank, h.B, h.top_n, h.cutoff_prob,
+    call(_beam_entry(h.lm, h.hot, 1), *x, h.N, Tc, h.C, P(sz), h.blank, h.B, h.top_n, h.cutoff_prob,
          *_lm_block(h.lm), *_hot_block(h.lm, h.hot), P(h.state), h.max_frames, *out, P(ws), S())
 
 

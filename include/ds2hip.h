@@ -590,6 +590,30 @@ int ds2_beam_decode_lm_grid(const float* x, long stride_n, long stride_t, int N,
                             const float* betas, int* tokens, int* offsets, int* lens, float* scores, float* acoustic, void* ws,
                             ds2_stream_t stream);
 
+/* ---- character language model (DESIGN.md "ds2_beam", character language model) ---------------------------------------------
+ * The search with an n-gram model whose units are the labels themselves (label sets without word boundaries): every new label is
+ * an event of the model, lm += alpha * ln P(label | the last order - 1 labels) + beta, with <s> in front of a short string.
+ * After the shared leading arguments comes one block: cid [C] device int32, the unigram id of every class, -1 where the file
+ * has none (the blank's entry is not read); ngram_table / ngram_slots as for ds2_beam_decode_lm; order in [1, 5]; bos = id of
+ * <s>; alpha, beta (the grid form: G, alphas, betas as ds2_beam_decode_lm_grid).  There is no word table, no lexicon, no
+ * end-of-utterance term and no re-rank: scores = -(log p + lm) of the last selection's ranks, acoustic (may be null) = -log p.
+ * With alpha = beta = 0 the outputs are ds2_beam_decode's bit for bit.  The stream form works on a buffer sized with flags = 5
+ * (bit 2 = "the language model scores characters", valid only with bit 0 and without bit 1); its state has the word LM's size.
+ * Outputs, ws, bounds and error codes as for the _lm counterparts; DS2_ERR_ARG also for a null cid. */
+int ds2_beam_decode_clm(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                        int cutoff_top_n, float cutoff_prob, const int* cid, const void* ngram_table, long ngram_slots, int order,
+                        int bos, float alpha, float beta, int* tokens, int* offsets, int* lens, float* scores, float* acoustic,
+                        void* ws, ds2_stream_t stream);
+int ds2_beam_decode_clm_grid(const float* x, long stride_n, long stride_t, int N, int T, int C, const int* sizes, int blank, int B,
+                             int cutoff_top_n, float cutoff_prob, const int* cid, const void* ngram_table, long ngram_slots,
+                             int order, int bos, int G, const float* alphas, const float* betas, int* tokens, int* offsets,
+                             int* lens, float* scores, float* acoustic, void* ws, ds2_stream_t stream);
+int ds2_beam_stream_feed_clm(const float* x, long stride_n, long stride_t, int N, int Tc, int C, const int* sizes, int blank, int B,
+                             int cutoff_top_n, float cutoff_prob, const int* cid, const void* ngram_table, long ngram_slots,
+                             int order, int bos, float alpha, float beta, void* state, int max_frames, int* tokens, int* offsets,
+                             long row_stride, int out_ranks, int* lens, float* scores, float* acoustic, void* ws,
+                             ds2_stream_t stream);
+
 /* ---- hot words (DESIGN.md "ds2_beam", hot words) ---------------------------------------------------------------------------
  * ds2_beam_decode / ds2_beam_decode_lm with a table of hot phrases: a beam earns a boost while its string ends in a prefix of a
  * phrase, and keeps the boost of every phrase it has completed.  hot_table: the open-addressing table of hotwords.build_table,
@@ -633,7 +657,8 @@ int ds2_beam_decode_lm_hot(const float* x, long stride_n, long stride_t, int N, 
  *   bonus and re-rank, which always look at all the live beams; acoustic [N][out_ranks] may be null.
  *   The consumed count never passes max_frames, so it needs no bound of its own.
  * flags (the former `lm` argument of the two size queries and of ds2_beam_stream_reset; 0 and 1 mean what they meant): bit 0 a
- *   language model, bit 1 hot words; any other bit gives size 0 / DS2_ERR_ARG.  Hot words add, from the next multiple of 8 bytes
+ *   language model, bit 1 hot words, bit 2 (only as flags = 5) a character language model, whose fields take the word LM's
+ *   36 * B bytes; any other word gives size 0 / DS2_ERR_ARG.  Hot words add, from the next multiple of 8 bytes
  *   after the other fields, 24 * B bytes (match hash, done, v, space value, flags), and 8 * B more (the partial-word hash) when
  *   there is no LM: a stride of 16 + 64 * B bytes without an LM and 16 + align8(68 * B) + 24 * B with one, rounded up to 256.
  * ds2_beam_stream_feed_hot / _feed_lm_hot: the same with the hot words of ds2_beam_decode_hot / _lm_hot, on a buffer sized with

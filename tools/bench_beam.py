@@ -25,6 +25,13 @@ chunked feeds is shorter where CHUNK_FRAMES does not divide T'; it is not the "l
 
     python tools/bench_beam.py --hot 100 [--lm tests/golden/lm/toy3.arpa] [--stream 100]
 
+    python tools/bench_beam.py --lm tests/golden/lm/char3.arpa --lm-unit char --space-token "|" [--grid 16] [--stream 100]
+    python tools/bench_beam.py --lm tests/golden/lm/cjk3.arpa --lm-unit char --top-n 64
+
+With --lm-unit char the file is a character model and the widths are timed through ops.beam_decode_clm ("beam+clm"), the grid
+through ops.beam_decode_clm_grid and the stream through ds2_beam_stream_feed_clm.  A file whose unigrams are not all English
+labels (the CJK fixture) gets an input with one class per unigram besides the blank.
+
 With --hot the same widths are also timed through ops.beam_decode_hot (and, with --lm, ops.beam_decode_lm_hot; with --stream the
 hot streams too) on N synthetic phrases: half of them words cut from the input's own greedy transcripts, so that matches start,
 run on and complete, the other half random letter strings of one or two words.
@@ -111,7 +118,7 @@ def stream_rows(a, probs, lm, oneshot, hot=None):
         late = states.clone()
         fresh = lambda: ops.beam_stream_reset(h)
         resume = lambda: states.copy_(late)
-        row = dict(decoder="stream" + ("+lm" if lm else "") + ("+hot" if hot else ""), B=B, chunk=Tc, feeds=len(chunks))
+        row = dict(decoder="stream" + (("+clm" if lm.get("unit") == "char" else "+lm") if lm else "") + ("+hot" if hot else ""), B=B, chunk=Tc, feeds=len(chunks))
         row["oneshot_ms"], row["oneshot_min"], row["oneshot_max"] = timed(lambda: oneshot(B), a.runs)
         row["chunked_ms"], row["chunked_min"], row["chunked_max"] = timed(chunked, a.runs)
         row["feed_ms"], row["feed_min"], row["feed_max"] = timed(lambda: ops.beam_stream_feed(h, chunks[0]), a.runs, prep=fresh)
@@ -234,6 +241,65 @@ def grid_rows(a, probs, sizes, wt, gt, model, C):
     return rows
 
 
+def char_lm_rows(a, probs, sizes, model, labels):
+    """--lm-unit char: ops.beam_decode_clm per width; with --grid the grid entry against a loop of single-point calls (the
+    ops calls, and the raw entries on buffers allocated beforehand); with --stream the resumable search.  Returns (rows, note)."""
+    from deepspeech.pytorch_amd import lm as LM
+    from deepspeech.pytorch_amd.ops import P, S, call, query
+    N, T, C = probs.shape
+    t0 = time.perf_counter()
+    ids, gt = LM.build_char_tables(model, labels, 0, a.space_token, a.table_spread or LM.CHAR_TABLE_SPREAD)
+    t1 = time.perf_counter()
+    ids, gt = torch.from_numpy(ids).cuda(), torch.from_numpy(gt).cuda()
+    note = ("# character lm %s: order %d, n-grams %s; %d of %d labels have a unigram, space token %r; table build %.2f s, n-gram "
+            "table %d slots (%.1f KB); alpha %.2f beta %.2f"
+            % (a.lm, model.order, model.counts, int((ids >= 0).sum()), C - 1, a.space_token, t1 - t0, gt.shape[0], gt.numel() * 8 / 1e3,
+               a.alpha, a.beta))
+    rows = []
+    tail = (ids, gt, model.order, model.bos)
+    for B in [int(w) for w in a.widths.split(",")]:
+        med, lo, hi = timed(lambda: ops.beam_decode_clm(probs, sizes, 0, B, a.top_n, 1.0, *tail, a.alpha, a.beta), a.runs)
+        rows.append(dict(decoder="beam+clm", B=B, ms_per_batch=med, min_ms=lo, max_ms=hi, us_per_step=1e3 * med / T))
+    sz = sizes.cuda()
+    for B in [int(w) for w in a.widths.split(",")] if a.grid else []:
+        for G in [int(g) for g in a.grid.split(",")]:
+            al = np.linspace(0.0, 2.0, G).astype(np.float32)
+            be = np.linspace(2.0, 0.0, G).astype(np.float32)
+            ws = torch.empty(query("ds2_beam_grid_ws_bytes", G, N, T, B), dtype=torch.uint8, device="cuda")
+            gbuf = torch.zeros((2, G, N, T), dtype=torch.int32, device="cuda")
+            glen = torch.zeros((G, N), dtype=torch.int32, device="cuda")
+            gsc = torch.zeros((2, G, N), dtype=torch.float32, device="cuda")
+            bbuf = torch.zeros((2, N, B, T), dtype=torch.int32, device="cuda")
+            blen = torch.zeros((N, B), dtype=torch.int32, device="cuda")
+            bsc = torch.zeros((2, N, B), dtype=torch.float32, device="cuda")
+            ald, bed = torch.from_numpy(al).cuda(), torch.from_numpy(be).cuda()
+            head = (P(probs), probs.stride(0), probs.stride(1), N, T, C, P(sz), 0, B, a.top_n, 1.0, P(ids), P(gt), gt.shape[0],
+                    model.order, model.bos)
+
+            def grid_kernels():
+                call("ds2_beam_decode_clm_grid", *head, G, P(ald), P(bed), P(gbuf[0]), P(gbuf[1]), P(glen), P(gsc[0]), P(gsc[1]),
+                     P(ws), S())
+
+            def loop_kernels():
+                for g in range(G):
+                    call("ds2_beam_decode_clm", *head, float(al[g]), float(be[g]), P(bbuf[0]), P(bbuf[1]), P(blen), P(bsc[0]),
+                         P(bsc[1]), P(ws), S())
+
+            def loop_call():
+                for g in range(G):
+                    ops.beam_decode_clm(probs, sizes, 0, B, a.top_n, 1.0, *tail, float(al[g]), float(be[g]))
+
+            for name, whole, kernels in (("grid", lambda: ops.beam_decode_clm_grid(probs, sizes, 0, B, a.top_n, 1.0, *tail, al, be),
+                                          grid_kernels), ("loop", loop_call, loop_kernels)):
+                med, lo, hi = timed(whole, a.runs, warmup=2)
+                kmed, _, _ = timed(kernels, a.runs, warmup=2)
+                rows.append(dict(decoder=name, B=B, G=G, ms_per_call=med, min_ms=lo, max_ms=hi, kernel_ms=kmed, ms_per_point=med / G))
+    if a.stream:
+        lm_args = dict(unit="char", label_ids=ids, ngram_table=gt, order=model.order, bos=model.bos, alpha=a.alpha, beta=a.beta)
+        rows += stream_rows(a, probs, lm_args, lambda B: ops.beam_decode_clm(probs, sizes, 0, B, a.top_n, 1.0, *tail, a.alpha, a.beta))
+    return rows, note
+
+
 def words_rows(a, probs, sizes):
     """decode_words against decode_beams, the confidence pass alone, and the streamed best_words() against best(), per width"""
     from deepspeech.pytorch_amd.configs import LABELS
@@ -287,6 +353,12 @@ def main():
     ap.add_argument("--scale", type=float, default=3.0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--lm", default=None, help="ARPA file: also time ops.beam_decode_lm")
+    ap.add_argument("--lm-unit", default="word", choices=["word", "char"],
+                    help="char: the file is a character model, timed through ops.beam_decode_clm (with --grid and --stream too); "
+                         "when its unigrams are not all English labels the input has one class per unigram and the blank")
+    ap.add_argument("--space-token", default=None, help="with --lm-unit char: the unigram that stands for the space label")
+    ap.add_argument("--table-spread", type=int, default=None,
+                    help="with --lm-unit char: slots of the n-gram table as a multiple of the word mode's (default: lm.CHAR_TABLE_SPREAD)")
     ap.add_argument("--alpha", type=float, default=1.0)
     ap.add_argument("--beta", type=float, default=1.0)
     ap.add_argument("--open", action="store_true", help="open mode (lexicon=False)")
@@ -301,6 +373,15 @@ def main():
     assert a.runs >= 10
     assert torch.cuda.is_available(), "bench_beam needs a HIP device"
     N, T, C = 32, 751, 29
+    char_model = char_labels = None
+    if a.lm and a.lm_unit == "char":
+        from deepspeech.pytorch_amd import lm as LM
+        from deepspeech.pytorch_amd.configs import LABELS
+        char_model, char_labels = LM.load_arpa(a.lm), list(LABELS)
+        units = [w for w in char_model.words if w not in LM.SPECIAL_TOKENS]
+        if not all(w in LABELS or w == a.space_token for w in units):
+            char_labels = ["_"] + units                   # a label set of the file's own, e.g. the CJK fixture: no space
+            C = len(char_labels)
     rng = np.random.default_rng(0)
     z = rng.standard_normal((N, T, C)) * a.scale
     z[:, :, C - 1] += a.space_boost                       # configs.LABELS: the space is the last label
@@ -329,7 +410,11 @@ def main():
         for B in [int(w) for w in a.widths.split(",")]:
             med, lo, hi = timed(lambda: ops.beam_decode_hot(probs, sizes, 0, B, a.top_n, 1.0, C - 1, ht), a.runs)
             rows.append(dict(decoder="beam+hot", B=B, ms_per_batch=med, min_ms=lo, max_ms=hi, us_per_step=1e3 * med / T))
-    if a.lm:
+    if char_model is not None:
+        more, note = char_lm_rows(a, probs, sizes, char_model, char_labels)
+        rows += more
+        notes.append(note)
+    elif a.lm:
         from deepspeech.pytorch_amd import lm as LM
         from deepspeech.pytorch_amd.configs import LABELS
         assert len(LABELS) == C and LABELS[C - 1] == ' '
@@ -353,14 +438,14 @@ def main():
                 med, lo, hi = timed(lambda: ops.beam_decode_lm_hot(probs, sizes, 0, B, a.top_n, 1.0, C - 1, wt, gt, model.order,
                                                                    model.bos, a.alpha, a.beta, not a.open, ht, a.hot_oov_logp), a.runs)
                 rows.append(dict(decoder="beam+lm+hot", B=B, ms_per_batch=med, min_ms=lo, max_ms=hi, us_per_step=1e3 * med / T))
-    if a.lm and a.grid:
+    if a.lm and a.grid and char_model is None:
         rows += grid_rows(a, probs, sizes, wt, gt, model, C)
     if a.stream:
         rows += stream_rows(a, probs, None, lambda B: ops.beam_decode(probs, sizes, 0, B, a.top_n, 1.0))
         hot_args = None if ht is None else dict(space=C - 1, table=ht, oov_logp=a.hot_oov_logp)
         if ht is not None:
             rows += stream_rows(a, probs, None, lambda B: ops.beam_decode_hot(probs, sizes, 0, B, a.top_n, 1.0, C - 1, ht), hot_args)
-        if a.lm:
+        if a.lm and char_model is None:
             lm_args = dict(space=C - 1, word_table=wt, ngram_table=gt, order=model.order, bos=model.bos, alpha=a.alpha, beta=a.beta,
                            lexicon=not a.open)
             rows += stream_rows(a, probs, lm_args,

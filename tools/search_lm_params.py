@@ -27,7 +27,7 @@ from deepspeech.pytorch_amd.lm_search import LMGridSearch  # noqa: E402
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Search alpha and beta of the n-gram LM decoder on saved outputs")
     ap.add_argument("batches", nargs="+", help=".npz files with probs, sizes, targets, target_sizes")
-    ap.add_argument("--lm-path", required=True, help="ARPA text file of the word n-gram model")
+    ap.add_argument("--lm-path", required=True, help="ARPA text file of the n-gram model")
     ap.add_argument("--output-path", default="lm_search.json")
     ap.add_argument("--labels-path", default=None, help="JSON list of labels (default: the package's labels)")
     ap.add_argument("--alpha-from", type=float, default=0.0)
@@ -40,6 +40,9 @@ def main(argv=None):
     ap.add_argument("--cutoff-top-n", type=int, default=40)
     ap.add_argument("--cutoff-prob", type=float, default=1.0)
     ap.add_argument("--open-vocabulary", action="store_true", help="lexicon=False: words outside the LM's vocabulary survive")
+    ap.add_argument("--lm-unit", default="word", choices=["word", "char", "auto"],
+                    help="what the model's units are: words, characters (every label is an event), or by ctcdecode's test")
+    ap.add_argument("--space-token", default=None, help="character mode: the unigram that stands for the space label, e.g. '|'")
     ap.add_argument("--max-ws-mb", type=int, default=1024, help="workspace cap of one launch; larger grids run in chunks")
     a = ap.parse_args(argv)
     assert torch.cuda.is_available(), "search_lm_params needs a HIP device"
@@ -48,7 +51,8 @@ def main(argv=None):
         with open(a.labels_path) as f:
             labels = json.load(f)
     dec = BeamCTCDecoder(labels, a.lm_path, cutoff_top_n=a.cutoff_top_n, cutoff_prob=a.cutoff_prob, beam_width=a.beam_width,
-                         blank_index=labels.index('_') if '_' in labels else 0, lexicon=not a.open_vocabulary)
+                         blank_index=labels.index('_') if '_' in labels else 0, lexicon=not a.open_vocabulary, lm_unit=a.lm_unit,
+                         space_token=a.space_token)
     search = LMGridSearch.from_ranges(a.alpha_from, a.alpha_to, a.num_alphas, a.beta_from, a.beta_to, a.num_betas, decoder=dec,
                                       max_ws_bytes=a.max_ws_mb << 20)
     for path in a.batches:
