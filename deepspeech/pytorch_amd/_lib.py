@@ -98,6 +98,8 @@ SIGNATURES = {
     "ds2_wave_ws_bytes": (_l, [_i]),
     "ds2_wave_energy": (_i, [_vp, _l, _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp]),
     "ds2_wave_mix": (_i, [_vp, _l, _vp, _i, _vp, _vp, _vp, _l, _vp, _vp, _vp, _vp, _l, _vp]),
+    "ds2_reverb_tile": (_i, []),
+    "ds2_reverb": (_i, [_vp, _l, _vp, _i, _vp, _l, _vp, _vp, _vp, _vp, _l, _vp]),
     "ds2_resample_out_len": (_l, [_l, _i, _i]),
     "ds2_resample_tile": (_i, [_i, _i, _i]),
     "ds2_resample_plan": (_i, [_l, _i, _i, _i, _i, _i, _vp]),

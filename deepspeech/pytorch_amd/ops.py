@@ -2237,6 +2237,35 @@ def wave_mix(wav, nsamples, gain=None, level=None, bank=None, noise_off=None, no
     return out
 
 
+def reverb(wav, nsamples, bank, rir_off, rir_len, rir_peak, out=None):
+    """Every clip of wav (N, Lmax) convolved with its room impulse response, aligned on the response's peak tap and cut to the
+    clip's length: out[i] = sum_k h[k] x[i + peak - k], ds2_reverb (csrc/ds2_reverb.hip).  bank = the 1-D device buffer of the
+    responses (augment.RirBank.samples), rir_off [N] int64 (negative = the clip is copied; None = every clip is copied and bank /
+    rir_len / rir_peak may be None), rir_len / rir_peak [N] int32.  Returns a new (N, Lmax) tensor (or fills `out`, (N, ldo)), zero
+    beyond a clip's own samples."""
+    wav, ns = _wave_batch(wav, nsamples)
+    N = wav.shape[0]
+    off = _per_clip(rir_off, N, wav.device, torch.int64, "rir_off")
+    ln = pk = None
+    if off is not None:
+        if bank is None or rir_len is None or rir_peak is None:
+            raise ValueError("rir_off needs the bank of responses with per-clip lengths and peaks")
+        if not (bank.is_cuda and bank.dtype == torch.float32 and bank.dim() == 1 and bank.is_contiguous()):
+            raise ValueError("the bank of responses is a contiguous 1-D float32 HIP device tensor")
+        ln = _per_clip(rir_len, N, wav.device, torch.int32, "rir_len")
+        pk = _per_clip(rir_peak, N, wav.device, torch.int32, "rir_peak")
+    else:
+        bank = None
+    if out is None:
+        out = torch.empty_like(wav)
+    if out.dim() != 2 or out.shape[0] != N or not out.is_contiguous() or out.dtype != torch.float32:
+        raise ValueError("out must be a contiguous float32 (N, ldo) tensor")
+    # the row length, not stride(0): a contiguous one-row view may carry any stride there
+    call("ds2_reverb", P(wav), wav.shape[1], P(ns), N, P(bank), bank.numel() if bank is not None else 0, P(off), P(ln), P(pk),
+         P(out), out.shape[1], S())
+    return out
+
+
 # ---- exact chunked inference (csrc/ds2_stream.hip, streaming.StreamingTranscriber(carry_context=True)) ----------------------
 STREAM_CONV_CARRY = 10     # positions both convolutions carry: their kernel width in time minus one
 

@@ -6,7 +6,8 @@ front-end's DFT GEMM is specialised for (the conv kernels take any bin count, ``
 to come from elsewhere); the window type follows ``SpectConfig.window`` (enums.py:8-14).  With ``augment=True`` the reference's
 ``spec_augment`` (loader/spec_augment.py:68-115, see ``augment.SpecAugment``) is folded into the same call.  A front-end built with
 ``wave_augment=augment.WaveAugment(...)`` first runs the loader's waveform augmentations (tempo, gain, noise injection,
-data_loader.py:151-159) on the device, so one call covers everything ``parse_audio`` does.  Waveforms at another sample rate
+data_loader.py:151-159) on the device, so one call covers everything ``parse_audio`` does; with a ``rir_bank`` it also
+reverberates clips between tempo and gain (``augment.RirBank``, the project's own addition).  Waveforms at another sample rate
 (``input_rate=44100``, ...) are converted to 16 kHz on the device in front of all that (``resample.Resampler``, DESIGN.md section
 7.2), one-shot and in ``stream()``.
 
@@ -232,8 +233,8 @@ class SpectrogramFrontEnd:
             call("ds2_spectrogram_aug", *head, ops.P(aug[0]), aug[1], ops.P(aug[2]), aug[3], ops.P(aug[4]), aug[5], ops.P(aug[6]), ops.S())
 
     def _call_wave_augmented(self, wav, ns, augment, wd=None):
-        """__call__ with the waveform augmentations in front: tempo (ds2_wsola), then gain / noise (ds2_wave_energy +
-        ds2_wave_mix), then the spectrogram call on the new buffer.  Frame counts, percentages and Tmax follow the lengths after
+        """__call__ with the waveform augmentations in front: tempo (ds2_wsola), then reverberation (ds2_reverb; it keeps every
+        length), then gain / noise (ds2_wave_energy + ds2_wave_mix), then the spectrogram call on the new buffer.  Frame counts, percentages and Tmax follow the lengths after
         the tempo change, which the host knows in closed form (augment.wsola_out_len): nothing is read back.  wd: the WaveDraws
         of these rows when they were drawn already (collate).  wav / ns are the 16 kHz signal: a front-end with input_rate has
         resampled before it comes here."""
@@ -246,11 +247,17 @@ class SpectrogramFrontEnd:
         frames = 1 + ns2.to(torch.int64) // HOP
         sa = self.spec_augment
         sdraws = list(sa.draw(frames.numpy(), N_BIN, self.rng)) if augment else []
-        views = self.upload_draws([ns.numpy()] + wd.arrays() + sdraws, dev)
+        views = self.upload_draws([ns.numpy()] + wd.arrays() + sdraws + wd.rir_arrays(), dev)
         ns_dev, (noise_off, tempo, gain, level, noise_start) = views[0], views[1:6]
+        rir_off, rir_len, rir_peak = views[-3:]
         offsets = None
         if tempo is not None:
             wav, ns_dev, offsets = ops.wsola(wav, ns_dev, tempo, Lm, int(wd.segments.max()))
+        if rir_off is not None:
+            rirs = wa.rir_bank.samples
+            if rirs.device != dev:
+                raise Ds2HipError("the bank of impulse responses lives on %s, the waveforms on %s" % (rirs.device, dev))
+            wav = ops.reverb(wav, ns_dev, rirs, rir_off, rir_len, rir_peak)
         if gain is not None or level is not None:
             bank = wa.noise_bank.samples if level is not None else None
             if bank is not None and bank.device != dev:
@@ -259,7 +266,7 @@ class SpectrogramFrontEnd:
         self.last_wave = (wd, offsets)
         out = torch.empty((N, 1, N_BIN, Tmax), dtype=torch.float32, device=dev)
         if augment:
-            warp, fmask, tmask = views[6:]
+            warp, fmask, tmask = views[6:9]
             self.last_coef = torch.empty((N, 3), dtype=torch.float32, device=dev)
             self._launch(wav, ns_dev, N, Lm, out, (warp, sa.W, fmask, sdraws[1].shape[1], tmask, sdraws[2].shape[1], self.last_coef))
         else:

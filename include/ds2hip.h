@@ -456,6 +456,28 @@ int ds2_wave_mix(const float* wav, long ldw, const int* nsamples, int N, const f
                  long bank_len, const long long* noise_off, const int* noise_start, const void* ws, float* out, long ldo,
                  ds2_stream_t stream);
 
+/* ---- reverberation (DESIGN.md section 7.1 "Reverberation"; the reference has none, the rule is the project's own): every clip
+ * convolved with its room impulse response, time-aligned on the response's direct-path tap.  For clip n with L = nsamples[n] samples
+ * x, a response h of K = rir_len[n] taps at bank[rir_off[n] ..] and its peak index p = rir_peak[n] (0 <= p < K):
+ *   out[i] = sum_{k = 0}^{K - 1} h[k] * x[i + p - k]   for 0 <= i < L,   x = 0 outside [0, L)
+ *   out[i] = 0                                         for L <= i < ldo
+ * so the output has the input's length and its timing (frame counts, transcripts, alignments and the noise step's data length do
+ * not change); the reverberant tail beyond the clip's end is cut.  All arithmetic is fp32 with fp32 accumulation, nothing is
+ * clamped.  Summation order of output i: acc = +0, then acc = fma(h[k], x[i + p - k], acc) over the blocks q = 0, 1, .. (K + 30) / 32
+ * of 32 taps in rising q, inside a block k = 32 q + (i mod 32) - r in rising r = 0 .. 31 (k falls); a k outside [0, K) enters
+ * as h = 0.  The order depends on i mod 32 and K alone -- never on the row, N, ldw / ldo or the other rows --, no atomics, no sum
+ * is split: a clip's output bits are the same wherever it sits.  (Adding to +0 turns a -0 sample into +0.)
+ *   bank: bank_len f32 on the device, the responses back to back; reads outside the bank are zero
+ *   rir_off [N] int64, rir_len / rir_peak [N] int32 (device).  rir_off[n] < 0: the clip is copied bit for bit (zeros beyond L);
+ *   a null rir_off copies every clip (bank / rir_len / rir_peak unused).  rir_len[n] < 1 gives zeros.
+ * The kernel is the direct-form FIR as a block-Toeplitz product on v_mfma_f32_32x32x2_f32; a row costs its own K, a copied row
+ * nothing.  ds2_reverb_tile(): the consecutive outputs one workgroup computes (host-only query).
+ * DS2_ERR_ARG: a null wav, nsamples or out, wav == out, N < 1 or > 65535, ldw or ldo < 1, a rir_off without bank, rir_len or
+ * rir_peak; nothing is launched then. */
+int ds2_reverb_tile(void);
+int ds2_reverb(const float* wav, long ldw, const int* nsamples, int N, const float* bank, long bank_len, const long long* rir_off,
+               const int* rir_len, const int* rir_peak, float* out, long ldo, ds2_stream_t stream);
+
 /* ---- rational polyphase resampling to 16 kHz (the reference converts its corpora with sox `rate` offline).
  * g = gcd(in_rate, 16000), U = 16000 / g, D = in_rate / g, W = the half-width in input samples, taps [U][2W] f32 on the device,
  * 8-byte aligned, U * 2W * 4 <= 128 KiB (resample.Resampler builds them on the host in fp64).  Output m of a clip x of n samples:
