@@ -165,6 +165,10 @@ SIGNATURES = {
     "ds2_error_counts": (_i, [_vp, _l, _vp, _i, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ds2_ctc_ws_floats": (_l, [_i, _i, _i, _i]),
     "ds2_ctc_loss_grad": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _vp, _vp, _vp, _l, _vp, _i, _vp]),
+    "ds2_ctc_multi_ws_floats": (_l, [_i, _i, _i, _i, _i, _i]),
+    "ds2_ctc_multi_forward": (_i, [_vp, _l, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    "ds2_ctc_multi_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp, _l, _vp, _vp]),
+    "ds2_mwer_weights": (_i, [_vp, _vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "ds2_ctc_align_ws_bytes": (_l, [_i, _i, _i]),
     "ds2_ctc_align": (_i, [_vp, _l, _l, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ds2_confidence_ws_bytes": (_l, [_i, _i]),

@@ -18,7 +18,7 @@ LIB = os.path.join(HERE, "libds2hip.so")
 SOURCES = ["ds2_norm.hip", "ds2_gemm.hip", "ds2_gemm8.hip", "ds2_rnn.hip", "ds2_rnn_persist.hip", "ds2_rnn_persist_gru.hip",
            "ds2_rnn_persist_lstm.hip", "ds2_rnn_persist_rnn.hip", "ds2_conv.hip", "ds2_ctc.hip", "ds2_seqops.hip", "ds2_decode.hip",
            "ds2_beam.hip", "ds2_errors.hip", "ds2_optim.hip", "ds2_spect.hip", "ds2_waveaug.hip", "ds2_align.hip", "ds2_fc.hip", "ds2_stream.hip",
-           "ds2_resample.hip", "ds2_endpoint.hip", "ds2_confidence.hip", "ds2_kws.hip", "ds2_reverb.hip"]
+           "ds2_resample.hip", "ds2_endpoint.hip", "ds2_confidence.hip", "ds2_kws.hip", "ds2_reverb.hip", "ds2_mwer.hip"]
 # the general persistent recurrent kernels: instantiation source -> its table in ds2_rnn_persist_widths.h; one object per row
 INSTANCES = {"ds2_rnn_persist3_inst.hip": "DS2_PERSIST3_WIDTHS", "ds2_rnn_persist2_inst.hip": "DS2_PERSIST2_INSTANCES"}
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -57,6 +57,29 @@ __device__ __forceinline__ float lse2(float a, float b) {
   return add_ln_1to3(ms, __expf(a - ms) + __expf(b - ms));
 }
 
+// Multi-hypothesis form (ds2_ctc_multi_forward / _backward; MULTI = true): R label rows per clip scored against the clip's one
+// log-prob scratch.  Rows are rank-major, p = r * N + n (the convention of ds2_error_counts): the recursion grids gain a z dimension,
+// blockIdx.x stays the clip n (frames, log-probs) and blockIdx.z is the rank r; the row p indexes the labels, the alpha / beta rows,
+// nll and ll.  A row is absent when its length is negative (one longer than max_target_len, which sized the alpha / beta rows, is
+// treated the same: nothing is written past a row); absent and infeasible rows and clips without frames report nll = +inf
+// (the caller's softmax over a clip's rows needs it) where the single-sequence form reports zero_infinity's 0.  A null ws_alpha
+// (forward only) keeps no rows.  With MULTI = false every kernel below is what ds2_ctc_loss_grad has always launched.
+template <bool MULTI>
+__device__ __forceinline__ int ctc_row() {
+  if constexpr (MULTI) return blockIdx.z * gridDim.x + blockIdx.x;
+  return blockIdx.x;
+}
+template <bool MULTI>
+__device__ __forceinline__ void ctc_no_paths(float* __restrict__ nll_out, float* __restrict__ ws_ll, int p) {
+  nll_out[p] = MULTI ? INFINITY : 0.f;
+  ws_ll[p] = INFINITY;                               // sentinel: no gradient for this row
+}
+template <bool MULTI>
+__device__ __forceinline__ void ctc_finish(float* __restrict__ nll_out, float* __restrict__ ws_ll, int p, bool feasible, float ll) {
+  nll_out[p] = feasible ? -ll : MULTI ? INFINITY : 0.f;
+  ws_ll[p] = feasible ? ll : INFINITY;
+}
+
 template <int CP>
 __global__ void __launch_bounds__(256) k_ctc_logsoftmax(const float* __restrict__ logits, long ldl,
                                                         const int* __restrict__ in_len, int Tp, int N, int C,
@@ -94,7 +117,7 @@ __global__ void __launch_bounds__(256) k_ctc_logsoftmax(const float* __restrict_
 }
 
 // blockIdx.x = sample, blockIdx.y = 0: alpha (t = 0 .. Ti-1), 1: beta (t = Ti-1 .. 0)
-template <int CP>
+template <int CP, bool MULTI = false>
 __global__ void __launch_bounds__(REC_THREADS) k_ctc_recursion(const int* __restrict__ targets, const int* __restrict__ toff,
                                                                const int* __restrict__ in_len, const int* __restrict__ tg_len,
                                                                int Tp, int blank, int Lmax, float* __restrict__ nll_out,
@@ -106,22 +129,20 @@ __global__ void __launch_bounds__(REC_THREADS) k_ctc_recursion(const int* __rest
   int* ext = reinterpret_cast<int*>(row1 + Lmax);    // [Lmax]
   float* lpl = reinterpret_cast<float*>(ext + Lmax); // [2 chunk buffers][LP_CHUNK][CP]: staged log-prob rows
   const int tid = threadIdx.x;
-  const int n = blockIdx.x;
+  const int n = blockIdx.x, p = ctc_row<MULTI>();
   const bool is_beta = blockIdx.y != 0;
+  const bool keep = !MULTI || ws_alpha != nullptr;
   int Ti = in_len[n];
   if (Ti > Tp) Ti = Tp;
-  const int S = tg_len[n];
+  const int S = tg_len[p];
   const int L = 2 * S + 1;
-  if (Ti <= 0) {
-    if (!is_beta && tid == 0) {
-      nll_out[n] = 0.f;
-      ws_ll[n] = INFINITY;                           // sentinel: no gradient for this sample
-    }
+  if (Ti <= 0 || (MULTI && (S < 0 || 2 * S + 2 > Lmax))) {
+    if (!is_beta && tid == 0) ctc_no_paths<MULTI>(nll_out, ws_ll, p);
     return;
   }
-  const int* tg = targets + toff[n];
+  const int* tg = targets + toff[p];
   const float* lp = ws_lp + (long)n * Tp * CP;                               // [Tp][CP] of this sample
-  float* dst = (is_beta ? ws_beta : ws_alpha) + (long)n * Tp * Lmax;         // [Tp][Lmax]
+  float* dst = (is_beta ? ws_beta : ws_alpha) + (long)p * Tp * Lmax;         // [Tp][Lmax]
   for (int s = tid; s < L; s += REC_THREADS) ext[s] = (s & 1) ? tg[s >> 1] : blank;
   constexpr int PE = LP_CHUNK * CP / REC_THREADS;    // elements of a chunk [LP_CHUNK][CP] each thread stages (1 for CP = 32)
   static_assert(PE * REC_THREADS == LP_CHUNK * CP, "whole prefetch elements per thread");
@@ -199,7 +220,7 @@ __global__ void __launch_bounds__(REC_THREADS) k_ctc_recursion(const int* __rest
             const float rec = lse3(p0[q], p1[q] + st_m1[q], p2[q] + st_m2[q]);
             const float v = (i == 0 ? st_m0[q] : rec) + pe[q];
             cur[st_s[q]] = v;
-            dst[(long)t * Lmax + st_s[q]] = v;
+            if (keep) dst[(long)t * Lmax + st_s[q]] = v;
           }
       } else {
         // very long targets (> 511 labels): strided states, same arithmetic
@@ -221,7 +242,7 @@ __global__ void __launch_bounds__(REC_THREADS) k_ctc_recursion(const int* __rest
             v = lse3(b0, b1, b2) + lpt[e];
           }
           cur[s] = v;
-          dst[(long)t * Lmax + s] = v;
+          if (keep) dst[(long)t * Lmax + s] = v;
         }
       }
       lds_barrier();
@@ -242,8 +263,7 @@ __global__ void __launch_bounds__(REC_THREADS) k_ctc_recursion(const int* __rest
     // gradient.  A NaN (poisoned logits, e.g. from a timed-out recurrent sweep) stays NaN in the loss and in the gradient,
     // as torch's ctc_loss does: it must never look like a sample that contributes nothing.
     const bool feasible = L <= 2 * Ti + 1 && ll != -INFINITY;
-    nll_out[n] = feasible ? -ll : 0.f;
-    ws_ll[n] = feasible ? ll : INFINITY;
+    ctc_finish<MULTI>(nll_out, ws_ll, p, feasible, ll);
   }
 }
 
@@ -408,26 +428,23 @@ __global__ void __launch_bounds__(64) k_ctc_recursion_wave(const int* __restrict
 // on the recursion: each lane gathers its two log-probs of a whole chunk of K steps from global memory one chunk ahead (the
 // sample's log-prob rows are L2-resident), so there is no class-row staging and no class-count limit.  Same lse3 / lse2 terms in the
 // same order as the kernels above: bit-identical rows.
-template <int K, bool is_beta>
+template <int K, bool is_beta, bool MULTI>
 __device__ __forceinline__ void ctc_recursion_pairs(const int* __restrict__ targets, const int* __restrict__ toff,
                                                     const int* __restrict__ in_len, const int* __restrict__ tg_len, int Tp, int blank,
                                                     int LS, int CP, float* __restrict__ nll_out, const float* __restrict__ ws_lp,
                                                     float* __restrict__ ws_alpha, float* __restrict__ ws_beta,
                                                     float* __restrict__ ws_ll, float (*xch)[16][K][2], float* fin) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, W = blockDim.x >> 6;
-  const int n = blockIdx.x;
+  const int n = blockIdx.x, p = ctc_row<MULTI>();
   int Ti = in_len[n];
   if (Ti > Tp) Ti = Tp;
-  const int S = tg_len[n];
+  const int S = tg_len[p];
   const int L = 2 * S + 1;
-  if (Ti <= 0) {
-    if (!is_beta && threadIdx.x == 0) {
-      nll_out[n] = 0.f;
-      ws_ll[n] = INFINITY;
-    }
+  if (Ti <= 0 || (MULTI && (S < 0 || 2 * S + 2 > LS))) {
+    if (!is_beta && threadIdx.x == 0) ctc_no_paths<MULTI>(nll_out, ws_ll, p);
     return;
   }
-  const int* tg = targets + toff[n];
+  const int* tg = targets + toff[p];
   const int P = w * (64 - K) + lane;                 // pair index in traversal order
   const bool own = w == 0 || lane >= K;
   const int lab = P < S ? tg[is_beta ? S - 1 - P : P] : blank;
@@ -437,10 +454,10 @@ __device__ __forceinline__ void ctc_recursion_pairs(const int* __restrict__ targ
   // A pair is ONE 8-byte store: rows have an even stride LS = 2 S_max + 2 and the beta rows start one float late (the host passes
   // ws_beta + 1), so alpha's {2P, 2P + 1} and beta's {L - 2 - 2P, L - 1 - 2P} are both 8-byte aligned; the label half of pair S (it
   // does not exist) lands in the row's pad slot.
-  const bool st = own && 2 * P < L;
+  const bool st = own && 2 * P < L && (!MULTI || ws_alpha != nullptr);
   const int sp = is_beta ? L - 2 - 2 * P : 2 * P;
   const float* lp = ws_lp + (long)n * Tp * CP;
-  float* dst = (is_beta ? ws_beta : ws_alpha) + (long)n * Tp * LS;
+  float* dst = (is_beta ? ws_beta : ws_alpha) + (long)p * Tp * LS;
   const long tstep = is_beta ? -1 : 1;
   const int t0 = is_beta ? Ti - 1 : 0;
   // step 0: the first blank and the first label
@@ -516,8 +533,7 @@ __device__ __forceinline__ void ctc_recursion_pairs(const int* __restrict__ targ
       const float l2 = L > 1 ? fin[1] : -INFINITY;
       const float ll = lse3(l1, l2, -INFINITY);
       const bool feasible = L <= 2 * Ti + 1 && ll != -INFINITY;      // zero_infinity: only an infinite loss is zeroed (see above)
-      nll_out[n] = feasible ? -ll : 0.f;
-      ws_ll[n] = feasible ? ll : INFINITY;
+      ctc_finish<MULTI>(nll_out, ws_ll, p, feasible, ll);
     }
   }
 }
@@ -526,7 +542,7 @@ __device__ __forceinline__ void ctc_recursion_pairs(const int* __restrict__ targ
 #endif
 constexpr int PAIRS_K = DS2_PAIRS_K;
 // blockIdx.x = sample, blockIdx.y = 0: alpha, 1: beta (the direction is a template parameter of the body: no per-step selects)
-template <int K>
+template <int K, bool MULTI = false>
 __global__ void __launch_bounds__(1024) k_ctc_recursion_pairs(const int* __restrict__ targets, const int* __restrict__ toff,
                                                               const int* __restrict__ in_len, const int* __restrict__ tg_len,
                                                               int Tp, int blank, int LS, int CP, float* __restrict__ nll_out,
@@ -535,9 +551,9 @@ __global__ void __launch_bounds__(1024) k_ctc_recursion_pairs(const int* __restr
   __shared__ float xch[2][16][K][2];                 // [chunk parity][wave][halo lane]{blank, label}
   __shared__ float fin[2];
   if (blockIdx.y == 0)
-    ctc_recursion_pairs<K, false>(targets, toff, in_len, tg_len, Tp, blank, LS, CP, nll_out, ws_lp, ws_alpha, ws_beta, ws_ll, xch, fin);
+    ctc_recursion_pairs<K, false, MULTI>(targets, toff, in_len, tg_len, Tp, blank, LS, CP, nll_out, ws_lp, ws_alpha, ws_beta, ws_ll, xch, fin);
   else
-    ctc_recursion_pairs<K, true>(targets, toff, in_len, tg_len, Tp, blank, LS, CP, nll_out, ws_lp, ws_alpha, ws_beta, ws_ll, xch, fin);
+    ctc_recursion_pairs<K, true, MULTI>(targets, toff, in_len, tg_len, Tp, blank, LS, CP, nll_out, ws_lp, ws_alpha, ws_beta, ws_ll, xch, fin);
 }
 constexpr int PAIRS_MAX_WAVES = 16;
 // waves a recursion over targets of up to `max_target_len` labels needs (max_target_len + 1 pairs)
@@ -548,7 +564,10 @@ static int pairs_waves(int max_target_len) {
 
 // grid (ceil(Tp / GRAD_FRAMES), N); one wave per frame.  Writes EVERY row of dlogits of its frames (zeros past the
 // sample's length and for infeasible samples).
-template <int CP>
+// MULTI: the clip's R rows p = r * N + n go into the one per-wave class accumulator in increasing r, each term times weights[p]
+// (rows without paths, ll = +inf, are skipped before their weight is read); -a / y and the softmax backward then run once.  The
+// LDS atomics stay those of ONE wave, row after row, so the order of additions is fixed.
+template <int CP, bool MULTI = false>
 __global__ void __launch_bounds__(GRAD_WAVES * 64) k_ctc_gradient(const int* __restrict__ targets, const int* __restrict__ toff,
                                                                   const int* __restrict__ in_len,
                                                                   const int* __restrict__ tg_len, int Tp, int N, int C,
@@ -557,16 +576,16 @@ __global__ void __launch_bounds__(GRAD_WAVES * 64) k_ctc_gradient(const int* __r
                                                                   const float* __restrict__ ws_lp,
                                                                   const float* __restrict__ ws_alpha,
                                                                   const float* __restrict__ ws_beta,
-                                                                  const float* __restrict__ ws_ll) {
+                                                                  const float* __restrict__ ws_ll,
+                                                                  const float* __restrict__ weights, int R) {
   __shared__ float acc[GRAD_WAVES][CP];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int n = blockIdx.y;
   int Ti = in_len[n];
   if (Ti > Tp) Ti = Tp;
-  const int L = 2 * tg_len[n] + 1;
-  const int* tg = targets + toff[n];
-  const float ll = ws_ll[n];
-  const bool live = ll != INFINITY;
+  const int rows = MULTI ? R : 1;
+  bool live = false;
+  for (int r = 0; r < rows; ++r) live |= ws_ll[(long)r * N + n] != INFINITY;
   float* wacc = acc[wave];
   const int t_end = min((int)(blockIdx.x + 1) * GRAD_FRAMES, Tp);
   for (int t = blockIdx.x * GRAD_FRAMES + wave; t < t_end; t += GRAD_WAVES) {
@@ -576,17 +595,26 @@ __global__ void __launch_bounds__(GRAD_WAVES * 64) k_ctc_gradient(const int* __r
       continue;
     }
     const float* lpt = ws_lp + ((long)n * Tp + t) * CP;
-    const float* al = ws_alpha + ((long)n * Tp + t) * Lmax;
-    const float* be = ws_beta + ((long)n * Tp + t) * Lmax;
     for (int c = lane; c < CP; c += 64) wacc[c] = 0.f;
     __builtin_amdgcn_wave_barrier();
     float blank_part = 0.f;
-    for (int s = lane; s < L; s += 64) {
-      const float w = expf(al[s] + be[s] - ll);      // <= 1
-      if (s & 1)
-        atomicAdd(&wacc[tg[s >> 1]], w);             // within one wave: the order is fixed
-      else
-        blank_part += w;
+    for (int r = 0; r < rows; ++r) {
+      const long p = (long)r * N + n;
+      const float ll = ws_ll[p];
+      if (MULTI && ll == INFINITY) continue;         // wave-uniform
+      const float wgt = MULTI ? weights[p] : 1.f;
+      const int L = 2 * tg_len[p] + 1;
+      const int* tg = targets + toff[p];
+      const float* al = ws_alpha + (p * Tp + t) * Lmax;
+      const float* be = ws_beta + (p * Tp + t) * Lmax;
+      for (int s = lane; s < L; s += 64) {
+        float w = expf(al[s] + be[s] - ll);          // <= 1
+        if (MULTI) w *= wgt;
+        if (s & 1)
+          atomicAdd(&wacc[tg[s >> 1]], w);           // within one wave: the order is fixed
+        else
+          blank_part += w;
+      }
     }
     blank_part = wave_sum(blank_part);
     __builtin_amdgcn_wave_barrier();
@@ -600,7 +628,7 @@ __global__ void __launch_bounds__(GRAD_WAVES * 64) k_ctc_gradient(const int* __r
         float a = wacc[c];
         if (c == blank) a += blank_part;
         y[j] = expf(lpt[c]);
-        g[j] = a > 0.f ? -a / y[j] : 0.f;
+        g[j] = (MULTI ? a != 0.f : a > 0.f) ? -a / y[j] : 0.f;       // weighted sums have either sign
       }
       gpart += g[j];
     }
@@ -642,6 +670,7 @@ __global__ void __launch_bounds__(256) k_ctc_logsoftmax_big(const float* __restr
   for (int c = lane; c < C; c += 64) lp[c] = x[c] - lz;
 }
 
+template <bool MULTI = false>
 __global__ void __launch_bounds__(REC_THREADS) k_ctc_recursion_big(const int* __restrict__ targets, const int* __restrict__ toff,
                                                                    const int* __restrict__ in_len, const int* __restrict__ tg_len,
                                                                    int Tp, int blank, int Lmax, int ldp, float* __restrict__ nll_out,
@@ -651,21 +680,19 @@ __global__ void __launch_bounds__(REC_THREADS) k_ctc_recursion_big(const int* __
   float* prev = reinterpret_cast<float*>(smem);
   float* cur = prev + Lmax;
   int* ext = reinterpret_cast<int*>(cur + Lmax);
-  const int tid = threadIdx.x, n = blockIdx.x;
+  const int tid = threadIdx.x, n = blockIdx.x, p = ctc_row<MULTI>();
   const bool is_beta = blockIdx.y != 0;
+  const bool keep = !MULTI || ws_alpha != nullptr;
   int Ti = in_len[n];
   if (Ti > Tp) Ti = Tp;
-  const int S = tg_len[n], L = 2 * S + 1;
-  if (Ti <= 0) {
-    if (!is_beta && tid == 0) {
-      nll_out[n] = 0.f;
-      ws_ll[n] = INFINITY;
-    }
+  const int S = tg_len[p], L = 2 * S + 1;
+  if (Ti <= 0 || (MULTI && (S < 0 || 2 * S + 2 > Lmax))) {
+    if (!is_beta && tid == 0) ctc_no_paths<MULTI>(nll_out, ws_ll, p);
     return;
   }
-  const int* tg = targets + toff[n];
+  const int* tg = targets + toff[p];
   const float* lp = ws_lp + (long)n * Tp * ldp;
-  float* dst = (is_beta ? ws_beta : ws_alpha) + (long)n * Tp * Lmax;
+  float* dst = (is_beta ? ws_beta : ws_alpha) + (long)p * Tp * Lmax;
   for (int s = tid; s < L; s += REC_THREADS) ext[s] = (s & 1) ? tg[s >> 1] : blank;
   __syncthreads();
   for (int i = 0; i < Ti; ++i) {
@@ -689,7 +716,7 @@ __global__ void __launch_bounds__(REC_THREADS) k_ctc_recursion_big(const int* __
         v = lse3(b0, b1, b2) + lpt[e];
       }
       cur[s] = v;
-      dst[(long)t * Lmax + s] = v;
+      if (keep) dst[(long)t * Lmax + s] = v;
     }
     lds_barrier();
     float* tmp = prev;
@@ -701,28 +728,28 @@ __global__ void __launch_bounds__(REC_THREADS) k_ctc_recursion_big(const int* __
     const float l2 = L > 1 ? prev[L - 2] : -INFINITY;
     const float ll = lse3(l1, l2, -INFINITY);
     const bool feasible = L <= 2 * Ti + 1 && ll != -INFINITY;      // zero_infinity: see k_ctc_recursion
-    nll_out[n] = feasible ? -ll : 0.f;
-    ws_ll[n] = feasible ? ll : INFINITY;
+    ctc_finish<MULTI>(nll_out, ws_ll, p, feasible, ll);
   }
 }
 
-// grid (ceil(Tp / GRAD_FRAMES), N); one wave per frame; dynamic LDS: GRAD_WAVES x ldp floats
+// grid (ceil(Tp / GRAD_FRAMES), N); one wave per frame; dynamic LDS: GRAD_WAVES x ldp floats.  MULTI: see k_ctc_gradient
+template <bool MULTI = false>
 __global__ void __launch_bounds__(GRAD_WAVES * 64) k_ctc_gradient_big(const int* __restrict__ targets, const int* __restrict__ toff,
                                                                       const int* __restrict__ in_len, const int* __restrict__ tg_len,
                                                                       int Tp, int N, int C, int blank, int Lmax, int ldp, float grad_scale,
                                                                       float* __restrict__ dlogits, long ldg, const float* __restrict__ ws_lp,
                                                                       const float* __restrict__ ws_alpha, const float* __restrict__ ws_beta,
-                                                                      const float* __restrict__ ws_ll) {
+                                                                      const float* __restrict__ ws_ll, const float* __restrict__ weights,
+                                                                      int R) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float* wacc = reinterpret_cast<float*>(smem) + (long)wave * ldp;
   const int n = blockIdx.y;
   int Ti = in_len[n];
   if (Ti > Tp) Ti = Tp;
-  const int L = 2 * tg_len[n] + 1;
-  const int* tg = targets + toff[n];
-  const float ll = ws_ll[n];
-  const bool live = ll != INFINITY;
+  const int rows = MULTI ? R : 1;
+  bool live = false;
+  for (int r = 0; r < rows; ++r) live |= ws_ll[(long)r * N + n] != INFINITY;
   const int t_end = min((int)(blockIdx.x + 1) * GRAD_FRAMES, Tp);
   for (int t = blockIdx.x * GRAD_FRAMES + wave; t < t_end; t += GRAD_WAVES) {
     float* dl = dlogits + ((long)t * N + n) * ldg;
@@ -731,17 +758,26 @@ __global__ void __launch_bounds__(GRAD_WAVES * 64) k_ctc_gradient_big(const int*
       continue;
     }
     const float* lpt = ws_lp + ((long)n * Tp + t) * ldp;
-    const float* al = ws_alpha + ((long)n * Tp + t) * Lmax;
-    const float* be = ws_beta + ((long)n * Tp + t) * Lmax;
     for (int c = lane; c < ldp; c += 64) wacc[c] = 0.f;
     __builtin_amdgcn_wave_barrier();
     float blank_part = 0.f;
-    for (int s = lane; s < L; s += 64) {
-      const float w = expf(al[s] + be[s] - ll);      // <= 1
-      if (s & 1)
-        atomicAdd(&wacc[tg[s >> 1]], w);             // LDS atomics of one wave; a class that occurs in several states of one
-      else                                           // 64-state pass is summed in the hardware's lane order (fixed)
-        blank_part += w;
+    for (int r = 0; r < rows; ++r) {
+      const long p = (long)r * N + n;
+      const float ll = ws_ll[p];
+      if (MULTI && ll == INFINITY) continue;         // wave-uniform
+      const float wgt = MULTI ? weights[p] : 1.f;
+      const int L = 2 * tg_len[p] + 1;
+      const int* tg = targets + toff[p];
+      const float* al = ws_alpha + (p * Tp + t) * Lmax;
+      const float* be = ws_beta + (p * Tp + t) * Lmax;
+      for (int s = lane; s < L; s += 64) {
+        float w = expf(al[s] + be[s] - ll);          // <= 1
+        if (MULTI) w *= wgt;
+        if (s & 1)
+          atomicAdd(&wacc[tg[s >> 1]], w);           // LDS atomics of one wave; a class that occurs in several states of one
+        else                                         // 64-state pass is summed in the hardware's lane order (fixed)
+          blank_part += w;
+      }
     }
     blank_part = wave_sum(blank_part);
     __builtin_amdgcn_wave_barrier();
@@ -750,7 +786,7 @@ __global__ void __launch_bounds__(GRAD_WAVES * 64) k_ctc_gradient_big(const int*
       float a = wacc[c];
       if (c == blank) a += blank_part;
       const float y = expf(lpt[c]);
-      const float g = a > 0.f ? -a / y : 0.f;
+      const float g = (MULTI ? a != 0.f : a > 0.f) ? -a / y : 0.f;
       wacc[c] = g;                                   // the lane's own class: reused as its g
       gpart += g;
     }
@@ -810,11 +846,11 @@ int ds2_ctc_loss_grad(const float* logits, long ldl, const int* targets, const i
     DS2_REQUIRE(shm_r <= 160 * 1024 && shm_g <= 160 * 1024, DS2_ERR_ARG);
     static size_t attr_r[DS2_MAX_DEVICES], attr_g[DS2_MAX_DEVICES];
     if (attr_r[dev] < shm_r) {
-      (void)hipFuncSetAttribute((const void*)k_ctc_recursion_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_r);
+      (void)hipFuncSetAttribute((const void*)k_ctc_recursion_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_r);
       attr_r[dev] = shm_r;
     }
     if (attr_g[dev] < shm_g) {
-      (void)hipFuncSetAttribute((const void*)k_ctc_gradient_big, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_g);
+      (void)hipFuncSetAttribute((const void*)k_ctc_gradient_big<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_g);
       attr_g[dev] = shm_g;
     }
     hipLaunchKernelGGL(k_ctc_logsoftmax_big, dim3(ds2_cdiv((long)Tp * N, 4)), dim3(256), 0, st, logits, ldl, input_lengths, Tp, N, C, CP, ws_lp);
@@ -823,11 +859,12 @@ int ds2_ctc_loss_grad(const float* logits, long ldl, const int* targets, const i
       hipLaunchKernelGGL(k_ctc_recursion_pairs<PAIRS_K>, dim3(N, 2), dim3(64 * pw), 0, st, targets, target_offsets, input_lengths, target_lengths,
                          Tp, blank, Lmax, CP, nll, ws_lp, ws_alpha, ws_beta, ws_ll);
     else
-      hipLaunchKernelGGL(k_ctc_recursion_big, dim3(N, 2), dim3(REC_THREADS), shm_r, st, targets, target_offsets, input_lengths, target_lengths,
+      hipLaunchKernelGGL(k_ctc_recursion_big<false>, dim3(N, 2), dim3(REC_THREADS), shm_r, st, targets, target_offsets, input_lengths, target_lengths,
                          Tp, blank, Lmax, CP, nll, ws_lp, ws_alpha, ws_beta, ws_ll);
     DS2_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_ctc_gradient_big, dim3(ds2_cdiv(Tp, GRAD_FRAMES), N), dim3(GRAD_WAVES * 64), shm_g, st, targets, target_offsets,
-                       input_lengths, target_lengths, Tp, N, C, blank, Lmax, CP, grad_scale, dlogits, ldg, ws_lp, ws_alpha, ws_beta, ws_ll);
+    hipLaunchKernelGGL(k_ctc_gradient_big<false>, dim3(ds2_cdiv(Tp, GRAD_FRAMES), N), dim3(GRAD_WAVES * 64), shm_g, st, targets, target_offsets,
+                       input_lengths, target_lengths, Tp, N, C, blank, Lmax, CP, grad_scale, dlogits, ldg, ws_lp, ws_alpha, ws_beta, ws_ll,
+                       (const float*)nullptr, 1);
     DS2_CHECK_LAUNCH();
     hipLaunchKernelGGL(k_sum_small, dim3(1), dim3(64), 0, st, nll, N, loss_sum);
     DS2_CHECK_LAUNCH();
@@ -869,7 +906,7 @@ int ds2_ctc_loss_grad(const float* logits, long ldl, const int* targets, const i
     DS2_CHECK_LAUNCH();                                                                                                             \
     hipLaunchKernelGGL(k_ctc_gradient<CPT>, dim3(ds2_cdiv(Tp, GRAD_FRAMES), N), dim3(GRAD_WAVES * 64), 0, st, targets,              \
                        target_offsets, input_lengths, target_lengths, Tp, N, C, blank, Lmax, grad_scale, dlogits, ldg, ws_lp,       \
-                       ws_alpha, ws_beta, ws_ll);                                                                                   \
+                       ws_alpha, ws_beta, ws_ll, (const float*)nullptr, 1);                                                         \
     DS2_CHECK_LAUNCH();                                                                                                             \
   }
   if (CP == 32) DS2_CTC_LAUNCH(32, 0)
@@ -878,6 +915,133 @@ int ds2_ctc_loss_grad(const float* logits, long ldl, const int* targets, const i
   else DS2_CTC_LAUNCH(256, 3)
 #undef DS2_CTC_LAUNCH
   hipLaunchKernelGGL(k_sum_small, dim3(1), dim3(64), 0, st, nll, N, loss_sum);
+  DS2_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---- multi-hypothesis CTC: R label rows per clip against the clip's one log-softmax ------------------------------------------
+// Workspace: [N][Tp][CP] log-probs | ll of the P = R N rows (padded to an even count) | with want_grad the alpha rows [P][Tp][LS],
+// one float, the beta rows [P][Tp][LS], one float (LS = 2 max_target_len + 2; the beta rows start one float late, see
+// ds2_ctc_loss_grad).  The forward-only form needs the first two parts alone.
+struct CtcMultiWs {
+  float *lp, *ll, *alpha, *beta;
+};
+static bool ctc_multi_args(int Tp, int N, int R, int C, int max_target_len) {
+  return Tp > 0 && N > 0 && R > 0 && R <= 65535 && C > 0 && C <= CTC_MAX_CLASSES && max_target_len >= 0 && (long)R * N <= 0x7fffffffL;
+}
+static CtcMultiWs ctc_multi_ws(float* ws, int Tp, int N, int R, int C, int max_target_len, int want_grad) {
+  const long P = (long)R * N, LS = 2L * max_target_len + 2;
+  CtcMultiWs w;
+  w.lp = ws;
+  w.ll = ws + (long)N * Tp * ctc_class_stride(C);
+  w.alpha = want_grad ? w.ll + (P + 1) / 2 * 2 : nullptr;
+  w.beta = want_grad ? w.alpha + P * Tp * LS + 1 : nullptr;
+  return w;
+}
+
+long ds2_ctc_multi_ws_floats(int Tp, int N, int R, int C, int max_target_len, int want_grad) {
+  if (!ctc_multi_args(Tp, N, R, C, max_target_len)) return -1;
+  const long P = (long)R * N, LS = 2L * max_target_len + 2;
+  return (long)N * Tp * ctc_class_stride(C) + (P + 1) / 2 * 2 + (want_grad ? 2 * P * Tp * LS + 2 : 0);
+}
+
+int ds2_ctc_multi_forward(const float* logits, long ldl, const int* targets, const int* target_offsets, const int* target_lengths,
+                          const int* input_lengths, int Tp, int N, int R, int C, int blank, int max_target_len, int want_grad,
+                          float* nll, float* ws, int recursion, ds2_stream_t st_) {
+  hipStream_t st = (hipStream_t)st_;
+  DS2_REQUIRE(ctc_multi_args(Tp, N, R, C, max_target_len) && blank >= 0 && blank < C && ldl >= C, DS2_ERR_ARG);
+  DS2_REQUIRE(recursion == 0 || recursion == 1, DS2_ERR_ARG);
+  DS2_REQUIRE(logits && targets && target_offsets && target_lengths && input_lengths && nll && ws, DS2_ERR_ARG);
+  const int pw = pairs_waves(max_target_len);
+  const bool pairs = recursion == 0 && pw <= PAIRS_MAX_WAVES;
+  const int CP = ctc_class_stride(C);
+  const int Lmax = 2 * max_target_len + 2;
+  const CtcMultiWs w = ctc_multi_ws(ws, Tp, N, R, C, max_target_len, want_grad);
+  const dim3 grid(N, want_grad ? 2 : 1, R);          // (clip, direction, rank); forward only: alpha alone
+  int dev = 0;
+  (void)hipGetDevice(&dev);
+  dev = dev >= 0 && dev < DS2_MAX_DEVICES ? dev : 0;
+  if (C > 256) {
+    const size_t shm_r = (size_t)Lmax * 12;
+    DS2_REQUIRE(shm_r <= 160 * 1024, DS2_ERR_ARG);
+    static size_t attr_r[DS2_MAX_DEVICES];
+    if (attr_r[dev] < shm_r) {
+      (void)hipFuncSetAttribute((const void*)k_ctc_recursion_big<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_r);
+      attr_r[dev] = shm_r;
+    }
+    hipLaunchKernelGGL(k_ctc_logsoftmax_big, dim3(ds2_cdiv((long)Tp * N, 4)), dim3(256), 0, st, logits, ldl, input_lengths, Tp, N, C, CP, w.lp);
+    DS2_CHECK_LAUNCH();
+    if (pairs)
+      hipLaunchKernelGGL((k_ctc_recursion_pairs<PAIRS_K, true>), grid, dim3(64 * pw), 0, st, targets, target_offsets, input_lengths,
+                         target_lengths, Tp, blank, Lmax, CP, nll, w.lp, w.alpha, w.beta, w.ll);
+    else
+      hipLaunchKernelGGL(k_ctc_recursion_big<true>, grid, dim3(REC_THREADS), shm_r, st, targets, target_offsets, input_lengths,
+                         target_lengths, Tp, blank, Lmax, CP, nll, w.lp, w.alpha, w.beta, w.ll);
+    DS2_CHECK_LAUNCH();
+    return 0;
+  }
+  const size_t shm = (size_t)Lmax * 12 + 2 * LP_CHUNK * CP * 4;
+  DS2_REQUIRE(shm <= 160 * 1024, DS2_ERR_ARG);
+#define DS2_CTC_MULTI_FWD(CPT)                                                                                                      \
+  {                                                                                                                                 \
+    static size_t attr[DS2_MAX_DEVICES];                                                                                            \
+    if (attr[dev] < shm) {                                                                                                          \
+      (void)hipFuncSetAttribute((const void*)k_ctc_recursion<CPT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);     \
+      attr[dev] = shm;                                                                                                              \
+    }                                                                                                                               \
+    hipLaunchKernelGGL(k_ctc_logsoftmax<CPT>, dim3(ds2_cdiv((long)Tp * N, 256)), dim3(256), 0, st, logits, ldl, input_lengths, Tp, \
+                       N, C, w.lp);                                                                                                 \
+    DS2_CHECK_LAUNCH();                                                                                                             \
+    if (pairs)                                                                                                                      \
+      hipLaunchKernelGGL((k_ctc_recursion_pairs<PAIRS_K, true>), grid, dim3(64 * pw), 0, st, targets, target_offsets,               \
+                         input_lengths, target_lengths, Tp, blank, Lmax, CPT, nll, w.lp, w.alpha, w.beta, w.ll);                    \
+    else                                                                                                                            \
+      hipLaunchKernelGGL((k_ctc_recursion<CPT, true>), grid, dim3(REC_THREADS), shm, st, targets, target_offsets, input_lengths,    \
+                         target_lengths, Tp, blank, Lmax, nll, w.lp, w.alpha, w.beta, w.ll);                                        \
+    DS2_CHECK_LAUNCH();                                                                                                             \
+  }
+  if (CP == 32) DS2_CTC_MULTI_FWD(32)
+  else if (CP == 64) DS2_CTC_MULTI_FWD(64)
+  else if (CP == 128) DS2_CTC_MULTI_FWD(128)
+  else DS2_CTC_MULTI_FWD(256)
+#undef DS2_CTC_MULTI_FWD
+  return 0;
+}
+
+int ds2_ctc_multi_backward(const int* targets, const int* target_offsets, const int* target_lengths, const int* input_lengths, int Tp,
+                           int N, int R, int C, int blank, int max_target_len, const float* weights, float* dlogits, long ldg,
+                           float* ws, ds2_stream_t st_) {
+  hipStream_t st = (hipStream_t)st_;
+  DS2_REQUIRE(ctc_multi_args(Tp, N, R, C, max_target_len) && blank >= 0 && blank < C && ldg >= C, DS2_ERR_ARG);
+  DS2_REQUIRE(targets && target_offsets && target_lengths && input_lengths && weights && dlogits && ws, DS2_ERR_ARG);
+  const int CP = ctc_class_stride(C);
+  const int Lmax = 2 * max_target_len + 2;
+  const CtcMultiWs w = ctc_multi_ws(ws, Tp, N, R, C, max_target_len, 1);
+  const dim3 grid(ds2_cdiv(Tp, GRAD_FRAMES), N), block(GRAD_WAVES * 64);
+  if (C > 256) {
+    const size_t shm_g = (size_t)GRAD_WAVES * CP * 4;
+    DS2_REQUIRE(shm_g <= 160 * 1024, DS2_ERR_ARG);
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    dev = dev >= 0 && dev < DS2_MAX_DEVICES ? dev : 0;
+    static size_t attr_g[DS2_MAX_DEVICES];
+    if (attr_g[dev] < shm_g) {
+      (void)hipFuncSetAttribute((const void*)k_ctc_gradient_big<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm_g);
+      attr_g[dev] = shm_g;
+    }
+    hipLaunchKernelGGL(k_ctc_gradient_big<true>, grid, block, shm_g, st, targets, target_offsets, input_lengths, target_lengths, Tp, N, C,
+                       blank, Lmax, CP, 1.f, dlogits, ldg, w.lp, w.alpha, w.beta, w.ll, weights, R);
+    DS2_CHECK_LAUNCH();
+    return 0;
+  }
+#define DS2_CTC_MULTI_BWD(CPT)                                                                                                      \
+  hipLaunchKernelGGL((k_ctc_gradient<CPT, true>), grid, block, 0, st, targets, target_offsets, input_lengths, target_lengths, Tp,  \
+                     N, C, blank, Lmax, 1.f, dlogits, ldg, w.lp, w.alpha, w.beta, w.ll, weights, R);
+  if (CP == 32) DS2_CTC_MULTI_BWD(32)
+  else if (CP == 64) DS2_CTC_MULTI_BWD(64)
+  else if (CP == 128) DS2_CTC_MULTI_BWD(128)
+  else DS2_CTC_MULTI_BWD(256)
+#undef DS2_CTC_MULTI_BWD
   DS2_CHECK_LAUNCH();
   return 0;
 }

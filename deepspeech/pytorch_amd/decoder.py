@@ -498,6 +498,22 @@ class BeamCTCDecoder:
         return ops.beam_search(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob, lm, hot,
                                _words=words)
 
+    def nbest_device(self, probs, sizes, nbest):
+        """The label rows of the best `nbest` beams of every clip, left on the device for the training step (mwer.MWERLoss):
+        tokens [nbest][N][T'] int32 and lens [nbest][N] int32, rank-major (row r * N + n, ds2_error_counts' convention), lens = -1
+        where the search's score is +inf (fewer beams alive than asked for); entries past a row's length are not initialised.  The search runs in the form this decoder is set up
+        for (plain, LM, character LM, hot words); only the label rows are used, so scores and frames stay behind.  Nothing
+        travels to the host."""
+        if not 1 <= int(nbest) <= self.beam_width:
+            raise ValueError("nbest must be in [1, beam_width=%d], got %r" % (self.beam_width, nbest))
+        if not (torch.is_tensor(probs) and probs.is_cuda):
+            raise ValueError("nbest_device needs a HIP device tensor; there is no CPU fallback")
+        from .mwer import rank_major
+        K = int(nbest)
+        buf, lens, scores = ops.beam_search_device(probs, sizes, self.blank_index, self.beam_width, self.cutoff_top_n, self.cutoff_prob,
+                                                   self._lm_args(probs.device), self._hot_args(probs.device))
+        return rank_major(buf[0], lens, scores[0], K)
+
     def decode_beams_detailed(self, probs, sizes=None):
         """(strings, offsets, scores, acoustic): decode_beams' three values and the acoustic -log p of the same beams.  With an
         LM, scores = acoustic - lm (the total that ranked the beams); without one the two are equal."""

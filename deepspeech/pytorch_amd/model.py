@@ -1441,7 +1441,19 @@ class DeepSpeech(_Base):
             ops.poll_persistent_error(inputs.device)      # a sweep that timed out in an earlier step raises here (no host sync)
         input_sizes = input_percentages.mul_(int(inputs.size(3))).int()       # model.py:243
         logits, output_sizes, _, lens_dev, N, Tp = self._logits(inputs, input_sizes)
+        if self._training_loss is not None:
+            return self._training_loss.from_logits(logits, targets, lens_dev, target_sizes, N, Tp, len(self.labels), self.blank_index)
         return _CtcFn.apply(logits, targets, lens_dev, target_sizes, N, Tp, len(self.labels), self.blank_index)
+
+    _training_loss = None          # attach_training_loss: None = the CTC criterion above
+
+    def attach_training_loss(self, loss=None):
+        """Swap the objective of training_step: an object with ``from_logits(logits [T'*N][ld], targets, lens_dev, target_sizes, N,
+        Tp, Cc, blank)`` -- the arguments of _CtcFn.apply -- that returns a scalar differentiable with respect to the logits, e.g.
+        mwer.MWERLoss.  None restores the CTC criterion.  Nothing else in the step changes."""
+        if loss is not None and not callable(getattr(loss, "from_logits", None)):
+            raise ValueError("attach_training_loss takes None or an object with from_logits(...), got %r" % (loss,))
+        self._training_loss = loss
 
     def validation_step(self, batch, batch_idx):
         # model.py:251-271, statement for statement.  The reference's `autocast(enabled=self.precision == 16)` is fp16

@@ -959,6 +959,25 @@ def beam_search(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm=N
     return _beam_to_host(buf, lens, scores, N, B, plain=plain)
 
 
+def beam_search_device(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, lm=None, hot=None):
+    """beam_search without the trip to the host: the same checks and the same launch, and the tensors of _beam_outputs come back as
+    they are -- buf (2, N, B, T') int32 = tokens and offsets, lens (N, B) int32, scores (2, N, B) f32 = ranking and acoustic (the
+    plain form leaves the second plane unwritten; a rank with no beam alive has score +inf).  probs needs frames (N, T' > 0)."""
+    N, T, Cc = probs.shape
+    B, top_n, lm, hot = _beam_settings(Cc, probs.device, beam_width, cutoff_top_n, blank, lm, hot)
+    if N == 0 or T == 0:
+        raise ValueError("beam_search_device needs at least one clip and one frame, got probs of shape %s" % (tuple(probs.shape),))
+    if not probs.is_cuda:
+        raise ValueError("beam_search_device needs a HIP device tensor; there is no CPU fallback")
+    probs = _f32_classes(probs)
+    dev = probs.device
+    sz = sizes.to(dev, torch.int32) if sizes is not None else None
+    buf, lens, scores = _beam_outputs(N, B, T, dev)
+    ws = torch.empty(query("ds2_beam_ws_bytes", N, T, B), dtype=torch.uint8, device=dev)
+    _beam_launch(probs, sz, blank, B, top_n, cutoff_prob, lm, hot, buf, lens, scores, ws)
+    return buf, lens, scores
+
+
 def beam_decode(probs, sizes, blank, beam_width, cutoff_top_n, cutoff_prob, _words=None):
     """CTC prefix beam search without a language model (ds2_beam_decode).  probs: (N, T', C) CUDA tensor of probabilities (any
     strides with a contiguous class dimension); sizes: [N] int tensor or None (= T').  Returns host lists: tokens[n][b] (labels
@@ -1706,7 +1725,115 @@ def ctc_loss_grad(logits, targets_i32, target_offsets, input_lengths, target_len
     return loss, nll, dlogits
 
 
-CTC_ALIGN_MAX_TARGET_LEN = 2047      # ds2_ctc_align: labels of one target
+class CtcMultiState:
+    """what ctc_multi_forward(want_grad=True) keeps for ctc_multi_backward: the label rows, the shapes and the workspace"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _ctc_multi_rows(logits, rows, row_lens, input_lengths, Tp, N, Cc, blank):
+    """the argument checks of ctc_multi_forward; returns (rows [R][N][ld] int32, lens [R*N] int32, offsets [R*N], input lengths)"""
+    if not (torch.is_tensor(logits) and logits.is_cuda and logits.dtype == torch.float32 and logits.dim() == 2
+            and logits.stride(1) == 1):
+        raise ValueError("logits must be a float32 HIP device tensor [Tp*N][ld] with contiguous classes")
+    if Tp < 1 or N < 1 or logits.shape[0] != Tp * N or not 0 < Cc <= logits.shape[1]:
+        raise ValueError("logits has shape %s for Tp = %d, N = %d, %d classes" % (tuple(logits.shape), Tp, N, Cc))
+    if not 0 <= int(blank) < Cc:
+        raise ValueError("blank must be a label in [0, %d), got %r" % (Cc, blank))
+    if not (torch.is_tensor(rows) and rows.is_cuda and rows.dim() == 3 and rows.shape[1] == N and rows.shape[0] >= 1):
+        raise ValueError("rows must be a HIP device tensor of label rows [R][N][ld] with N = %d" % N)
+    dev = logits.device
+    R, _, ld = rows.shape
+    rows = rows.to(torch.int32).contiguous()
+    if ld == 0:                                             # empty rows only: the kernels still take a valid pointer
+        rows = torch.zeros((R, N, 1), dtype=torch.int32, device=dev)
+    lens = torch.as_tensor(row_lens).to(dev, torch.int32).reshape(-1).contiguous()
+    if lens.shape[0] != R * N:
+        raise ValueError("row_lens has %d entries for %d x %d rows" % (lens.shape[0], R, N))
+    il = torch.as_tensor(input_lengths).to(dev, torch.int32).reshape(-1).contiguous()
+    if il.shape[0] != N:
+        raise ValueError("input_lengths has %d entries for %d clips" % (il.shape[0], N))
+    offs = torch.arange(R * N, dtype=torch.int32, device=dev) * rows.shape[2]
+    return rows, lens, offs, il
+
+
+def ctc_multi_forward(logits, rows, row_lens, input_lengths, Tp, N, Cc, blank, want_grad=False, max_target_len=None,
+                      recursion=None):
+    """Exact CTC -log p(y | x) of several label rows per clip against the same frames (ds2_ctc_multi_forward): one log-softmax
+    per clip, one alpha (and, with want_grad, beta) recursion per row.  logits [Tp*N][ld] f32 (row = t*N + n); rows [R][N][ld]
+    int device tensor of labels, row_lens [R][N] their lengths (negative = the row is absent), rank-major as ds2_error_counts
+    takes them; input_lengths [N].  max_target_len: the longest row, where the caller knows it (it sizes the workspace; default
+    the rows' width).  Returns (nll [R][N] f32: +inf for absent and infeasible rows and clips without frames, state): state is
+    None without want_grad, else what ctc_multi_backward takes."""
+    rows, lens, offs, il = _ctc_multi_rows(logits, rows, row_lens, input_lengths, Tp, N, Cc, blank)
+    dev = logits.device
+    R, ld = rows.shape[0], rows.shape[2]
+    mtl = ld if max_target_len is None else int(max_target_len)
+    if not 0 <= mtl <= ld:
+        raise ValueError("max_target_len must be in [0, %d], got %r" % (ld, max_target_len))
+    rec = int(CTC_RECURSION if recursion is None else recursion)
+    if rec not in (0, 1):
+        raise ValueError("ctc_multi_forward runs recursion 0 (pair tiles) or 1 (four waves), got %r" % (rec,))
+    nws = query("ds2_ctc_multi_ws_floats", Tp, N, R, Cc, mtl, int(bool(want_grad)))
+    if nws < 0:
+        raise ValueError("ds2_ctc_multi_forward refuses Tp = %d, N = %d, R = %d, %d classes, %d labels" % (Tp, N, R, Cc, mtl))
+    ws = torch.empty(nws, dtype=torch.float32, device=dev)
+    nll = torch.empty((R, N), dtype=torch.float32, device=dev)
+    call("ds2_ctc_multi_forward", P(logits), logits.stride(0), P(rows), P(offs), P(lens), P(il), Tp, N, R, Cc, int(blank), mtl,
+         int(bool(want_grad)), P(nll), P(ws), rec, S())
+    if not want_grad:
+        return nll, None
+    return nll, CtcMultiState(rows=rows, offs=offs, lens=lens, il=il, Tp=Tp, N=N, R=R, Cc=Cc, blank=int(blank), mtl=mtl, ws=ws)
+
+
+def ctc_multi_backward(state, weights, ldg):
+    """dlogits [Tp*N][ldg] f32 = per clip, the sum over its rows in rank order of weights[r][n] * d nll / d logits, log-softmax
+    backward fused (ds2_ctc_multi_backward).  state: ctc_multi_forward(want_grad=True)'s; weights [R][N] f32 on the device.  Rows
+    whose nll is +inf add nothing whatever their weight; every row and column of dlogits is written."""
+    if not isinstance(state, CtcMultiState):
+        raise ValueError("state must come from ctc_multi_forward(want_grad=True)")
+    s = state
+    if not (torch.is_tensor(weights) and weights.is_cuda and weights.dtype == torch.float32 and weights.numel() == s.R * s.N):
+        raise ValueError("weights must be a float32 HIP device tensor of %d x %d entries" % (s.R, s.N))
+    if int(ldg) < s.Cc:
+        raise ValueError("ldg = %r is narrower than the %d classes" % (ldg, s.Cc))
+    w = weights.contiguous()
+    dlogits = torch.empty((s.Tp * s.N, int(ldg)), dtype=torch.float32, device=w.device)
+    call("ds2_ctc_multi_backward", P(s.rows), P(s.offs), P(s.lens), P(s.il), s.Tp, s.N, s.R, s.Cc, s.blank, s.mtl, P(w), P(dlogits),
+         int(ldg), P(s.ws), S())
+    return dlogits
+
+
+def mwer_weights(nll, err, K, has_ref, ce_weight):
+    """The MWER rule on the device (ds2_mwer_weights).  nll [(K + has_ref)][N] f32 of ctc_multi_forward, err [K][N] int32 error
+    counts of the K hypothesis ranks (None when K = 0).  Returns device tensors (weights, same shape as nll; risk [N]; nll_ref [N];
+    loss [1])."""
+    if not (torch.is_tensor(nll) and nll.is_cuda and nll.dtype == torch.float32 and nll.dim() == 2):
+        raise ValueError("nll must be a float32 HIP device tensor [ranks][N]")
+    K, has_ref = int(K), bool(has_ref)
+    R, N = nll.shape
+    if K < 0 or R != K + int(has_ref) or R < 1 or N < 1:
+        raise ValueError("nll has %d ranks of %d clips for K = %d hypotheses%s" % (R, N, K, " and the reference" if has_ref else ""))
+    ce_weight = float(ce_weight)
+    if not 0.0 <= ce_weight <= 3.4e38:
+        raise ValueError("ce_weight must be a finite value >= 0, got %r" % (ce_weight,))
+    if K > 0:
+        if not (torch.is_tensor(err) and err.is_cuda and err.numel() == K * N):
+            raise ValueError("err must be a HIP device tensor of %d x %d error counts" % (K, N))
+        err = err.to(torch.int32).contiguous()
+    else:
+        err = None
+    dev = nll.device
+    nll = nll.contiguous()
+    weights = torch.empty_like(nll)
+    out = torch.empty(2 * N + 1, dtype=torch.float32, device=dev)
+    risk, nll_ref, loss = out[:N], out[N:2 * N], out[2 * N:]
+    call("ds2_mwer_weights", P(nll), P(err), N, K, int(has_ref), ce_weight, P(weights), P(risk), P(nll_ref), P(loss), S())
+    return weights, risk, nll_ref, loss
+
+
+CTC_ALIGN_MAX_TARGET_LEN = 2047     # ds2_ctc_align: labels of one target
 CTC_ALIGN_MODES = {"logits": 0, "probs": 1, "log_probs": 2}
 
 

@@ -313,6 +313,42 @@ int ds2_ctc_loss_grad(const float* logits, long ldl, const int* targets, const i
                       const int* target_lengths, int Tp, int N, int C, int blank, int max_target_len, float grad_scale,
                       float* nll, float* loss_sum, float* dlogits, long ldg, float* ws, int recursion, ds2_stream_t stream);
 
+/* ---- multi-hypothesis CTC: several label rows per clip against the same frames, one gradient (mwer.py) ------------------------
+ * R rows per clip, P = R * N rows in all, rank-major: row p = r * N + n belongs to clip n = p % N (ds2_error_counts' convention).
+ * logits, input_lengths [N], blank as for ds2_ctc_loss_grad; targets is the flat int32 label array with target_offsets[P] and
+ * target_lengths[P] (a padded [R][N][ld] buffer is target_offsets[p] = p * ld).  A row with target_lengths[p] < 0 is absent; one
+ * longer than max_target_len is treated as absent.
+ * ds2_ctc_multi_forward: the log-softmax once per clip, then the alpha recursion of every row (grid clip x direction x rank);
+ * with want_grad also beta, and the rows stay in ws for ds2_ctc_multi_backward.  nll[p] = -log p(y_p | x_n); +inf for an absent
+ * row, an infeasible row and a clip without frames (NOT zero_infinity's 0: the caller's softmax over a clip's rows needs the +inf).
+ * want_grad = 0 gives the same nll bits.  recursion: 0 = the pair-tile kernel (the four-wave kernel beyond 783 labels), 1 = always
+ * the four-wave kernel; same bits.  R = 1 gives ds2_ctc_loss_grad's nll bits.
+ * ds2_ctc_multi_backward: dlogits[t*N + n][:] = sum over the rows p of clip n, in increasing r, of weights[p] * d nll_p / d logits
+ * (log-softmax backward fused).  Rows whose nll is +inf contribute nothing whatever their weight (NaN and infinite weights
+ * included: they are not read).  Every row of dlogits is written: frames past a clip's length and columns C .. ldg are zero.  The
+ * order of additions is fixed: every launch gives the same bits, and R = 1 with weight 1 gives ds2_ctc_loss_grad(grad_scale = 1)'s.
+ * It takes the arguments ds2_ctc_multi_forward(want_grad = 1) was called with and its ws.
+ * ws: ds2_ctc_multi_ws_floats(...) floats, 8-byte aligned (-1 for arguments the entries refuse): [N][Tp][CP] log-probs, P (rounded
+ * up to even) row log-likelihoods, and with want_grad 2 * (P * Tp * (2 max_target_len + 2) + 1) floats of alpha / beta rows. */
+long ds2_ctc_multi_ws_floats(int Tp, int N, int R, int C, int max_target_len, int want_grad);
+int ds2_ctc_multi_forward(const float* logits, long ldl, const int* targets, const int* target_offsets, const int* target_lengths,
+                          const int* input_lengths, int Tp, int N, int R, int C, int blank, int max_target_len, int want_grad,
+                          float* nll, float* ws, int recursion, ds2_stream_t stream);
+int ds2_ctc_multi_backward(const int* targets, const int* target_offsets, const int* target_lengths, const int* input_lengths, int Tp,
+                           int N, int R, int C, int blank, int max_target_len, const float* weights, float* dlogits, long ldg,
+                           float* ws, ds2_stream_t stream);
+
+/* ---- MWER weights: the expected error count over an n-best list and its derivative by the rows' nll (ds2_mwer.hip) ------------
+ * nll [P] f32 of ds2_ctc_multi_forward, P = (K + has_ref) * N rank-major: ranks 0 .. K-1 are hypotheses, rank K (iff has_ref) the
+ * reference.  err [K*N] int32: the error count of every hypothesis (ds2_error_counts), negative = not counted.  Per clip, in fp64
+ * with every output rounded to fp32 once: A = the ranks k < K with finite nll and err >= 0; s_k = -nll_k;
+ * phat_k = exp(s_k - max_A s) / sum_A exp(s_j - max_A s); ebar = sum_A phat_k err_k; risk[n] = ebar (0 when A is empty);
+ * weights[k*N + n] = -phat_k (err_k - ebar) = d risk / d nll_k (0 outside A); weights[K*N + n] = ce_weight when the reference's nll
+ * is finite, else 0, and nll_ref[n] = that nll or 0 (zero_infinity).  The reference never joins the softmax.
+ * loss[0] = sum_n risk[n] + ce_weight * sum_n nll_ref[n], added in index order.  K = 0 needs has_ref; ce_weight >= 0 and finite. */
+int ds2_mwer_weights(const float* nll, const int* err, int N, int K, int has_ref, float ce_weight, float* weights, float* risk,
+                     float* nll_ref, float* loss, ds2_stream_t stream);
+
 /* ---- optimizer step (configure_optimizers, model.py:273-297; Lightning's gradient_clip_val, configs/an4.yaml:12) -----------
  * ds2_clip_coef: out[0] = global L2 norm of `count` fp32 gradient tensors, out[1] = min(1, max_norm / (norm + 1e-6)) -- the
  * coefficient torch.nn.utils.clip_grad_norm_ multiplies the gradients by; computed on the device, deterministic order.
